@@ -2,7 +2,7 @@
 """bench.py — query-doc pairs scored / second, ColBERT MaxSim (Q32 / D180 / dim128, bf16,
 1000 candidates per query; BASELINE.json configs[1]), on N MI355X GPUs of one node.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 
 `--gpus N` with N > 1 starts itself: when no torch.distributed environment is present the script re-executes
 under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...` (one process
@@ -14,10 +14,15 @@ A "step" = one pass of the hot path (mm_maxsim_fwd) over one resident batch of `
 HBM).  Every rank scores its own shard of queries (weak scaling, no data-path collective); with N > 1 one
 RCCL all-gather of the fp32 scores per step is part of the timed region (the ranking merge of SURVEY.md §8e).
 
-Prints ONE JSON line (rank 0).  `roofline`: algorithmic bytes per launch / average kernel
-time measured with HIP events on the launch stream; `cpu_baseline`: the torch CPU port of the reference's ops
-(oracle/torch_port.py) timed on this host's cores on a bounded sample of the same workload.  At N = 1 the line
-also carries `extra`: the reference's own batch layout through the same operator (`dropin_forward`: query
+Prints ONE JSON line (rank 0).  `ms_per_step`: host time of one timed step; `roofline`: algorithmic bytes per launch
+ / average kernel time measured with HIP events on the launch stream of the timed steps.
+
+A plain run sets up, runs W warm-up and K timed steps and prints the line, nothing else.  `--full` adds everything
+else the benchmark measures and checks: the HBM calibration before the warm-up, the `self_check` of the timed scores
+against the numpy oracle, the gather checks and the final sort with a process group, and at N = 1 `cpu_baseline`
+(the torch CPU port of the reference's ops, oracle/torch_port.py, timed on this host's cores on a bounded sample of
+the same workload; `--no-cpu-baseline` skips it) and `extra` (`--no-extras` skips it): the reference's own batch
+layout through the same operator (`dropin_forward`: query
 replicated per pair, HF int64 masks — what eval.py:108 hands to ColBERT.forward), and the other BASELINE.json
 configs on this GPU (`tk` configs[0] shapes at scale, `tkl` configs[2], `dot_topk` one rank's shard of
 configs[4]), each with its own roofline fraction, CPU leg and the rocprof summary it can be checked against.
@@ -25,6 +30,9 @@ configs[4]), each with its own roofline fraction, CPU leg and the rocprof summar
 `--only <leg>` runs ONE leg (headline | dropin_forward | published_checkpoint | all_pairs | tk | tkl | dot_topk |
 maxsim_fp32 | eval_batch) and prints it alone: the command tools/profile_round.sh puts under `rocprofv3 --kernel-trace`, so
 that every fraction in the line can be re-derived from a profile of the very code that produced it.
+
+`--dump-outputs DIR` writes the scores of the last timed step as DIR/scores.npy (float32; with a process group also
+DIR/gathered_scores.npy, the all-gathered scores).  The inputs are seeded, so two builds can be compared output for output.
 
 `--dry` (with `--backend gloo --device cpu`) exercises ONLY the launch + collective plumbing on a machine
 without GPUs (tests/test_bench_launch_cpu.py): scores are fabricated, `value` is null — never a measurement.
@@ -1423,8 +1431,14 @@ def main():
     ap.add_argument("--queries", type=int, default=256,
                     help="queries per GPU per step (x1000 candidates; 256 -> 11.8 GB of bf16 token embeddings resident)")
     ap.add_argument("--lengths", default="full", choices=["full", "msmarco"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the drop-in-layout / TK / TKL / dot-top-k legs (N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: HBM calibration, oracle self-check, CPU baseline and the "
+                         "extra legs (without it a run only sets up, warms up, times the K steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the scores of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the drop-in-layout / TK / TKL / dot-top-k legs "
+                                                             "(N = 1 only)")
     ap.add_argument("--backend", default=None, choices=["nccl", "gloo"])
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"])
     ap.add_argument("--force-dist", action="store_true",
@@ -1533,11 +1547,11 @@ def main():
             merge(s)
         return s
 
-    # The box's own stream rate over the SAME document tensor is measured first (N = 1): the calibration legs keep the device
-    # at its working clocks, then exactly W warm-up steps and the K timed steps follow — no further untimed steps (rounds 3-5
-    # ran ~40 ms of priming launches between warm-up and timing).
+    # --full: the box's own stream rate over the SAME document tensor is measured first (N = 1): the calibration legs keep the
+    # device at its working clocks, then exactly W warm-up steps and the K timed steps follow — no further untimed steps
+    # (rounds 3-5 ran ~40 ms of priming launches between warm-up and timing).
     cal = None
-    if world == 1 and dev.type == "cuda" and not args.dry:
+    if args.full and world == 1 and dev.type == "cuda" and not args.dry:
         try:
             cal = extra_hbm_calibration(d, 10, None)
         except Exception as e:
@@ -1568,9 +1582,18 @@ def main():
     t = time.perf_counter() - t0
     kern_ms = sum(a.elapsed_time(b) for a, b in ev) / len(ev) if use_ev else None
 
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: this rank's scores [nq * 1000] and, with a process
+        # group, the gathered scores of all ranks (float32; the inputs are seeded, so two builds can be compared 1:1)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), s.float().cpu().numpy())
+        if use_dist or config4:
+            np.save(os.path.join(args.dump_outputs, "gathered_scores.npy"), all_scores.float().cpu().numpy())
+
     gather_matches = None
     sort_info = None
-    if config4:
+    if config4 and args.full:
         # this rank's rows of the gathered matrix must BE its local scores; the final ranking (core_metrics.py:502-511:
         # stable descending sort per query) is timed on its own, and a sampled query's ranking must equal the ranking of
         # its local scores alone (what a single rank would have produced)
@@ -1582,7 +1605,7 @@ def main():
         same = bool(torch.equal(order[row0 + qs], rank_candidates(s.view(nq, CANDS)[qs:qs + 1])[0]))
         sort_info = {"ms": sort_ms, "rows": int(all_scores.shape[0]), "what": "torch.sort(stable, descending) of the gathered "
                      "[n_total, 1000] scores, outside the timed steps", "ranking_equals_single_rank": same}
-    elif use_dist and not args.dry:      # the gathered tensor's slice of this rank must BE its local scores
+    elif use_dist and not args.dry and args.full:      # the gathered tensor's slice of this rank must BE its local scores
         gather_matches = bool(torch.equal(gathered[rank * B:(rank + 1) * B], s))
     tt = torch.tensor([t], dtype=torch.float64, device=dev)
     if use_dist:
@@ -1626,25 +1649,26 @@ def main():
             out["note"] = "launch/collective plumbing check only: scores fabricated, nothing measured"
             out["all_gather_verified"] = gather_ok
         else:
-            # the timed scores themselves, checked in-process against the oracle on one sampled query (checker only)
-            try:
-                import numpy as np
-                from oracle import np_oracle as O
-                from matchmaker_amd import synth as _synth
-                qi = nq // 2
-                got = s[qi * CANDS:(qi + 1) * CANDS].float().cpu().numpy()
-                ref = O.maxsim_paired(np.repeat(q[qi:qi + 1].float().cpu().numpy(), CANDS, axis=0),
-                                      d[qi * CANDS:(qi + 1) * CANDS].float().cpu().numpy(),
-                                      _synth.len_to_mask(q_len[qi:qi + 1].cpu(), Q).numpy().repeat(CANDS, axis=0),
-                                      _synth.len_to_mask(d_len[qi * CANDS:(qi + 1) * CANDS].cpu(), D).numpy())
-                err = float(np.abs(got - ref).max())
-                out["self_check"] = {"query": qi, "pairs": CANDS, "max_abs_err_vs_oracle": err, "tolerance": 1e-2,
-                                     "ok": bool(err <= 1e-2),
-                                     "same_order_as_oracle": bool((np.argsort(-got, kind="stable") == np.argsort(-ref, kind="stable")).mean() > 0.99)}
-                if err > 1e-2:
-                    out["value"] = None      # a fast kernel whose results differ from the reference's is not a measurement
-            except Exception as e:
-                out["self_check"] = {"error": repr(e)}
+            # --full: the timed scores themselves, checked in-process against the oracle on one sampled query (checker only)
+            if args.full:
+                try:
+                    import numpy as np
+                    from oracle import np_oracle as O
+                    from matchmaker_amd import synth as _synth
+                    qi = nq // 2
+                    got = s[qi * CANDS:(qi + 1) * CANDS].float().cpu().numpy()
+                    ref = O.maxsim_paired(np.repeat(q[qi:qi + 1].float().cpu().numpy(), CANDS, axis=0),
+                                          d[qi * CANDS:(qi + 1) * CANDS].float().cpu().numpy(),
+                                          _synth.len_to_mask(q_len[qi:qi + 1].cpu(), Q).numpy().repeat(CANDS, axis=0),
+                                          _synth.len_to_mask(d_len[qi * CANDS:(qi + 1) * CANDS].cpu(), D).numpy())
+                    err = float(np.abs(got - ref).max())
+                    out["self_check"] = {"query": qi, "pairs": CANDS, "max_abs_err_vs_oracle": err, "tolerance": 1e-2,
+                                         "ok": bool(err <= 1e-2),
+                                         "same_order_as_oracle": bool((np.argsort(-got, kind="stable") == np.argsort(-ref, kind="stable")).mean() > 0.99)}
+                    if err > 1e-2:
+                        out["value"] = None      # a fast kernel whose results differ from the reference's is not a measurement
+                except Exception as e:
+                    out["self_check"] = {"error": repr(e)}
             ab = algorithmic_bytes(nq, CANDS)
             achieved = ab / (kern_ms * 1e-3) / 1e9
             flop = 2.0 * B * Q * D * E
@@ -1662,10 +1686,10 @@ def main():
             if busy is not None:
                 out["roofline"]["mfma_util"]["pmc_busy_frac"] = busy[0]
                 out["roofline"]["mfma_util"]["pmc_source"] = f"profiles/{busy[1]} (SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE / 8 XCDs), tools/summarize_rocprof.py)"
-            out["timing"] = ("(N = 1: the hbm_calibration legs over the same tensor first,) exactly W warm-up steps, then the K timed "
-                             "steps between barrier + synchronize pairs, nothing in between; kernel_ms = mean HIP-event time of "
-                             "the K scoring launches")
-            if world == 1:      # CPU leg and extras are N = 1 figures; ranks > 0 would idle through them
+            out["timing"] = (("(N = 1: the hbm_calibration legs over the same tensor first,) " if args.full else "") +
+                             "exactly W warm-up steps, then the K timed steps between barrier + synchronize pairs, nothing in "
+                             "between; kernel_ms = mean HIP-event time of the K scoring launches")
+            if world == 1 and args.full:      # CPU leg and extras are N = 1 figures; ranks > 0 would idle through them
                 if cal is not None and "error" not in cal:   # what this box's memory system gives the same access pattern, same process
                     cal["headline_kernel_GBps"] = achieved
                     cal["headline_over_read_stream"] = achieved / cal["lds_dma_read_stream_nt"]["GBps"]

@@ -285,3 +285,45 @@ def make_tkl(embsize=300, mu=TK_MU, sigma=TK_SIGMA, saturation_type="embedding",
 def tkl_forward(model, q, d, q_mask, d_mask, secondary=False):
     with torch.no_grad():
         return model.forward(q, d, q_mask, d_mask, secondary)
+
+
+# --------------------------------------------------------------------------- Model.from_config on the YAML files
+FROM_CONFIG_CASES = [("TK", "tk.yaml"), ("TKL", "tkl.yaml"), ("TK_Sparse", "tk.yaml"), ("knrm", None), ("conv_knrm", None)]
+
+
+def train_config(model_yaml):
+    """The merged dictionary models/all.py:141-152 hands to Model.from_config: config/train/defaults.yaml,
+    non-bert-defaults.yaml and the model's own file (+ tk_att_proj_dim, read by CIKM20_TK_Sparse.from_config and absent
+    from the YAML files)."""
+    import yaml
+    cfg = {}
+    files = ["defaults.yaml", "non-bert-defaults.yaml"] + ([os.path.join("models", model_yaml)] if model_yaml else [])
+    for f in files:
+        with open(os.path.join(REFERENCE_ROOT, "config", "train", f)) as fh:
+            cfg.update(yaml.safe_load(fh) or {})
+    cfg.setdefault("tk_att_proj_dim", 32)
+    return cfg
+
+
+def from_config_reference(model_name, cfg, emb_dim):
+    """The real class of `model_name` built by its own from_config(cfg, emb_dim)."""
+    install_shims()
+    if model_name == "TK":
+        from matchmaker.models.published.ecai20_tk import ECAI20_TK as Ref
+    elif model_name == "TKL":
+        from matchmaker.models.published.sigir20_tkl import TKL_sigir20 as Ref
+    elif model_name == "TK_Sparse":
+        from matchmaker.models.published.cikm20_tk_sparse import CIKM20_TK_Sparse as Ref
+    elif model_name == "knrm":
+        from matchmaker.models.knrm import KNRM as Ref
+    else:
+        from matchmaker.models.conv_knrm import Conv_KNRM as Ref
+    # the reference builds its range vectors with torch.cuda.LongTensor: use the CPU branch
+    saved = Ref.__dict__.get("get_range_vector")
+    if saved is not None:
+        Ref.get_range_vector = lambda self, size, device: torch.arange(0, size, dtype=torch.long)
+    try:
+        return Ref.from_config(cfg, emb_dim)
+    finally:
+        if saved is not None:
+            Ref.get_range_vector = saved

@@ -18,6 +18,7 @@ sys.path.insert(0, ROOT)
 from oracle import ref_harness as R  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+MAX_FILE_BYTES = 1 << 20          # no committed file may be larger
 
 
 def bf16_round(x: torch.Tensor) -> torch.Tensor:
@@ -100,8 +101,16 @@ def gen_colbert_16bit_flow():
         dm = prefix_mask(d_len, D, torch.int64)
         dm[2, min(3, D - 1)] = 0                                         # a hole
         bits = (lambda x: x.view(torch.int16).numpy().view(np.uint16))
-        np.savez_compressed(os.path.join(OUT, f"flow16_{tag}_q{Q}_d{D}_e{E}.npz"),
-                            dtype=tag, q_bits=bits(q), d_bits=bits(d),
+        name = f"flow16_{tag}_q{Q}_d{D}_e{E}.npz"
+        d_bits = bits(d)
+        if d_bits.nbytes > MAX_FILE_BYTES:      # random 16-bit patterns do not compress: split, tests/util.load reassembles
+            for i, part in enumerate(np.array_split(d_bits, 2, axis=0)):
+                np.save(os.path.join(OUT, f"{name[:-4]}.d_bits.{i}.npy"), part)
+            d_bits = {}
+        else:
+            d_bits = {"d_bits": d_bits}
+        np.savez_compressed(os.path.join(OUT, name),
+                            dtype=tag, q_bits=bits(q), **d_bits,
                             q_mask=qm.numpy().astype(np.uint8), d_mask=dm.numpy().astype(np.uint8),
                             forward=R.colbert_forward_16bit(q, d, qm, dm).float().numpy(),
                             forward_aggregation=R.colbert_forward_aggregation(q, d).float().numpy(),
@@ -404,8 +413,115 @@ def gen_tkl_grad():
                             **extra, **grads, **sd)
 
 
+def gen_live_checks():
+    """The live-reference checks of tests/test_oracle_golden.py, recorded: their inputs and what the REAL classes return on
+    them, so the checks also run where the reference tree is absent."""
+    out = {}
+    torch.manual_seed(7)
+    B, Q, D, E = 6, 17, 45, 48
+    q, d = torch.randn(B, Q, E), torch.randn(B, D, E)
+    qm = (torch.rand(B, Q) > 0.3).long()
+    dm = (torch.rand(B, D) > 0.3).long()       # arbitrary (non-prefix) masks
+    out.update({"random.q": q.numpy(), "random.d": d.numpy(), "random.q_mask": qm.numpy(), "random.d_mask": dm.numpy(),
+                "random.forward": R.colbert_forward(q, d, qm, dm).numpy(),
+                "random.forward_inbatch_aggregation": R.colbert_forward_inbatch_aggregation(q, qm, d, dm).numpy()})
+    torch.manual_seed(3)
+    B, Q, D, E = 4, 9, 21, 16
+    q, d = torch.randn(B, Q, E), torch.randn(B, D, E)
+    qm = (torch.rand(B, Q) > 0.3).long()
+    dm = (torch.rand(B, D) > 0.3).long()
+    go = torch.randn(B)
+    qr, dr = q.clone().requires_grad_(True), d.clone().requires_grad_(True)
+    R.colbert_forward(qr, dr, qm, dm, grad=True).backward(go)
+    out.update({"grad.q": q.numpy(), "grad.d": d.numpy(), "grad.q_mask": qm.numpy(), "grad.d_mask": dm.numpy(),
+                "grad.grad_out": go.numpy(), "grad.grad_q": qr.grad.numpy(), "grad.grad_d": dr.grad.numpy()})
+    ref = R.make_knrm(11, seed=1)
+    torch.manual_seed(11)
+    x, m = torch.randn(2, 5, 8), torch.tensor([[1., 1, 1, 0, 0], [1, 0, 0, 0, 0]])
+    with torch.no_grad():
+        rep = ref.forward_representation(x, m)
+    out.update({"knrm.state_dict_keys": np.array(sorted(ref.state_dict().keys())), "knrm.mu": ref.mu.view(-1).numpy(),
+                "knrm.sigma": ref.sigma.view(-1).numpy(), "knrm.dense.weight": ref.state_dict()["dense.weight"].numpy(),
+                "knrm.x": x.numpy(), "knrm.mask": m.numpy(), "knrm.forward_representation": rep.numpy()})
+    np.savez_compressed(os.path.join(OUT, "live_checks.npz"), **out)
+
+
+def gen_from_config():
+    """tests/test_host_cpu.py's from_config check, recorded: the merged YAML settings of each model and the parameter /
+    buffer names and shapes the REAL class builds from them."""
+    import json
+    out = {}
+    for model_name, model_yaml in R.FROM_CONFIG_CASES:
+        cfg = R.train_config(model_yaml)
+        ref = R.from_config_reference(model_name, cfg, 300)
+        out[model_name] = {"config": cfg, "state_dict_shapes": {k: list(v.shape) for k, v in ref.state_dict().items()},
+                           "parameters": sorted(k for k, _ in ref.named_parameters())}
+    with open(os.path.join(OUT, "from_config.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+
+
+def gen_dropins_mirror():
+    """tests/test_host_cpu.py's state_dict / positional-feature check, recorded: the REAL TK's and TKL's state_dicts (seeded
+    constructors of ref_harness.make_tk / make_tkl, contextualiser on) and TKL's forward_representation on one input."""
+    ref_tk = R.make_tk(60, bypass_contextualizer=False, att_heads=6, att_ff_dim=32, max_length=50)
+    ref_tkl = R.make_tkl(64, bypass_contextualizer=False, att_heads=8, att_ff_dim=32)
+    torch.manual_seed(9)
+    x = torch.randn(2, 9, 64)
+    mk = torch.ones(2, 9)
+    mk[1, 5:] = 0
+    with torch.no_grad():
+        a, _ = ref_tkl.forward_representation(x, mk, ref_tkl.positional_features_q[:, :9, :])
+    out = {"tk." + k: v.numpy() for k, v in ref_tk.state_dict().items()}
+    out.update({"tkl." + k: v.numpy() for k, v in ref_tkl.state_dict().items()})
+    out.update({"x": x.numpy(), "mk": mk.numpy(), "tkl_forward_representation": a.numpy()})
+    np.savez_compressed(os.path.join(OUT, "dropins_tk_tkl.npz"), **out)
+
+
+def gen_idcm_live():
+    """tests/test_variants_cpu.py's IDCM comparisons, recorded: the REAL IDCM around a tiny DistilBERT, every parameter set
+    by tests/util.set_deterministic_params (so the drop-in is replayed with the same values, no weights stored), on seeded
+    token ids; one case per passage sampler and one without sampling."""
+    from tests import util
+    from tests.test_variants_cpu import _tiny_distilbert, _oracle_kernel_pool
+    from matchmaker_amd import ops
+    saved, ops.kernel_pool = ops.kernel_pool, _oracle_kernel_pool      # the oracle in the native operator's place (CPU)
+    out = {}
+    try:
+        for case, ctx_kind, sample_n, seed, lq, ld, q_lens, d_lens in [
+                ("tk", "tk", 3, 3, 10, 260, [10, 4, 7], [260, 33, 150]),
+                ("ck", "ck", 3, 3, 10, 260, [10, 4, 7], [260, 33, 150]),
+                ("ck_small", "ck-small", 3, 3, 10, 260, [10, 4, 7], [260, 33, 150]),
+                ("no_sampling", "ck", -1, 4, 9, 190, [9, 4, 6], [190, 20, 101])]:
+            ref = util.set_deterministic_params(R.make_idcm(_tiny_distilbert(), sample_n=sample_n, sample_context=ctx_kind,
+                                                            top_k_chunks=3, seed=5))
+            g = torch.Generator().manual_seed(seed)
+            B = len(q_lens)
+            q_mask = prefix_mask(torch.tensor(q_lens), lq, torch.long)
+            d_mask = prefix_mask(torch.tensor(d_lens), ld, torch.long)
+            q_ids = torch.randint(1, 200, (B, lq), generator=g) * q_mask
+            d_ids = torch.randint(1, 200, (B, ld), generator=g) * d_mask
+            with torch.no_grad():
+                res = ref.forward({"input_ids": q_ids, "attention_mask": q_mask},
+                                  {"input_ids": d_ids, "attention_mask": d_mask}, use_fp16=False, output_secondary_output=True)
+            rec = {"q_ids": q_ids.numpy(), "q_mask": q_mask.numpy(), "d_ids": d_ids.numpy(), "d_mask": d_mask.numpy(),
+                   "score": res[0].numpy(), "state_dict_keys": np.array(sorted(ref.state_dict().keys()))}
+            if sample_n > 0:                   # (score, second output, secondary dict, ...)
+                rec["scores_1"] = res[1].numpy()
+                rec["sampling_scores"] = res[2]["sampling_scores"].numpy()
+            else:                              # (score, secondary dict)
+                sec = res[1]
+                rec["bert_scores"] = sec["bert_scores"].numpy()
+                rec["packed_indices"] = sec["packed_indices"].numpy()
+            out.update({f"{case}.{k}": v for k, v in rec.items()})
+    finally:
+        ops.kernel_pool = saved
+    np.savez_compressed(os.path.join(OUT, "idcm_live.npz"), **out)
+
+
 GENERATORS = {"colbert": gen_colbert, "colbert_16bit_flow": gen_colbert_16bit_flow, "colbert_e2e": gen_colbert_e2e, "e2e_tk_tkl": gen_e2e_tk_tkl, "tk": gen_tk,
-              "knrm": gen_knrm, "conv_knrm": gen_conv_knrm, "tkl": gen_tkl, "tk_sparse": gen_tk_sparse, "idcm": gen_idcm, "tkl_grad": gen_tkl_grad}
+              "knrm": gen_knrm, "conv_knrm": gen_conv_knrm, "tkl": gen_tkl, "tk_sparse": gen_tk_sparse, "idcm": gen_idcm, "tkl_grad": gen_tkl_grad,
+              "live_checks": gen_live_checks, "from_config": gen_from_config,
+              "dropins_mirror": gen_dropins_mirror, "idcm_live": gen_idcm_live}
 
 if __name__ == "__main__":
     for name in (sys.argv[1:] or list(GENERATORS)):      # python gen_golden.py [generator ...]

@@ -40,6 +40,26 @@ def test_single_rank_dry_and_the_cpu_guard():
     assert r.returncode != 0 and "only valid with --dry" in (r.stderr + r.stdout)
 
 
+def test_dump_outputs_writes_the_last_timed_step_and_repeats_run_to_run(tmp_path):
+    """--dump-outputs DIR: the scores of the last timed step as float32 .npy; with a process group the gathered scores too.
+    The same arguments give the same inputs, hence the same files.  (--dry: fabricated rank-tagged scores.)"""
+    a, b = tmp_path / "a", tmp_path / "b"
+    for out in (a, b):
+        r, lines = _run("--gpus", "2", "--dry", "--device", "cpu", "--backend", "gloo", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = json.loads(lines[-1])
+        assert j["steps"] == 2 and "ms_per_step" in j
+    import numpy as np
+    n = j["config"]["queries_per_gpu"] * 1000
+    s, g = np.load(a / "scores.npy"), np.load(a / "gathered_scores.npy")
+    assert s.dtype == np.float32 and s.shape == (n,) and g.dtype == np.float32 and g.shape == (2 * n,)
+    np.testing.assert_array_equal(g, np.arange(2 * n, dtype=np.float32))
+    np.testing.assert_array_equal(s, g[:n])
+    for f in ("scores.npy", "gathered_scores.npy"):
+        np.testing.assert_array_equal(np.load(a / f), np.load(b / f))
+
+
 def _bench_module():
     import importlib.util
     spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))

@@ -131,32 +131,42 @@ def test_tkl_param_packing_layout():
     assert m.pack_params() is not v                  # invalidated by an in-place update
 
 
-@pytest.mark.skipif(not R.available(), reason="/root/reference not mounted (GPU box)")
 def test_dropins_mirror_reference_state_dict_and_positions():
+    """The real TK's / TKL's state_dicts and TKL's contextualiser output are recorded in tests/golden/dropins_tk_tkl.npz
+    (gen_golden.py gen_dropins_mirror); where the reference tree is present they come from live instances."""
+    from tests import util
     from matchmaker_amd.tk import ECAI20_TK, sinusoid_positions
     from matchmaker_amd.tkl import TKL_sigir20
-    ref_tk = R.make_tk(60, bypass_contextualizer=False, att_heads=6, att_ff_dim=32, max_length=50)
+    g = util.load("dropins_tk_tkl.npz")
+    recorded = lambda prefix: {k[len(prefix):]: torch.from_numpy(v) for k, v in g.items() if k.startswith(prefix)}
+    live = R.available()
+    if live:
+        ref_tk = R.make_tk(60, bypass_contextualizer=False, att_heads=6, att_ff_dim=32, max_length=50)
+        ref_tkl = R.make_tkl(64, bypass_contextualizer=False, att_heads=8, att_ff_dim=32)
+    tk_sd = ref_tk.state_dict() if live else recorded("tk.")
+    tkl_sd = ref_tkl.state_dict() if live else recorded("tkl.")
     mine = ECAI20_TK(60, MU, SIGMA, 6, 2, 32, 50, True, True)
-    assert {k: tuple(v.shape) for k, v in ref_tk.state_dict().items()} == \
+    assert {k: tuple(v.shape) for k, v in tk_sd.items()} == \
         {k: tuple(v.shape) for k, v in mine.state_dict().items()}
-    torch.testing.assert_close(mine.positional_features_q, ref_tk.positional_features_q, rtol=0, atol=0)
-    torch.testing.assert_close(mine.positional_features_d, ref_tk.positional_features_d, rtol=0, atol=0)
-    mine.load_state_dict(ref_tk.state_dict())        # strict load works
+    torch.testing.assert_close(mine.positional_features_q, tk_sd["positional_features_q"], rtol=0, atol=0)
+    torch.testing.assert_close(mine.positional_features_d, tk_sd["positional_features_d"], rtol=0, atol=0)
+    mine.load_state_dict(tk_sd)                      # strict load works
     # odd dimension: zero column appended
     assert sinusoid_positions(7, 3).shape == (1, 3, 7) and float(sinusoid_positions(7, 3)[0, :, -1].abs().sum()) == 0
 
-    ref_tkl = R.make_tkl(64, bypass_contextualizer=False, att_heads=8, att_ff_dim=32)
     mine_l = TKL_sigir20(64, MU, SIGMA, 8, 2, 32, 2000, True, True, "embedding")
-    assert {k: tuple(v.shape) for k, v in ref_tkl.state_dict().items()} == \
+    assert {k: tuple(v.shape) for k, v in tkl_sd.items()} == \
         {k: tuple(v.shape) for k, v in mine_l.state_dict().items()}
-    mine_l.load_state_dict(ref_tkl.state_dict())
+    mine_l.load_state_dict(tkl_sd)
     # the contextualiser half (stays PyTorch) is the same function as the reference's
-    x = torch.randn(2, 9, 64)
-    mk = torch.ones(2, 9)
-    mk[1, 5:] = 0
-    ref_tkl.eval(); mine_l.eval()
+    x, mk = torch.from_numpy(g["x"]), torch.from_numpy(g["mk"])
+    mine_l.eval()
     with torch.no_grad():
-        a, _ = ref_tkl.forward_representation(x, mk, ref_tkl.positional_features_q[:, :9, :])
+        if live:
+            ref_tkl.eval()
+            a, _ = ref_tkl.forward_representation(x, mk, ref_tkl.positional_features_q[:, :9, :])
+        else:
+            a = torch.from_numpy(g["tkl_forward_representation"])
         b, _ = mine_l.forward_representation(x, mk, mine_l.positional_features_q[:, :9, :])
     torch.testing.assert_close(a, b)
 
@@ -268,60 +278,73 @@ def test_conv_knrm_block_decomposition_matches_the_real_class():
     np.testing.assert_allclose(score, g["score"], atol=2e-5, rtol=1e-4)
 
 
-@pytest.mark.skipif(not R.available(), reason="needs the reference tree (config files + real classes)")
-@pytest.mark.parametrize("model_name,model_yaml", [("TK", "tk.yaml"), ("TKL", "tkl.yaml"), ("TK_Sparse", "tk.yaml"),
-                                                   ("knrm", None), ("conv_knrm", None)])
+@pytest.mark.parametrize("model_name,model_yaml", R.FROM_CONFIG_CASES)
 def test_from_config_on_the_reference_yaml_files_builds_the_same_parameters(model_name, model_yaml):
     """models/all.py:141-152 builds these models with Model.from_config(config, word_embedding_dim) from the merged
     YAML files under config/train/.  The drop-ins must accept the very same dictionaries and end up with the same
     parameters / buffers (names and shapes) as the real classes: checkpoints and param-group routing by name
-    (train.py:119-137) keep working."""
-    import os
-    import yaml
-    R.install_shims()
-    cfg = {}
-    files = ["defaults.yaml", "non-bert-defaults.yaml"] + ([os.path.join("models", model_yaml)] if model_yaml else [])
-    for f in files:
-        with open(os.path.join(R.REFERENCE_ROOT, "config", "train", f)) as fh:
-            cfg.update(yaml.safe_load(fh) or {})
-    cfg.setdefault("tk_att_proj_dim", 32)               # read by CIKM20_TK_Sparse.from_config, absent from the YAML files
-    emb_dim = 300
+    (train.py:119-137) keep working.  The settings and the real classes' names and shapes are recorded in
+    tests/golden/from_config.json (gen_golden.py gen_from_config); where the reference tree is present they are
+    re-derived live and a real instance's state_dict is loaded too."""
+    import json
+    from tests import util
     if model_name == "TK":
-        from matchmaker.models.published.ecai20_tk import ECAI20_TK as Ref
         from matchmaker_amd.tk import ECAI20_TK as Mine
     elif model_name == "TKL":
-        from matchmaker.models.published.sigir20_tkl import TKL_sigir20 as Ref
         from matchmaker_amd.tkl import TKL_sigir20 as Mine
     elif model_name == "TK_Sparse":
-        from matchmaker.models.published.cikm20_tk_sparse import CIKM20_TK_Sparse as Ref
         from matchmaker_amd.tk_sparse import CIKM20_TK_Sparse as Mine
     elif model_name == "knrm":
-        from matchmaker.models.knrm import KNRM as Ref
         from matchmaker_amd.knrm import KNRM as Mine
     else:
-        from matchmaker.models.conv_knrm import Conv_KNRM as Ref
         from matchmaker_amd.conv_knrm import Conv_KNRM as Mine
-
-    # the reference builds its range vectors with torch.cuda.LongTensor: use the CPU branch for the test
-    saved = Ref.__dict__.get("get_range_vector")
-    if saved is not None:
-        Ref.get_range_vector = lambda self, size, device: torch.arange(0, size, dtype=torch.long)
-    try:
-        ref = Ref.from_config(cfg, emb_dim)
-    finally:
-        if saved is not None:
-            Ref.get_range_vector = saved
+    with open(os.path.join(util.GOLDEN, "from_config.json")) as f:
+        rec = json.load(f)[model_name]
+    cfg = rec["config"]
+    emb_dim = 300
+    shapes = lambda m: {k: list(v.shape) for k, v in m.state_dict().items()}
+    if R.available():
+        cfg = R.train_config(model_yaml)
+        assert cfg == rec["config"]
+        ref = R.from_config_reference(model_name, cfg, emb_dim)
+        assert shapes(ref) == rec["state_dict_shapes"]
+        assert sorted(k for k, _ in ref.named_parameters()) == rec["parameters"]
     mine = Mine.from_config(cfg, emb_dim)
-    shapes = lambda m: {k: tuple(v.shape) for k, v in m.state_dict().items()}
-    assert shapes(ref) == shapes(mine)
-    assert {k for k, _ in ref.named_parameters()} == {k for k, _ in mine.named_parameters()}
-    mine.load_state_dict(ref.state_dict(), strict=True)
+    assert shapes(mine) == rec["state_dict_shapes"]
+    assert sorted(k for k, _ in mine.named_parameters()) == rec["parameters"]
+    mine.load_state_dict({k: torch.zeros(v) for k, v in rec["state_dict_shapes"].items()}, strict=True)
+    if R.available():
+        mine.load_state_dict(ref.state_dict(), strict=True)
 
 
-@pytest.mark.skipif(not R.available(), reason="needs the reference tree")
-def test_patch_matchmaker_rebinds_the_model_classes():
+def _stand_in_matchmaker(monkeypatch, table):
+    """Where the reference tree is absent: empty modules under the reference's module names, each holding a placeholder
+    for every class patch_matchmaker rebinds, and a models.all that imported them (sys.modules restored afterwards)."""
+    import sys
+    import types
+    all_mod = types.ModuleType("matchmaker.models.all")
+    for name in ("matchmaker", "matchmaker.models", "matchmaker.models.published"):
+        monkeypatch.setitem(sys.modules, name, types.ModuleType(name))
+    for ref_mod, ref_attr, _, _ in table:
+        mod = sys.modules.get(ref_mod)
+        if mod is None or ref_mod in ("matchmaker", "matchmaker.models", "matchmaker.models.published"):
+            mod = types.ModuleType(ref_mod)
+            monkeypatch.setitem(sys.modules, ref_mod, mod)
+        placeholder = type(ref_attr, (), {})
+        setattr(mod, ref_attr, placeholder)
+        setattr(all_mod, ref_attr, placeholder)
+    monkeypatch.setitem(sys.modules, "matchmaker.models.all", all_mod)
+    return all_mod
+
+
+def test_patch_matchmaker_rebinds_the_model_classes(monkeypatch):
+    """on the real modules where the reference tree is present, on stand-ins with the same names otherwise"""
     from matchmaker_amd import patch
-    R.install_shims()
+    all_mod = None
+    if R.available():
+        R.install_shims()
+    else:
+        all_mod = _stand_in_matchmaker(monkeypatch, patch._TABLE)
     import importlib
     saved = {}
     for ref_mod, ref_attr, _, _ in patch._TABLE:
@@ -341,6 +364,8 @@ def test_patch_matchmaker_rebinds_the_model_classes():
                                           "tk_att_ff_dim": 100, "max_doc_length": 200, "tk_use_diff_posencoding": True,
                                           "tk_mix_hybrid_context": True}, 300)
         assert type(m).__module__ == "matchmaker_amd.tk"
+        if all_mod is not None:                          # the `from ... import *` copies of models.all follow
+            assert all_mod.ECAI20_TK is ECAI20_TK and all_mod.TKL_sigir20 is TKL_sigir20
     finally:                                             # other tests drive the real classes
         for (ref_mod, ref_attr), obj in saved.items():
             setattr(importlib.import_module(ref_mod), ref_attr, obj)

@@ -42,8 +42,8 @@ def _line(out):
 
 def test_rccl_all_gather_world_size_1():
     util.require_gpu()
-    rc, out, err = _run([sys.executable, "bench.py", "--force-dist", "--queries", "8", "--steps", "3", "--warmup", "1",
-                         "--no-extras", "--no-cpu-baseline"], 300)
+    rc, out, err = _run([sys.executable, "bench.py", "--full", "--force-dist", "--queries", "8", "--steps", "3",
+                         "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 300)
     assert rc == 0, err[-2000:]
     j = _line(out)
     assert j is not None, out[-2000:]
@@ -62,7 +62,7 @@ def test_rccl_all_gather_two_ranks_on_one_device():
         port = s.getsockname()[1]
     rc, out, err = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                          "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2", "--one-device", "--queries", "4",
-                         "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 240)
+                         "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline"], 240)
     j = _line(out) if rc == 0 else None
     rec = os.path.join(ROOT, "gpurun_out")
     if os.environ.get("GRAFT_REPO_ROOT") or os.path.isdir(rec):
@@ -83,8 +83,8 @@ def test_config4_rehearsal_world_size_1_under_nccl():
     timed separately, a sampled query's ranking compared with the ranking of its local scores.  (The query total is
     shrunk so the shard is 2 GB instead of 40.)"""
     util.require_gpu()
-    rc, out, err = _run([sys.executable, "bench.py", "--config4", "--total-queries", "349", "--force-dist", "--steps", "3",
-                         "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 400)
+    rc, out, err = _run([sys.executable, "bench.py", "--full", "--config4", "--total-queries", "349", "--force-dist",
+                         "--steps", "3", "--warmup", "1", "--no-extras", "--no-cpu-baseline"], 400)
     assert rc == 0, err[-2000:]
     j = _line(out)
     assert j is not None, out[-2000:]

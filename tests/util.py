@@ -14,9 +14,23 @@ def bf16_bits_to_f32(bits: np.ndarray) -> np.ndarray:
     return (bits.astype(np.uint32) << 16).view(np.float32)
 
 
+def split_parts(name):
+    """<stem>.<key>.<i>.npy files beside <stem>.npz: an array too large for one committed file (> 1 MiB), split along
+    axis 0 -> {key: [part paths in order]}"""
+    stem = name[:-len(".npz")] + "."
+    parts = {}
+    for f in sorted(os.listdir(GOLDEN)):
+        if f.startswith(stem) and f.endswith(".npy"):
+            key, idx = f[len(stem):-len(".npy")].rsplit(".", 1)
+            parts.setdefault(key, []).append((int(idx), os.path.join(GOLDEN, f)))
+    return {k: [p for _, p in sorted(v)] for k, v in parts.items()}
+
+
 def load(name):
     z = np.load(os.path.join(GOLDEN, name), allow_pickle=False)
     out = {k: z[k] for k in z.files}
+    for k, paths in split_parts(name).items():
+        out[k] = np.concatenate([np.load(p, allow_pickle=False) for p in paths], axis=0)
     for k in list(out):
         if k.endswith("_bf16"):
             out[k[:-5]] = bf16_bits_to_f32(out[k])
@@ -240,3 +254,35 @@ def tkl_check_documents(score, win, peaks, s64, w64, chunk_scoring, label="tkl",
                 print(f"[tkl tie] {label} doc {b}: peaks {peaks[b].tolist()} vs oracle {tkl_region_search(w64[b])}, "
                       f"gap {gap:.3e} <= {gap_tol:.3e}; score {score[b]:.6f} oracle {s64[b]:.6f}")
     return tied, aw, worst
+
+
+def _hash_uniform(name, n):
+    """n deterministic values in [0, 1) for the parameter `name`: splitmix64 on integer indices, so every host and numpy
+    version produces the same bits (no RNG stream involved)."""
+    import zlib
+    with np.errstate(over="ignore"):
+        x = np.arange(n, dtype=np.uint64) + np.uint64(zlib.crc32(name.encode()) << 20)
+        x = x * np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        x = x ^ (x >> np.uint64(31))
+    return (x >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+def set_deterministic_params(model):
+    """Overwrites every parameter of `model` with values that depend on its name and shape only (fixtures recorded from one
+    class can be replayed on another class with the same parameter names): norms' weights ~1, biases ~0, everything else
+    uniform with std 1 / sqrt(fan-in).  Buffers are left as the constructor made them."""
+    import torch
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            u = _hash_uniform(name, p.numel()).reshape(tuple(p.shape))
+            if "norm" in name.lower() and name.endswith(".weight"):
+                v = 1.0 + 0.2 * (u - 0.5)
+            elif name.endswith("bias"):
+                v = 0.02 * (u - 0.5)
+            else:
+                fan_in = p.shape[-1] if p.dim() >= 2 else 1
+                v = (u - 0.5) * np.sqrt(12.0 / fan_in)
+            p.copy_(torch.from_numpy(v).to(p.dtype))
+    return model
