@@ -406,6 +406,51 @@ int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t n_docs, int
 int mm_topk_merge(const float* in_scores, const int64_t* in_ids, int nq, int n_in, int k,
                   float* out_scores, int64_t* out_ids, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * PACRR: cosine match matrix -> n-gram convolutions + channel max -> per-row k-max pooling, fused.
+ *
+ *   cos[i,j]  = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))            (allennlp cosine, pacrr.py:78)
+ *   path 0    = top-k of cos[i, :]                                         (pacrr.py:86)
+ *   path n    = top-k of max_c (b_n[c] + sum_{a,b < n} W_n[c][a][b] cos[i + a, j + b]), n = 2 .. N, with cos = 0 past
+ *               the matrix (ConstantPad2d n - 1 columns right, n - 1 rows below; Conv2d; MaxPool3d over the C channels;
+ *               pacrr.py:53-58, :88-91)
+ *   out[p, i, :] = path 0, path 2, .., path N, k values each, sorted descending   (per_query_results, pacrr.py:97)
+ *
+ * Replaces: PACRR.forward up to per_query_results   matchmaker/models/pacrr.py:68-97
+ *           (the dense layers of :101-112 stay torch; no mask enters, as in the reference)
+ *
+ *   q [n_queries, Q, E], d [n_pairs, D, E] float32, E a multiple of 4 (16-byte rows); pair p uses query p / pairs_per_query
+ *   conv_w    float32, the Conv2d weights of widths n = 2 .. N packed in width order, [C, n, n] each (convolutions.<n-2>.1.weight
+ *             without its in-channel axis): C * (4 + 9 + .. + N^2) floats; conv_b [N - 1, C] the biases in the same order.
+ *             Both may be NULL when N = 1.
+ *   out       [n_pairs, Q, k N] float32
+ *   saved_idx optional int32 [n_pairs, Q, k N]: for every output value its document column, | winning channel << 16 on the
+ *             conv paths — what mm_pacrr_bwd needs; NULL for inference (same values, bit for bit)
+ *   Ties: among equal values the lower column comes first (tie policy); the channel max picks the lowest channel.
+ *   Limits: 1 <= Q <= 64, k <= D <= 2048, 4 <= E <= 1024, 1 <= C <= 64, 1 <= N <= 5, 1 <= k <= 32; anything else returns
+ *   MM_EUNSUPPORTED before any launch.  The forward needs no workspace (workspace may be NULL); the backward needs
+ *   mm_pacrr_workspace_bytes() bytes (0 when N = 1).
+ */
+size_t mm_pacrr_workspace_bytes(int64_t n_pairs, int Q, int D, int C, int N, int k);
+
+int mm_pacrr_fwd(const float* q, const float* d, const float* conv_w, const float* conv_b, float* out, int32_t* saved_idx,
+                 int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of mm_pacrr_fwd (training: train.py:503-524 through pacrr.py:78-97).  The output values are piecewise a linear
+ * function of at most k (1 + 4 + .. + N^2) cosines per query row, selected by saved_idx: the backward recomputes those cosines
+ * (one dot product each) and pushes grad_out through the convolutions and the cosine's normalisation (the + 1e-13 included).
+ *   saved_idx   as written by mm_pacrr_fwd on the SAME inputs; grad_out [n_pairs, Q, k N]
+ *   grad_q      [n_pairs, Q, E]: per PAIR (with pairs_per_query > 1 the caller sums each query's rows)
+ *   grad_d      [n_pairs, D, E]; both fully written (rows without gradient are zeros)
+ *   grad_w      [n_pairs, C * (4 + .. + N^2)], grad_b [n_pairs, (N - 1) C]: per-pair contributions in conv_w / conv_b's packing
+ *               (sum over pairs on the host side: deterministic, no atomics); NULL allowed when N = 1
+ *   workspace   mm_pacrr_workspace_bytes(n_pairs, Q, D, C, N, k) bytes: the recomputed window cosines */
+int mm_pacrr_bwd(const float* q, const float* d, const float* conv_w, const int32_t* saved_idx, const float* grad_out,
+                 float* grad_q, float* grad_d, float* grad_w, float* grad_b,
+                 int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
+                 void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -772,3 +772,120 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
                                           out_i.data_ptr(), _stream(dev))
         _lib.check(rc, "mm_topk_merge")
     return out_s, out_i
+
+
+def _pacrr_params(weights, biases, C: int, dev):
+    """Packs the conv weights ([C, 1, n, n] or [C, n, n], widths 2 .. N in order) and biases ([C] each) into the two float
+    buffers of mm_pacrr_fwd: C * (4 + .. + N^2) weights, (N - 1) * C biases.  Returns (w, b) or (None, None) for N = 1."""
+    weights, biases = list(weights), list(biases)
+    if len(weights) != len(biases):
+        raise NativeError(f"pacrr: {len(weights)} weight tensors but {len(biases)} bias tensors")
+    if not weights:
+        return None, None
+    for i, (w, b) in enumerate(zip(weights, biases)):
+        n = i + 2
+        if w.numel() != C * n * n or b.numel() != C:
+            raise NativeError(f"pacrr: width {n} needs weight [{C}, 1, {n}, {n}] and bias [{C}], got "
+                              f"{tuple(w.shape)} / {tuple(b.shape)}")
+    _dev_check(*weights, *biases)
+    w = torch.cat([t.detach().reshape(-1) for t in weights]).to(device=dev, dtype=torch.float32).contiguous()
+    b = torch.cat([t.detach().reshape(-1) for t in biases]).to(device=dev, dtype=torch.float32).contiguous()
+    return w, b
+
+
+def _pacrr_shapes(q, d, pairs_per_query, k):
+    nq, Q, E = q.shape
+    B, D, E2 = d.shape
+    if E != E2:
+        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
+        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    if not (1 <= k <= 32) or not (k <= D <= 2048) or not (1 <= Q <= 64) or E > 1024:
+        # the reference's torch.topk raises for D < k (pacrr.py:86); the kernel's limits are in mm_native.h
+        raise NativeError(f"pacrr_kmax: Q = {Q}, D = {D}, E = {E}, k = {k} outside 1 <= Q <= 64, k <= D <= 2048, "
+                          f"E <= 1024, 1 <= k <= 32 (MM_EUNSUPPORTED)")
+    return nq, Q, E, B, D
+
+
+def pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, pairs_per_query: int = 1, save: bool = False):
+    """PACRR's match matrix + n-gram convolutions + k-max pooling (matchmaker/models/pacrr.py:78-97) in ONE launch
+    (mm_pacrr_fwd): per_query_results [n_pairs, Q, k N], paths 0, 2, .., N.
+
+    q [n_queries, Q, E], d [n_pairs, D, E] float32; pair p scores against query p // pairs_per_query.
+    weights / biases: the Conv2d parameters of widths 2 .. N (convolutions.<n-2>.1.weight [C, 1, n, n] / .bias [C]), N - 1
+    of each (empty for N = 1).  save=True also returns the int32 indices [n_pairs, Q, k N] (column | channel << 16) that
+    pacrr_kmax_bwd takes; the values are the same bits either way."""
+    dev = _dev_check(q, d)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("pacrr_kmax: float32 embeddings only (the reference cosine rejects bf16)")
+    nq, Q, E, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    weights, biases = list(weights), list(biases)
+    C = weights[0].shape[0] if weights else 1
+    N = len(weights) + 1
+    w, b = _pacrr_params(weights, biases, C, dev)
+    out = torch.empty((B, Q, k * N), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, Q, k * N), dtype=torch.int32, device=dev) if save else None
+    if B:
+        q, d, E = _pad_rows(q, d, 4)
+        L = _lib.lib()
+        with _on(dev):
+            rc = L.mm_pacrr_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None,
+                                b.data_ptr() if b is not None else None, out.data_ptr(),
+                                idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
+                                None, 0, _stream(dev))
+        _lib.check(rc, "mm_pacrr_fwd")
+    return (out, idx) if save else out
+
+
+def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor, grad_out: torch.Tensor, k: int,
+                   pairs_per_query: int = 1):
+    """Backward of pacrr_kmax (mm_pacrr_bwd): idx as returned by pacrr_kmax(..., save=True) on the same inputs, grad_out
+    [n_pairs, Q, k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w, grad_b) with grad_w /
+    grad_b lists shaped like `weights` / their biases ([C]), summed over the pairs in a fixed order (no atomics)."""
+    dev = _dev_check(q, d, idx, grad_out)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("pacrr_kmax_bwd: float32 embeddings only")
+    nq, Q, E0, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    weights = list(weights)
+    C = weights[0].shape[0] if weights else 1
+    N = len(weights) + 1
+    w, _ = _pacrr_params(weights, [t.new_zeros(C) for t in weights], C, dev)
+    if tuple(idx.shape) != (B, Q, k * N) or idx.dtype != torch.int32:
+        raise NativeError(f"pacrr_kmax_bwd: idx must be int32 {(B, Q, k * N)}, got {idx.dtype} {tuple(idx.shape)}")
+    go = grad_out.detach().to(torch.float32).contiguous()
+    if tuple(go.shape) != (B, Q, k * N):
+        raise NativeError(f"pacrr_kmax_bwd: grad_out must be {(B, Q, k * N)}, got {tuple(go.shape)}")
+    idx = idx.contiguous()
+    q, d, E = _pad_rows(q, d, 4)
+    S = sum(n * n for n in range(2, N + 1))
+    gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
+    gd = torch.empty((B, D, E), dtype=torch.float32, device=dev)
+    gw = torch.empty((B, C * S), dtype=torch.float32, device=dev)
+    gb = torch.empty((B, C * (N - 1)), dtype=torch.float32, device=dev)
+    if B:
+        L = _lib.lib()
+        with _on(dev):
+            wsb = L.mm_pacrr_workspace_bytes(B, Q, D, C, N, k)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+            rc = L.mm_pacrr_bwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(),
+                                go.data_ptr(), gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None,
+                                gb.data_ptr() if N > 1 else None, B, pairs_per_query, Q, D, E, C, N, k,
+                                ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
+        _lib.check(rc, "mm_pacrr_bwd")
+    if E != E0:
+        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
+    if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
+        pad = nq * pairs_per_query - B
+        if pad:
+            gq = torch.cat([gq, gq.new_zeros((pad, Q, E0))])
+        gq = gq.view(nq, pairs_per_query, Q, E0).sum(1)
+    gw, gb = gw.sum(0), gb.sum(0)
+    grad_w, grad_b, off = [], [], 0
+    for i, t in enumerate(weights):
+        n = i + 2
+        grad_w.append(gw[C * off:C * (off + n * n)].view(t.shape).clone())     # separate tensors (no views of one sum)
+        grad_b.append(gb[C * i:C * (i + 1)].clone())
+        off += n * n
+    return gq, gd, grad_w, grad_b

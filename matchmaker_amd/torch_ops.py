@@ -20,7 +20,7 @@ is — and the promoted `sum` returns fp32; the TK family stays fp32 — allennl
 The drop-in modules call `matchmaker_amd.ops` directly; these registrations are the boundary for callers
 that want dispatcher-level ops (torch.compile graphs, TorchScript-free export, other extensions).
 """
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -161,3 +161,53 @@ def _tkl_backward(ctx, g, _gwin):
 
 tkl_window_pool.register_autograd(_tkl_backward, setup_context=_tkl_setup)
 torch.library.register_autocast(_NS + "::tkl_window_pool", "cuda", torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- PACRR
+@torch.library.custom_op(_NS + "::pacrr_kmax", mutates_args=(), device_types="cuda")
+def pacrr_kmax(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor], k: int,
+               pairs_per_query: int) -> Tuple[Tensor, Tensor]:
+    """(pairs_per_query has no default: the autograd wrapper drops trailing arguments left at their defaults from the input
+    structure the backward must return.)  per_query_results [n_pairs, Q, k N] of PACRR (pacrr.py:78-97) and the int32 positions [n_pairs, Q, k N]
+    (column | channel << 16) the backward routes through; no gradient flows through the positions."""
+    out, idx = ops.pacrr_kmax(q, d, weights, biases, k, pairs_per_query=pairs_per_query, save=True)
+    return out, idx
+
+
+@pacrr_kmax.register_fake
+def _(q, d, weights, biases, k, pairs_per_query):
+    shape = (d.shape[0], q.shape[1], k * (len(weights) + 1))
+    return q.new_empty(shape, dtype=torch.float32), q.new_empty(shape, dtype=torch.int32)
+
+
+@torch.library.custom_op(_NS + "::pacrr_kmax_backward", mutates_args=(), device_types="cuda")
+def pacrr_kmax_backward(q: Tensor, d: Tensor, weights: List[Tensor], idx: Tensor, grad_out: Tensor, k: int,
+                        pairs_per_query: int = 1) -> Tuple[Tensor, Tensor, List[Tensor], List[Tensor]]:
+    gq, gd, gw, gb = ops.pacrr_kmax_bwd(q, d, weights, idx, grad_out, k, pairs_per_query=pairs_per_query)
+    return gq, gd, gw, gb
+
+
+@pacrr_kmax_backward.register_fake
+def _(q, d, weights, idx, grad_out, k, pairs_per_query=1):
+    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
+            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
+            [w.new_empty((w.shape[0],), dtype=torch.float32) for w in weights])
+
+
+def _pacrr_setup(ctx, inputs, output):
+    q, d, weights, biases, k, ppq = inputs
+    ctx.save_for_backward(q, d, output[1], *weights)
+    ctx.meta = (k, ppq, [b.shape for b in biases])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _pacrr_backward(ctx, g, _gidx):
+    q, d, idx, *weights = ctx.saved_tensors
+    k, ppq, bshapes = ctx.meta
+    gq, gd, gw, gb = torch.ops.mm_native.pacrr_kmax_backward(q, d, weights, idx, g.contiguous(), k, ppq)
+    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
+            [t.view(s) for t, s in zip(gb, bshapes)], None, None)
+
+
+pacrr_kmax.register_autograd(_pacrr_backward, setup_context=_pacrr_setup)
+torch.library.register_autocast(_NS + "::pacrr_kmax", "cuda", torch.float32)
