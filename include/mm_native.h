@@ -451,6 +451,51 @@ int mm_pacrr_bwd(const float* q, const float* d, const float* conv_w, const int3
                  int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CO-PACRR: PACRR's cosine -> n-gram convolutions + channel max -> per-row k-max, at four nested document views, with the
+ * context similarity of every selected column.
+ *
+ *   cos, path 0 .. path N    as mm_pacrr_fwd (co_pacrr.py:90, :110-136)
+ *   ctx[j]    = cosine(mean_i q_i, (1/6) sum_{t = j .. j+5, t < D} d_t)          (co_pacrr.py:98-101: mean over ALL Q rows;
+ *               ConstantPad1d((0, 5)) + AvgPool1d(6, stride 1), :65-68)
+ *   view i    = the first min(v_i, D) columns of a path, v_i = int(U * f_i), f = 0.25 / 0.5 / 0.75 / 1 (:74), computed by the
+ *               caller with Python's int(); columns at or past min(v_3, D) enter no list but still feed the conv halo and the
+ *               context windows of earlier columns
+ *   out[p, i, path, :] = top-k of view 0, .., view 3 (k values each, sorted descending), then ctx[column] of those 4k slots
+ *               in slot order (:111-126, :148-151); paths 0, 2, .., N                 (per_query_results, co_pacrr.py:158)
+ *
+ * Replaces: CO_PACRR.forward up to per_query_results   matchmaker/models/co_pacrr.py:79-158
+ *           (the idf softmax and the query shuffle of :160-166 are dead code there; the dense layers of :168-179 stay torch)
+ *
+ *   q, d, conv_w, conv_b  as mm_pacrr_fwd
+ *   view0..view3          the four view sizes, ascending (MM_EINVAL otherwise)
+ *   out       [n_pairs, Q, 8 k N] float32
+ *   saved_idx optional int32 [n_pairs, Q, N, 4 k]: document column | winning channel << 16 of every VALUE slot (the context
+ *             slots share them) — what mm_co_pacrr_bwd needs; NULL for inference (same values, bit for bit)
+ *   Ties: descending, lower column first, lowest channel: among equal values this also decides which
+ *   ctx[column] is gathered.
+ *   Limits: 1 <= Q <= 64, k <= D <= 2048, 4 <= E <= 1024 (a multiple of 4), 1 <= C <= 64, 1 <= N <= 5, 1 <= k <= 8,
+ *   view0 >= k (torch.topk raises in the reference otherwise); anything else returns MM_EUNSUPPORTED before any launch.
+ *   The forward needs no workspace.
+ */
+size_t mm_co_pacrr_workspace_bytes(int64_t n_pairs, int Q, int D, int E, int C, int N, int k);
+
+int mm_co_pacrr_fwd(const float* q, const float* d, const float* conv_w, const float* conv_b, float* out, int32_t* saved_idx,
+                    int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
+                    int view0, int view1, int view2, int view3, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Backward of mm_co_pacrr_fwd (training: train.py:503-524 through co_pacrr.py:90-158), one launch.
+ *   value slots    as mm_pacrr_bwd over the 4k slots of every (row, path); a column chosen by several views adds up
+ *   context slots  d(loss)/d(ctx[col]) through the cosine Jacobian of (qctx, dctx[col]): every query row receives 1/Q of
+ *                  d(loss)/d(qctx), document rows col .. min(col + 5, D - 1) 1/6 of d(loss)/d(dctx[col])
+ *   saved_idx, grad_out [n_pairs, Q, 8 k N]; grad_q [n_pairs, Q, E] per PAIR; grad_d [n_pairs, D, E]; grad_w / grad_b per-pair
+ *   contributions as mm_pacrr_bwd (NULL allowed when N = 1)
+ *   workspace   mm_co_pacrr_workspace_bytes(n_pairs, Q, D, E, C, N, k) bytes (never 0 for n_pairs > 0) */
+int mm_co_pacrr_bwd(const float* q, const float* d, const float* conv_w, const int32_t* saved_idx, const float* grad_out,
+                    float* grad_q, float* grad_d, float* grad_w, float* grad_b,
+                    int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
+                    int view0, int view1, int view2, int view3, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,11 @@ SIGNATURES = {
     "mm_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
     "mm_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mm_co_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
+    "mm_co_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz,
+                             _vp]),
+    "mm_co_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
+                             _vp, _sz, _vp]),
 }
 
 _lib = None

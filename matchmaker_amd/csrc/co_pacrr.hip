@@ -1,15 +1,15 @@
-// PACRR (matchmaker/models/pacrr.py:68-113): cosine match matrix -> n-gram convolutions + channel max -> per-row k-max
-// pooling, fused.  Forward: ONE launch per call, one workgroup (four wavefronts) per pair; the match matrix lives only in
-// LDS, as a ring of 64 document columns (two 32-column blocks: the block being pooled and the next one, whose first n - 1
-// columns are the convolutions' right halo).  Backward: ONE launch, one workgroup per pair (see pacrr_bwd_kernel).
+// CO-PACRR (matchmaker/models/co_pacrr.py:79-158): PACRR's cosine match matrix -> n-gram convolutions + channel max ->
+// per-row k-max pipeline, with four nested document views and a context similarity gathered at every selected column.
+// Forward: ONE launch per call, one workgroup (four wavefronts) per pair, PACRR's structure (csrc/pacrr.hip): the match
+// matrix lives in an LDS ring of 64 document columns.  Backward: ONE launch, one workgroup per pair.
 //
-// Arithmetic:
-//   cosine   <q_i, d_j> * 1/(|q_i| + 1e-13) * 1/(|d_j| + 1e-13); the dot on v_mfma_f32_32x32x2_f32 (exact fp32: a k-ordered
-//            fma chain), the four wavefronts split E and their partial tiles are summed in fixed order (deterministic);
-//   conv     an im2col product [C x n^2] x [n^2 x 32 positions] on the same fp32 MFMA, the accumulator initialised with the
-//            bias; the channel max is taken on the accumulators (lowest channel on ties, MaxPool3d's rule);
-//   top-k    per (query row, path) a sorted list of k (value, column | channel << 16) in LDS, updated by whole-wave
-//            insertions; ties keep the lower column first.
+// Additions to PACRR's forward:
+//   context  ctx[j] = cosine(mean_i q_i, (1/6) sum_{t = j .. j+5, t < D} d_t) for every column j below min(v_3, D), computed
+//            before the stream (one wavefront per column, lanes over E) and kept in LDS;
+//   views    the view sizes v_0 <= .. <= v_3 are nested prefixes of the stream: the block holding min(v_i, D) inserts its
+//            columns below it, copies the running list (values and ctx[col]) to view i's output slots, then inserts the rest.
+//            No column at or past min(v_3, D) is inserted; the stream goes on to the next block for the conv halo.
+// Ties (values and therefore contexts): descending, lower column first, lowest channel — PACRR's rule.
 #include "pacrr_device.h"
 
 namespace mm {
@@ -18,21 +18,24 @@ namespace {
 
 using namespace pacrr_dev;
 
-struct PacrrArgs {
+constexpr int kCoKmax = 8;   // 4 views x k <= 32 list lanes in the backward
+
+struct CoArgs {
   const float* q;
   const float* d;
   const float* w;   // packed conv weights: width n = 2 .. N, [C, n, n] each
   const float* b;   // packed biases: [N - 1, C]
-  float* out;       // [n_pairs, Q, k N]
-  int32_t* idx;     // optional [n_pairs, Q, k N]: column | channel << 16
+  float* out;       // [n_pairs, Q, N, 8k]: per path 4k values (views 0..3), then their 4k contexts
+  int32_t* idx;     // optional [n_pairs, Q, N, 4k]: column | channel << 16 of every value slot
   int64_t n_pairs, ppq;
   int Q, D, E, C, N, k;
+  int v0, v1, v2, v3;
 };
 
-// LDS layout of the forward (floats)
-struct FwdLds {
-  int rq, rd, dn, wt, bs, ring, part, tv, ti, total;
-  __host__ __device__ FwdLds(int Q, int C, int N, int k) {
+// LDS layout of the forward (floats); the query context aliases `part` (free until the first cosine block)
+struct CoFwdLds {
+  int rq, rd, dn, wt, bs, ring, part, tv, ti, ctx, total;
+  __host__ __device__ CoFwdLds(int Q, int D, int C, int N, int k) {
     const int nrt = (Q + 31) / 32;
     int o = 0;
     rq = o; o += kPQmax;
@@ -41,22 +44,25 @@ struct FwdLds {
     wt = o; o += C * tap_off(N + 1);
     bs = o; o += C * (N - 1);
     ring = o; o += (Q + kPNmax) * kRing;
-    part = o; o += 4 * nrt * 32 * 33;
+    part = o; o += 4 * nrt * 32 * 33;     // >= 4224 >= kPEmax
     tv = o; o += Q * N * k;
     ti = o; o += Q * N * k;
+    ctx = o; o += D;
     total = o;
   }
 };
 
-__global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
+__global__ void __launch_bounds__(256, 4) co_pacrr_fwd_kernel(CoArgs a) {
   extern __shared__ float lds[];
   const int Q = a.Q, D = a.D, E = a.E, C = a.C, N = a.N, k = a.k;
-  const FwdLds L(Q, C, N, k);
+  const CoFwdLds L(Q, D, C, N, k);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r32 = lane & 31, h = lane >> 5;
   const int64_t pair = blockIdx.x;
   const float* q = a.q + (pair / a.ppq) * (int64_t)Q * E;
   const float* d = a.d + pair * (int64_t)D * E;
   const int nrt = (Q + 31) / 32, nch = (E + 7) / 8, nb = (D + 31) / 32, S = tap_off(N + 1);
+  const int Dv = min(a.v3, D);                 // columns that enter a list
+  const int nbp = (Dv + 31) / 32;        // blocks that are pooled
   float* rq = lds + L.rq;
   float* rd = lds + L.rd;
   float* dn = lds + L.dn;
@@ -66,8 +72,10 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
   float* part = lds + L.part;
   float* tv = lds + L.tv;
   int* ti = (int*)(lds + L.ti);
+  float* ctx = lds + L.ctx;
+  float* qc = part;
 
-  // prologue: weights, biases, zero halo rows of the ring, query norms (one wavefront per row)
+  // prologue: weights, biases, zero halo rows of the ring, query norms (one wavefront per row), query context (:98)
   for (int i = tid; i < C * S; i += 256) wt[i] = a.w[i];
   for (int i = tid; i < C * (N - 1); i += 256) bs[i] = a.b[i];
   for (int i = tid; i < (Q + kPNmax) * kRing; i += 256) ring[i] = 0.0f;
@@ -77,10 +85,41 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
     s = wave_sum(s);
     if (lane == 0) rq[i] = 1.0f / (sqrtf(s) + kTiny);
   }
+  for (int e = tid; e < E; e += 256) {
+    float s = 0.0f;
+    for (int i = 0; i < Q; ++i) s += q[(int64_t)i * E + e];
+    qc[e] = s / (float)Q;
+  }
   __syncthreads();
 
-  for (int s = 0; s <= nb; ++s) {
-    // ---- cosine block s -> ring half (s & 1); s == nb: the zero columns past the document (ConstantPad2d)
+  // ---- context similarities ctx[j], j < Dv (:99-101): one wavefront per column, four elements per lane
+  {
+    float qq = 0.0f;
+    for (int e = 4 * lane; e < E; e += 256) {
+      qq += qc[e] * qc[e] + qc[e + 1] * qc[e + 1] + qc[e + 2] * qc[e + 2] + qc[e + 3] * qc[e + 3];
+    }
+    const float rqc = 1.0f / (sqrtf(wave_sum(qq)) + kTiny);
+    for (int j = w; j < Dv; j += 4) {
+      const int t1 = min(j + 6, D);
+      float p1 = 0.0f, p2 = 0.0f;
+      for (int e = 4 * lane; e < E; e += 256) {
+        f32x4 s = *(const f32x4*)(d + (int64_t)j * E + e);
+        for (int t = j + 1; t < t1; ++t) s += *(const f32x4*)(d + (int64_t)t * E + e);
+        const f32x4 x = s / 6.0f;
+        p1 += x[0] * qc[e] + x[1] * qc[e + 1] + x[2] * qc[e + 2] + x[3] * qc[e + 3];
+        p2 += x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3];
+      }
+      p1 = wave_sum(p1);
+      p2 = wave_sum(p2);
+      if (lane == 0) ctx[j] = (p1 * rqc) * (1.0f / (sqrtf(p2) + kTiny));
+    }
+  }
+  __syncthreads();   // qc (in `part`) is dead from here on
+
+  float* o = a.out + pair * (int64_t)Q * N * 8 * k;
+  int32_t* oi = a.idx ? a.idx + pair * (int64_t)Q * N * 4 * k : nullptr;
+  for (int s = 0; s <= nbp; ++s) {
+    // ---- cosine block s -> ring half (s & 1); s >= nb: the zero columns past the document (ConstantPad2d)
     const int j0 = 32 * s, rb = (s & 1) * 32;
     if (s < nb) {
       f32x16 acc[2];
@@ -89,8 +128,6 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
       float dsq = 0.0f;
       const bool drow = j0 + r32 < D;
       const float* dp = d + (int64_t)(j0 + r32) * E;
-      // kPB chunks of 8 per batch: every load of a batch is issued before its first MFMA (one memory latency per batch,
-      // not per chunk: the rows are 4 x 16 B per lane, far apart, and nothing else hides their latency)
       for (int m0 = w; m0 < nch; m0 += 4 * kPB) {
         f32x4 dv[kPB], qv[2][kPB];
 #pragma unroll
@@ -149,7 +186,6 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
     // ---- block s - 1: every path, every query row (rows are wavefront-owned: no barrier between paths)
     const int c0 = 32 * (s - 1), cb = ((s - 1) & 1) * 32;
     const int col = c0 + r32;
-    const bool ok = col < D;
     const int cnt0 = (c0 < k ? c0 : k);
     for (int p = 0; p < N; ++p) {
       const int n = p + 1, nn = n * n;
@@ -203,7 +239,23 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
         float lv = lane < cnt0 ? tv[base + lane] : neg_inf();
         int li = lane < cnt0 ? ti[base + lane] : 0;
         int cnt = cnt0;
-        topk_insert(lv, li, cnt, v, id, ok, k, lane);
+        // views whose last column lies in this block: insert up to it, snapshot, go on (bnd[i] >= k: the list is full)
+        int lo = c0;
+#pragma unroll 1
+        for (int i = 0; i < 4; ++i) {
+          const int bi = min(i == 0 ? a.v0 : i == 1 ? a.v1 : i == 2 ? a.v2 : a.v3, D);
+          if (bi > c0 && bi <= c0 + 32) {
+            topk_insert(lv, li, cnt, v, id, col >= lo && col < bi, k, lane);
+            lo = bi;
+            if (lane < k) {
+              float* ov = o + ((int64_t)r * N + p) * 8 * k;
+              ov[i * k + lane] = lv;
+              ov[4 * k + i * k + lane] = ctx[li & 0xffff];
+              if (oi) oi[((int64_t)r * N + p) * 4 * k + i * k + lane] = li;
+            }
+          }
+        }
+        topk_insert(lv, li, cnt, v, id, col >= lo && col < Dv, k, lane);
         if (lane < cnt) {
           tv[base + lane] = lv;
           ti[base + lane] = li;
@@ -212,35 +264,30 @@ __global__ void __launch_bounds__(256, 4) pacrr_fwd_kernel(PacrrArgs a) {
     }
     __syncthreads();
   }
-
-  // per_query_results [Q, k N] in path order 0, 2, .., N (pacrr.py:97)
-  float* o = a.out + pair * (int64_t)Q * N * k;
-  for (int c = tid; c < Q * N * k; c += 256) o[c] = tv[c];
-  if (a.idx) {
-    int32_t* oi = a.idx + pair * (int64_t)Q * N * k;
-    for (int c = tid; c < Q * N * k; c += 256) oi[c] = ti[c];
-  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- backward
-struct BwdArgs {
+struct CoBwdArgs {
   const float* q;
   const float* d;
   const float* w;
-  const int32_t* idx;
-  const float* go;   // [n_pairs, Q, k N]
-  float* gq;         // [n_pairs, Q, E]
-  float* gd;         // [n_pairs, D, E]
-  float* gw;         // [n_pairs, C S]
-  float* gb;         // [n_pairs, (N - 1) C]
-  float* wincos;     // workspace [n_pairs, Q k S]
+  const int32_t* idx;   // [n_pairs, Q, N, 4k]
+  const float* go;      // [n_pairs, Q, N, 8k]
+  float* gq;            // [n_pairs, Q, E]
+  float* gd;            // [n_pairs, D, E]
+  float* gw;            // [n_pairs, C S]
+  float* gb;            // [n_pairs, (N - 1) C]
+  float* wincos;        // workspace [n_pairs, Q 4k S]
+  float* gdctx;         // workspace [n_pairs, D, E]: d(loss)/d(dctx_j) / 6
+  float* gqh;           // workspace [n_pairs, 4, E]: per-wavefront partials of d(loss)/d(qctx-hat)
   int64_t n_pairs, ppq;
   int Q, D, E, C, N, k;
 };
 
-struct BwdLds {
+// PACRR's backward layout with K = 4k list slots per (row, path)
+struct CoBwdLds {
   int rq, nq, rd, nd, wt, eg, ei, G, gwl, gbl, total;
-  __host__ __device__ BwdLds(int Q, int D, int C, int N, int k) {
+  __host__ __device__ CoBwdLds(int Q, int D, int C, int N, int K) {
     const int S = tap_off(N + 1);
     int o = 0;
     rq = o; o += kPQmax;
@@ -248,8 +295,8 @@ struct BwdLds {
     rd = o; o += D;
     nd = o; o += D;
     wt = o; o += C * S;
-    eg = o; o += Q * N * k;
-    ei = o; o += Q * N * k;
+    eg = o; o += Q * N * K;
+    ei = o; o += Q * N * K;
     G = o; o += Q * 33;
     gwl = o; o += C * S;
     gbl = o; o += C * (N - 1);
@@ -259,25 +306,22 @@ struct BwdLds {
 
 constexpr int kMaxEPerLane = kPEmax / 64;
 
-// One workgroup per pair:
-//   P0  norms of the query rows and of every document row, the weights, the pair's saved entries and their gradients -> LDS
-//   P1  the cosine at every tap of every selected conv window (one dot each, recomputed from q / d) -> workspace
-//   P2  grad_w / grad_b of the pair: thread (path, tap) owns column `tap` of that width's weight gradient, thread `path` its
-//       bias gradient; each walks the entries in a fixed order (no atomics)
-//   P3  per 32-column document block: the sparse dcos block gathered into LDS (each cell sums its contributions in a fixed
-//       order), grad_d of the block's rows through the normalisation Jacobian, grad_q-hat accumulated in grad_q
-//   P4  grad_q through the query's normalisation Jacobian
-// The rows of P3 / P4 are wavefront-owned with one lane per 64th element: the thread that accumulates a grad_q element is the
-// one that finishes it.
-__global__ void __launch_bounds__(256) pacrr_bwd_kernel(BwdArgs a) {
+// One workgroup per pair.  P0-P4 are PACRR's backward (pacrr_bwd_kernel) over the 4k VALUE slots of every (row, path): a
+// column chosen by several views appears in several slots and every slot adds its own term.  P5 adds the CONTEXT slots:
+//   P5a  gctx[j] = sum of the context-slot gradients whose slot selected column j (fixed slot order)
+//   P5b  per column j with gctx[j] != 0 (wavefront-owned, lanes over E): dctx_j recomputed, the cosine Jacobian of
+//        (qctx, dctx_j) -> d(loss)/d(dctx_j) / 6 into the workspace, d(loss)/d(qctx-hat) accumulated per wavefront
+//   P5c  grad_q rows += d(loss)/d(qctx) / Q; grad_d row t += the workspace rows j = t - 5 .. t in ascending order
+__global__ void __launch_bounds__(256) co_pacrr_bwd_kernel(CoBwdArgs a) {
   extern __shared__ float lds[];
-  const int Q = a.Q, D = a.D, E = a.E, C = a.C, N = a.N, k = a.k;
+  const int Q = a.Q, D = a.D, E = a.E, C = a.C, N = a.N, k = 4 * a.k;
   const int S = tap_off(N + 1), NK = N * k;
-  const BwdLds L(Q, D, C, N, k);
+  const CoBwdLds L(Q, D, C, N, k);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int64_t pair = blockIdx.x;
   const float* q = a.q + (pair / a.ppq) * (int64_t)Q * E;
   const float* d = a.d + pair * (int64_t)D * E;
+  const float* go = a.go + pair * (int64_t)Q * N * 2 * k;
   float* rq = lds + L.rq;
   float* nqv = lds + L.nq;
   float* rd = lds + L.rd;
@@ -291,14 +335,14 @@ __global__ void __launch_bounds__(256) pacrr_bwd_kernel(BwdArgs a) {
   float* wc = a.wincos + pair * (int64_t)Q * k * S;
   const int ME = (E + 63) / 64;
 
-  // ---- P0
+  // ---- P0 (value-slot gradients: the first 4k of every path's 8k)
   for (int i = tid; i < C * S; i += 256) {
     wt[i] = a.w[i];
     gwl[i] = 0.0f;
   }
   for (int i = tid; i < C * (N - 1); i += 256) gbl[i] = 0.0f;
   for (int i = tid; i < Q * NK; i += 256) {
-    eg[i] = a.go[pair * (int64_t)Q * NK + i];
+    eg[i] = go[(i / k) * 2 * k + i % k];
     ei[i] = a.idx[pair * (int64_t)Q * NK + i];
   }
   for (int i = w; i < Q; i += 4) {
@@ -453,7 +497,6 @@ __global__ void __launch_bounds__(256) pacrr_bwd_kernel(BwdArgs a) {
     }
     __syncthreads();
   }
-  // rows of the document past the last block do not exist (D is covered); grad_d rows with no entry were written as zeros
 
   // ---- P4
   for (int i = w; i < Q; i += 4) {
@@ -474,16 +517,123 @@ __global__ void __launch_bounds__(256) pacrr_bwd_kernel(BwdArgs a) {
       if (m < ME && e < E) gq[(int64_t)i * E + e] = acc[m] * r1 - q[(int64_t)i * E + e] * f;
     }
   }
+
+  // ---- P5a: eg <- the context-slot gradients (eg / rd are free after P3)
+  __syncthreads();
+  float* gctx = rd;
+  for (int i = tid; i < Q * NK; i += 256) eg[i] = go[(i / k) * 2 * k + k + i % k];
+  __syncthreads();
+  for (int j = tid; j < D; j += 256) {
+    float g = 0.0f;
+    for (int e = 0; e < Q * NK; ++e) {
+      if ((ei[e] & 0xffff) == j) g += eg[e];
+    }
+    gctx[j] = g;
+  }
+  __syncthreads();
+
+  // ---- P5b
+  float* W = a.gdctx + pair * (int64_t)D * E;
+  float qc[kMaxEPerLane], acc[kMaxEPerLane];
+  float qq = 0.0f;
+#pragma unroll
+  for (int m = 0; m < kMaxEPerLane; ++m) {
+    const int e = lane + 64 * m;
+    float s = 0.0f;
+    if (m < ME && e < E) {
+      for (int i = 0; i < Q; ++i) s += q[(int64_t)i * E + e];
+    }
+    qc[m] = s / (float)Q;
+    qq += qc[m] * qc[m];
+    acc[m] = 0.0f;
+  }
+  const float nqc = sqrtf(wave_sum(qq)), rqc = 1.0f / (nqc + kTiny);
+  for (int j = w; j < D; j += 4) {
+    const float g = gctx[j];
+    if (g == 0.0f) continue;
+    const int t1 = min(j + 6, D);
+    float x[kMaxEPerLane];
+    float p2 = 0.0f, dq = 0.0f;
+#pragma unroll
+    for (int m = 0; m < kMaxEPerLane; ++m) {
+      const int e = lane + 64 * m;
+      float s = 0.0f;
+      if (m < ME && e < E) {
+        for (int t = j; t < t1; ++t) s += d[(int64_t)t * E + e];
+      }
+      x[m] = s / 6.0f;
+      p2 += x[m] * x[m];
+      dq += x[m] * (qc[m] * rqc);
+    }
+    p2 = wave_sum(p2);
+    dq = wave_sum(dq);
+    const float nx = sqrtf(p2), rx = 1.0f / (nx + kTiny);
+    const float f = nx > 0.0f ? g * dq * rx * rx / nx : 0.0f;
+#pragma unroll
+    for (int m = 0; m < kMaxEPerLane; ++m) {
+      const int e = lane + 64 * m;
+      if (m < ME && e < E) W[(int64_t)j * E + e] = (g * (qc[m] * rqc) * rx - x[m] * f) / 6.0f;
+      acc[m] += g * rx * x[m];
+    }
+  }
+  float* P = a.gqh + pair * 4 * (int64_t)E;
+#pragma unroll
+  for (int m = 0; m < kMaxEPerLane; ++m) {
+    const int e = lane + 64 * m;
+    if (m < ME && e < E) P[w * E + e] = acc[m];
+  }
+  __syncthreads();
+
+  // ---- P5c
+  float dot = 0.0f;
+#pragma unroll
+  for (int m = 0; m < kMaxEPerLane; ++m) {
+    const int e = lane + 64 * m;
+    acc[m] = (m < ME && e < E) ? ((P[e] + P[E + e]) + P[2 * E + e]) + P[3 * E + e] : 0.0f;
+    dot += acc[m] * qc[m];
+  }
+  dot = wave_sum(dot);
+  const float fq = nqc > 0.0f ? dot * rqc * rqc / nqc : 0.0f;
+#pragma unroll
+  for (int m = 0; m < kMaxEPerLane; ++m) acc[m] = (acc[m] * rqc - qc[m] * fq) / (float)Q;   // d/dq_i of mean_i q_i
+  for (int i = w; i < Q; i += 4) {
+#pragma unroll
+    for (int m = 0; m < kMaxEPerLane; ++m) {
+      const int e = lane + 64 * m;
+      if (m < ME && e < E) gq[(int64_t)i * E + e] += acc[m];
+    }
+  }
+  for (int t = w; t < D; t += 4) {
+    const int j0 = max(t - 5, 0);
+    bool any = false;
+    for (int j = j0; j <= t; ++j) any |= gctx[j] != 0.0f;
+    if (!any) continue;
+#pragma unroll
+    for (int m = 0; m < kMaxEPerLane; ++m) {
+      const int e = lane + 64 * m;
+      if (m < ME && e < E) {
+        float s = gd[(int64_t)t * E + e];
+        for (int j = j0; j <= t; ++j) {
+          if (gctx[j] != 0.0f) s += W[(int64_t)j * E + e];
+        }
+        gd[(int64_t)t * E + e] = s;
+      }
+    }
+  }
 }
 
-int check_shape(int64_t n_pairs, int64_t ppq, int Q, int D, int E, int C, int N, int k, const char* what) {
+int check_shape(int64_t n_pairs, int64_t ppq, int Q, int D, int E, int C, int N, int k, const int* v, const char* what) {
   if (n_pairs < 0 || ppq < 1) return set_error(MM_EINVAL, "%s: n_pairs = %lld, pairs_per_query = %lld", what, (long long)n_pairs, (long long)ppq);
-  if (Q < 1 || Q > kPQmax || k < 1 || k > kPKmax || D < k || D > kPDmax || E < 4 || E > kPEmax || E % 4 || C < 1 ||
+  if (v[0] > v[1] || v[1] > v[2] || v[2] > v[3])
+    return set_error(MM_EINVAL, "%s: views %d / %d / %d / %d are not ascending", what, v[0], v[1], v[2], v[3]);
+  if (Q < 1 || Q > kPQmax || k < 1 || k > kCoKmax || D < k || D > kPDmax || E < 4 || E > kPEmax || E % 4 || C < 1 ||
       C > kPCmax || N < 1 || N > kPNmax)
     return set_error(MM_EUNSUPPORTED,
                      "%s: Q = %d, D = %d, E = %d, C = %d, N = %d, k = %d outside 1 <= Q <= 64, k <= D <= 2048, 4 <= E <= 1024 "
-                     "(a multiple of 4), 1 <= C <= 64, 1 <= N <= 5, 1 <= k <= 32",
+                     "(a multiple of 4), 1 <= C <= 64, 1 <= N <= 5, 1 <= k <= 8",
                      what, Q, D, E, C, N, k);
+  if (v[0] < k)   // torch.topk of a view narrower than k raises in the reference (co_pacrr.py:115, :140)
+    return set_error(MM_EUNSUPPORTED, "%s: view 0 holds %d < k = %d columns", what, v[0], k);
   return MM_OK;
 }
 
@@ -492,50 +642,56 @@ int check_shape(int64_t n_pairs, int64_t ppq, int Q, int D, int E, int C, int N,
 
 using namespace mm;
 
-extern "C" size_t mm_pacrr_workspace_bytes(int64_t n_pairs, int Q, int D, int C, int N, int k) {
-  (void)D;
+extern "C" size_t mm_co_pacrr_workspace_bytes(int64_t n_pairs, int Q, int D, int E, int C, int N, int k) {
   (void)C;
-  if (n_pairs <= 0 || Q <= 0 || k <= 0 || N < 2) return 0;
-  return (size_t)n_pairs * (size_t)Q * (size_t)k * (size_t)tap_off(N + 1) * sizeof(float);
+  if (n_pairs <= 0 || Q <= 0 || D <= 0 || E <= 0 || k <= 0 || N <= 0) return 0;
+  const size_t win = N >= 2 ? (size_t)Q * 4 * (size_t)k * (size_t)tap_off(N + 1) : 0;
+  return (size_t)n_pairs * (win + (size_t)D * E + 4 * (size_t)E) * sizeof(float);
 }
 
-extern "C" int mm_pacrr_fwd(const float* q, const float* d, const float* conv_w, const float* conv_b, float* out,
-                            int32_t* saved_idx, int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N,
-                            int k, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mm_co_pacrr_fwd(const float* q, const float* d, const float* conv_w, const float* conv_b, float* out,
+                               int32_t* saved_idx, int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C,
+                               int N, int k, int view0, int view1, int view2, int view3, void* workspace,
+                               size_t workspace_bytes, void* stream) {
   (void)workspace;
   (void)workspace_bytes;
   if (!q || !d || !out || (N >= 2 && (!conv_w || !conv_b)))
-    return set_error(MM_EINVAL, "mm_pacrr_fwd: null q / d / out, or null conv_w / conv_b with N >= 2");
-  int rc = check_shape(n_pairs, pairs_per_query, Q, D, E, C, N, k, "mm_pacrr_fwd");
+    return set_error(MM_EINVAL, "mm_co_pacrr_fwd: null q / d / out, or null conv_w / conv_b with N >= 2");
+  const int v[4] = {view0, view1, view2, view3};
+  int rc = check_shape(n_pairs, pairs_per_query, Q, D, E, C, N, k, v, "mm_co_pacrr_fwd");
   if (rc != MM_OK) return rc;
   if (n_pairs == 0) return MM_OK;
-  if (n_pairs > 0x7fffffff) return set_error(MM_EUNSUPPORTED, "mm_pacrr_fwd: %lld pairs in one call", (long long)n_pairs);
-  const FwdLds L(Q, C, N, k);
-  PacrrArgs a{q, d, conv_w, conv_b, out, saved_idx, n_pairs, pairs_per_query, Q, D, E, C, N, k};
-  (void)hipFuncSetAttribute((const void*)pacrr_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L.total * (int)sizeof(float));
-  hipLaunchKernelGGL(pacrr_fwd_kernel, dim3((unsigned)n_pairs), dim3(256), (size_t)L.total * sizeof(float),
+  if (n_pairs > 0x7fffffff) return set_error(MM_EUNSUPPORTED, "mm_co_pacrr_fwd: %lld pairs in one call", (long long)n_pairs);
+  const CoFwdLds L(Q, D, C, N, k);
+  CoArgs a{q, d, conv_w, conv_b, out, saved_idx, n_pairs, pairs_per_query, Q, D, E, C, N, k, view0, view1, view2, view3};
+  (void)hipFuncSetAttribute((const void*)co_pacrr_fwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L.total * (int)sizeof(float));
+  hipLaunchKernelGGL(co_pacrr_fwd_kernel, dim3((unsigned)n_pairs), dim3(256), (size_t)L.total * sizeof(float),
                      (hipStream_t)stream, a);
-  return check_launch("mm_pacrr_fwd");
+  return check_launch("mm_co_pacrr_fwd");
 }
 
-extern "C" int mm_pacrr_bwd(const float* q, const float* d, const float* conv_w, const int32_t* saved_idx,
-                            const float* grad_out, float* grad_q, float* grad_d, float* grad_w, float* grad_b,
-                            int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int mm_co_pacrr_bwd(const float* q, const float* d, const float* conv_w, const int32_t* saved_idx,
+                               const float* grad_out, float* grad_q, float* grad_d, float* grad_w, float* grad_b,
+                               int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
+                               int view0, int view1, int view2, int view3, void* workspace, size_t workspace_bytes,
+                               void* stream) {
   if (!q || !d || !saved_idx || !grad_out || !grad_q || !grad_d || (N >= 2 && (!conv_w || !grad_w || !grad_b)))
-    return set_error(MM_EINVAL, "mm_pacrr_bwd: null pointer argument");
-  int rc = check_shape(n_pairs, pairs_per_query, Q, D, E, C, N, k, "mm_pacrr_bwd");
+    return set_error(MM_EINVAL, "mm_co_pacrr_bwd: null pointer argument");
+  const int v[4] = {view0, view1, view2, view3};
+  int rc = check_shape(n_pairs, pairs_per_query, Q, D, E, C, N, k, v, "mm_co_pacrr_bwd");
   if (rc != MM_OK) return rc;
   if (n_pairs == 0) return MM_OK;
-  if (n_pairs > 0x7fffffff) return set_error(MM_EUNSUPPORTED, "mm_pacrr_bwd: %lld pairs in one call", (long long)n_pairs);
-  const size_t need = mm_pacrr_workspace_bytes(n_pairs, Q, D, C, N, k);
-  if (need && (!workspace || workspace_bytes < need))
-    return set_error(MM_EWORKSPACE, "mm_pacrr_bwd: workspace of %zu bytes, needs %zu", workspace_bytes, need);
-  const BwdLds L(Q, D, C, N, k);
-  BwdArgs a{q, d, conv_w, saved_idx, grad_out, grad_q, grad_d, grad_w, grad_b, (float*)workspace, n_pairs,
-            pairs_per_query, Q, D, E, C, N, k};
-  (void)hipFuncSetAttribute((const void*)pacrr_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L.total * (int)sizeof(float));
-  hipLaunchKernelGGL(pacrr_bwd_kernel, dim3((unsigned)n_pairs), dim3(256), (size_t)L.total * sizeof(float),
+  if (n_pairs > 0x7fffffff) return set_error(MM_EUNSUPPORTED, "mm_co_pacrr_bwd: %lld pairs in one call", (long long)n_pairs);
+  const size_t need = mm_co_pacrr_workspace_bytes(n_pairs, Q, D, E, C, N, k);
+  if (!workspace || workspace_bytes < need)
+    return set_error(MM_EWORKSPACE, "mm_co_pacrr_bwd: workspace of %zu bytes, needs %zu", workspace_bytes, need);
+  const CoBwdLds L(Q, D, C, N, 4 * k);
+  float* ws = (float*)workspace;
+  const size_t win = N >= 2 ? (size_t)n_pairs * Q * 4 * (size_t)k * (size_t)tap_off(N + 1) : 0;
+  CoBwdArgs a{q, d, conv_w, saved_idx, grad_out, grad_q, grad_d, grad_w, grad_b, ws, ws + win,
+              ws + win + (size_t)n_pairs * D * E, n_pairs, pairs_per_query, Q, D, E, C, N, k};
+  (void)hipFuncSetAttribute((const void*)co_pacrr_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, L.total * (int)sizeof(float));
+  hipLaunchKernelGGL(co_pacrr_bwd_kernel, dim3((unsigned)n_pairs), dim3(256), (size_t)L.total * sizeof(float),
                      (hipStream_t)stream, a);
-  return check_launch("mm_pacrr_bwd");
+  return check_launch("mm_co_pacrr_bwd");
 }

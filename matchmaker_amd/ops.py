@@ -889,3 +889,107 @@ def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor,
         grad_b.append(gb[C * i:C * (i + 1)].clone())
         off += n * n
     return gq, gd, grad_w, grad_b
+
+
+def co_pacrr_views(unified_document_length: int):
+    """The four k-max view sizes of CO-PACRR, computed as the reference does (co_pacrr.py:73-74): int(U * f)."""
+    return [int(unified_document_length * x) for x in [0.25, 0.5, 0.75, 1]]
+
+
+def _co_pacrr_check(B, Q, D, E, k, views):
+    if len(views) != 4 or any(views[i] > views[i + 1] for i in range(3)):
+        raise NativeError(f"co_pacrr_kmax: four ascending view sizes needed, got {list(views)}")
+    if not (1 <= k <= 8) or not (k <= D <= 2048) or not (1 <= Q <= 64) or E > 1024 or views[0] < k:
+        # the reference's torch.topk raises for a view (or D) narrower than k (co_pacrr.py:115, :140); the kernel's limits are in
+        # mm_native.h
+        raise NativeError(f"co_pacrr_kmax: Q = {Q}, D = {D}, E = {E}, k = {k}, views {list(views)} outside 1 <= Q <= 64, "
+                          f"k <= D <= 2048, E <= 1024, 1 <= k <= 8, views >= k (MM_EUNSUPPORTED)")
+
+
+def co_pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, views, pairs_per_query: int = 1,
+                  save: bool = False):
+    """CO-PACRR's match matrix + n-gram convolutions + k-max pooling at four views + context similarities
+    (matchmaker/models/co_pacrr.py:90-158) in ONE launch (mm_co_pacrr_fwd): per_query_results [n_pairs, Q, 8 k N], per
+    path 0, 2, .., N the 4k values of views 0..3 then their 4k contexts.
+
+    q / d / weights / biases as pacrr_kmax; views: the four view sizes (co_pacrr_views(U)).  save=True also returns the
+    int32 positions [n_pairs, Q, N, 4 k] (column | channel << 16) that co_pacrr_kmax_bwd takes; the values are the same
+    bits either way."""
+    dev = _dev_check(q, d)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("co_pacrr_kmax: float32 embeddings only (the reference cosine rejects bf16)")
+    nq, Q, E, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    views = [int(v) for v in views]
+    _co_pacrr_check(B, Q, D, E, k, views)
+    weights, biases = list(weights), list(biases)
+    C = weights[0].shape[0] if weights else 1
+    N = len(weights) + 1
+    w, b = _pacrr_params(weights, biases, C, dev)
+    out = torch.empty((B, Q, 8 * k * N), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, Q, N, 4 * k), dtype=torch.int32, device=dev) if save else None
+    if B:
+        q, d, E = _pad_rows(q, d, 4)
+        L = _lib.lib()
+        with _on(dev):
+            rc = L.mm_co_pacrr_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None,
+                                   b.data_ptr() if b is not None else None, out.data_ptr(),
+                                   idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
+                                   *views, None, 0, _stream(dev))
+        _lib.check(rc, "mm_co_pacrr_fwd")
+    return (out, idx) if save else out
+
+
+def co_pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor, grad_out: torch.Tensor, k: int, views,
+                      pairs_per_query: int = 1):
+    """Backward of co_pacrr_kmax (mm_co_pacrr_bwd, one launch): idx as returned by co_pacrr_kmax(..., save=True) on the same
+    inputs, grad_out [n_pairs, Q, 8 k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w,
+    grad_b) as pacrr_kmax_bwd."""
+    dev = _dev_check(q, d, idx, grad_out)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("co_pacrr_kmax_bwd: float32 embeddings only")
+    nq, Q, E0, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    views = [int(v) for v in views]
+    _co_pacrr_check(B, Q, D, E0, k, views)
+    weights = list(weights)
+    C = weights[0].shape[0] if weights else 1
+    N = len(weights) + 1
+    w, _ = _pacrr_params(weights, [t.new_zeros(C) for t in weights], C, dev)
+    if tuple(idx.shape) != (B, Q, N, 4 * k) or idx.dtype != torch.int32:
+        raise NativeError(f"co_pacrr_kmax_bwd: idx must be int32 {(B, Q, N, 4 * k)}, got {idx.dtype} {tuple(idx.shape)}")
+    go = grad_out.detach().to(torch.float32).contiguous()
+    if tuple(go.shape) != (B, Q, 8 * k * N):
+        raise NativeError(f"co_pacrr_kmax_bwd: grad_out must be {(B, Q, 8 * k * N)}, got {tuple(go.shape)}")
+    idx = idx.contiguous()
+    q, d, E = _pad_rows(q, d, 4)
+    S = sum(n * n for n in range(2, N + 1))
+    gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
+    gd = torch.empty((B, D, E), dtype=torch.float32, device=dev)
+    gw = torch.empty((B, C * S), dtype=torch.float32, device=dev)
+    gb = torch.empty((B, C * (N - 1)), dtype=torch.float32, device=dev)
+    if B:
+        L = _lib.lib()
+        with _on(dev):
+            wsb = L.mm_co_pacrr_workspace_bytes(B, Q, D, E, C, N, k)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            rc = L.mm_co_pacrr_bwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(),
+                                   go.data_ptr(), gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None,
+                                   gb.data_ptr() if N > 1 else None, B, pairs_per_query, Q, D, E, C, N, k, *views,
+                                   ws.data_ptr(), wsb, _stream(dev))
+        _lib.check(rc, "mm_co_pacrr_bwd")
+    if E != E0:
+        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
+    if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
+        pad = nq * pairs_per_query - B
+        if pad:
+            gq = torch.cat([gq, gq.new_zeros((pad, Q, E0))])
+        gq = gq.view(nq, pairs_per_query, Q, E0).sum(1)
+    gw, gb = gw.sum(0), gb.sum(0)
+    grad_w, grad_b, off = [], [], 0
+    for i, t in enumerate(weights):
+        n = i + 2
+        grad_w.append(gw[C * off:C * (off + n * n)].view(t.shape).clone())
+        grad_b.append(gb[C * i:C * (i + 1)].clone())
+        off += n * n
+    return gq, gd, grad_w, grad_b

@@ -211,3 +211,54 @@ def _pacrr_backward(ctx, g, _gidx):
 
 pacrr_kmax.register_autograd(_pacrr_backward, setup_context=_pacrr_setup)
 torch.library.register_autocast(_NS + "::pacrr_kmax", "cuda", torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- CO-PACRR
+@torch.library.custom_op(_NS + "::co_pacrr_kmax", mutates_args=(), device_types="cuda")
+def co_pacrr_kmax(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor], k: int, views: List[int],
+                  pairs_per_query: int) -> Tuple[Tensor, Tensor]:
+    """per_query_results [n_pairs, Q, 8 k N] of CO-PACRR (co_pacrr.py:90-158) and the int32 positions [n_pairs, Q, N, 4 k]
+    (column | channel << 16) the backward routes through; no gradient flows through the positions.  (pairs_per_query has
+    no default, as in pacrr_kmax.)"""
+    out, idx = ops.co_pacrr_kmax(q, d, weights, biases, k, views, pairs_per_query=pairs_per_query, save=True)
+    return out, idx
+
+
+@co_pacrr_kmax.register_fake
+def _(q, d, weights, biases, k, views, pairs_per_query):
+    N = len(weights) + 1
+    return (q.new_empty((d.shape[0], q.shape[1], 8 * k * N), dtype=torch.float32),
+            q.new_empty((d.shape[0], q.shape[1], N, 4 * k), dtype=torch.int32))
+
+
+@torch.library.custom_op(_NS + "::co_pacrr_kmax_backward", mutates_args=(), device_types="cuda")
+def co_pacrr_kmax_backward(q: Tensor, d: Tensor, weights: List[Tensor], idx: Tensor, grad_out: Tensor, k: int,
+                           views: List[int], pairs_per_query: int = 1) -> Tuple[Tensor, Tensor, List[Tensor], List[Tensor]]:
+    gq, gd, gw, gb = ops.co_pacrr_kmax_bwd(q, d, weights, idx, grad_out, k, views, pairs_per_query=pairs_per_query)
+    return gq, gd, gw, gb
+
+
+@co_pacrr_kmax_backward.register_fake
+def _(q, d, weights, idx, grad_out, k, views, pairs_per_query=1):
+    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
+            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
+            [w.new_empty((w.shape[0],), dtype=torch.float32) for w in weights])
+
+
+def _co_pacrr_setup(ctx, inputs, output):
+    q, d, weights, biases, k, views, ppq = inputs
+    ctx.save_for_backward(q, d, output[1], *weights)
+    ctx.meta = (k, list(views), ppq, [b.shape for b in biases])
+    ctx.mark_non_differentiable(output[1])
+
+
+def _co_pacrr_backward(ctx, g, _gidx):
+    q, d, idx, *weights = ctx.saved_tensors
+    k, views, ppq, bshapes = ctx.meta
+    gq, gd, gw, gb = torch.ops.mm_native.co_pacrr_kmax_backward(q, d, weights, idx, g.contiguous(), k, views, ppq)
+    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
+            [t.view(s) for t, s in zip(gb, bshapes)], None, None, None)
+
+
+co_pacrr_kmax.register_autograd(_co_pacrr_backward, setup_context=_co_pacrr_setup)
+torch.library.register_autocast(_NS + "::co_pacrr_kmax", "cuda", torch.float32)
