@@ -496,6 +496,39 @@ int mm_co_pacrr_bwd(const float* q, const float* d, const float* conv_w, const i
                     int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int C, int N, int k,
                     int view0, int view1, int view2, int view3, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * DRMM: cosine match matrix -> per query token a histogram of its cosines over the document -> (optionally) the scoring head.
+ *
+ *   cos[i,j]   = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))               (allennlp cosine, drmm.py:66; exact-fp32 MFMA)
+ *   hist[p,i,:] = torch.histc(cos[i, :], bins, min = -1, max = 1)             (drmm.py:71-74): an element with cos < -1 or
+ *                cos > 1 is dropped, otherwise it counts in bin min(int((cos + 1) / 2 * bins), bins - 1), evaluated in fp32.
+ *                No mask enters: zero rows (padding, OOV) give cos = 0 and count in bin bins / 2.
+ *   score[p]   = sum_i gate[g, i] * tanh(w2 . tanh(W1 log1p(hist[p,i,:]) + b1) + b2)   (drmm.py:77, :88; the head is
+ *                matching_classifier, the gate the masked softmax of query_gate, computed by the caller)
+ *
+ * Replaces: DRMM.forward   matchmaker/models/drmm.py:66-91   (cosine, the .cpu() copy, the per-row histc loop, the copy back,
+ *           log1p + matching_classifier + the gated sum; the query gate of :82-83 stays torch)
+ *
+ *   q [n_queries, Q, E], d [n_pairs, D, E] float32, E a multiple of 4; pair p uses query p / pairs_per_query
+ *   d_len    optional int32 [n_pairs]: document rows at or past d_len[p] are taken as zero rows without being read (their
+ *            count goes to bin bins / 2); NULL = every row is read.  Bit-equal to the full computation when those rows are zero.
+ *   hist     optional float32 [n_pairs, Q, bins] (raw counts); score optional float32 [n_pairs]; at least one of the two
+ *   gate     float32 [n_pairs, Q] when gate_per_pair = 1, else [n_queries, Q]; W1 [bins, bins] row-major (Linear.weight),
+ *            b1 [bins], w2 [bins], b2 [1]: needed with score only
+ *   clamp    0 = the reference (cosines that round above 1 are dropped, as histc does); 1 = clamp the cosine into [-1, 1]
+ *            before binning (a deliberate deviation: exact matches always count in the last bin)
+ *   No gradient: the histogram is piecewise constant in q and d.  Deterministic (no atomics).
+ *   Limits: 1 <= Q <= 64, 1 <= D <= 65535, 4 <= E <= 1024 (a multiple of 4), 1 <= bins <= 16; anything else returns
+ *   MM_EUNSUPPORTED before any launch; NULL or inconsistent arguments return MM_EINVAL.  No workspace is needed
+ *   (mm_drmm_workspace_bytes returns 0; workspace may be NULL).
+ */
+size_t mm_drmm_workspace_bytes(int64_t n_pairs, int Q, int D, int E, int bins);
+
+int mm_drmm_fwd(const float* q, const float* d, const int32_t* d_len, float* hist, float* score, const float* gate,
+                int gate_per_pair, const float* W1, const float* b1, const float* w2, const float* b2,
+                int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int bins, int clamp,
+                void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,8 @@ SIGNATURES = {
                              _vp]),
     "mm_co_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
                              _vp, _sz, _vp]),
+    "mm_drmm_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "mm_drmm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -993,3 +993,83 @@ def co_pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tens
         grad_b.append(gb[C * i:C * (i + 1)].clone())
         off += n * n
     return gq, gd, grad_w, grad_b
+
+
+# ---------------------------------------------------------------------------------------------- DRMM
+def _drmm_shapes(q, d, pairs_per_query, bins, what):
+    nq, Q, E = q.shape
+    B, D, E2 = d.shape
+    if E != E2:
+        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
+        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    if not (1 <= Q <= 64) or not (1 <= D <= 65535) or E > 1024 or not (1 <= bins <= 16):
+        raise NativeError(f"{what}: Q = {Q}, D = {D}, E = {E}, bins = {bins} outside 1 <= Q <= 64, 1 <= D <= 65535, "
+                          f"E <= 1024, 1 <= bins <= 16 (MM_EUNSUPPORTED)")
+    return nq, Q, E, B, D
+
+
+def _drmm_len(d_len, B, dev):
+    if d_len is None:
+        return None
+    t = d_len.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    if t.numel() != B:
+        raise NativeError(f"d_len has {t.numel()} entries for {B} pairs")
+    return t
+
+
+def _drmm_call(what, q, d, bins, pairs_per_query, d_len, clamp, want_hist, head):
+    dev = _dev_check(q, d, d_len, *(head or ()))
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError(f"{what}: float32 embeddings only (the reference cosine rejects bf16)")
+    nq, Q, E, B, D = _drmm_shapes(q, d, pairs_per_query, bins, what)
+    dl = _drmm_len(d_len, B, dev)
+    hist = torch.empty((B, Q, bins), dtype=torch.float32, device=dev) if want_hist else None
+    score = gate = W1 = b1 = w2 = b2 = None
+    per_pair = 0
+    if head is not None:
+        gate, W1, b1, w2, b2 = head
+        gate = gate.detach().to(torch.float32).contiguous()
+        if tuple(gate.shape) == (B, Q) and B != nq:
+            per_pair = 1
+        elif tuple(gate.shape) != (nq, Q):
+            raise NativeError(f"{what}: gate must be {(nq, Q)} (per query) or {(B, Q)} (per pair), got {tuple(gate.shape)}")
+        W1, b1, w2, b2 = _vec(W1.detach()), _vec(b1.detach()), _vec(w2.detach()), _vec(b2.detach())
+        if W1.numel() != bins * bins or b1.numel() != bins or w2.numel() != bins or b2.numel() != 1:
+            raise NativeError(f"{what}: head parameters must be W1 [{bins}, {bins}], b1 [{bins}], w2 [{bins}], b2 [1]")
+        score = torch.empty(B, dtype=torch.float32, device=dev)
+    if B:
+        q, d, E = _pad_rows(q, d, 4)
+        p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        with _on(dev):
+            rc = _lib.lib().mm_drmm_fwd(q.data_ptr(), d.data_ptr(), p(dl), p(hist), p(score), p(gate), per_pair, p(W1), p(b1),
+                                        p(w2), p(b2), B, pairs_per_query, Q, D, E, bins, 1 if clamp else 0, None, 0,
+                                        _stream(dev))
+        _lib.check(rc, "mm_drmm_fwd")
+    return hist, score
+
+
+def drmm_hist(q: torch.Tensor, d: torch.Tensor, bins: int = 10, pairs_per_query: int = 1,
+              d_len: Optional[torch.Tensor] = None, clamp: bool = False) -> torch.Tensor:
+    """DRMM's matching histograms (matchmaker/models/drmm.py:66-74) in ONE launch (mm_drmm_fwd), nothing leaves the device:
+    hist [n_pairs, Q, bins] float32 = torch.histc(cosine(q_i, d)[i, :], bins, -1, 1) per query token (raw counts; cosines
+    that round above 1 are dropped, as histc drops them; clamp=True clamps them into the last bin instead — a deviation).
+
+    q [n_queries, Q, E], d [n_pairs, D, E] float32 with padding / OOV rows already multiplied to zero (:56-58); pair p
+    scores against query p // pairs_per_query.  d_len [n_pairs] (optional): rows at or past it are zero rows and are not
+    read (bit-equal to reading them).  No gradient flows through a histogram."""
+    return _drmm_call("drmm_hist", q, d, bins, pairs_per_query, d_len, clamp, True, None)[0]
+
+
+def drmm_score(q: torch.Tensor, d: torch.Tensor, gate: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor,
+               b2: torch.Tensor, pairs_per_query: int = 1, d_len: Optional[torch.Tensor] = None, clamp: bool = False,
+               return_hist: bool = False):
+    """DRMM's score with the head fused into the histogram kernel (inference; drmm.py:66-91): score [n_pairs] =
+    sum_i gate[., i] * tanh(w2 . tanh(W1 log1p(hist_i) + b1) + b2).  gate [n_queries, Q] or [n_pairs, Q]: the masked
+    softmax of the query gate, computed by the caller; W1 [bins, bins], b1 [bins], w2 [bins] (or [1, bins]), b2 [1] =
+    matching_classifier._linear_layers.{0,1}.{weight,bias}.  return_hist=True also returns the histograms of the same
+    launch (the same bits as drmm_hist)."""
+    bins = b1.numel()
+    hist, score = _drmm_call("drmm_score", q, d, bins, pairs_per_query, d_len, clamp, return_hist, (gate, W1, b1, w2, b2))
+    return (score, hist) if return_hist else score

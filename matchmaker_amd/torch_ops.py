@@ -262,3 +262,54 @@ def _co_pacrr_backward(ctx, g, _gidx):
 
 co_pacrr_kmax.register_autograd(_co_pacrr_backward, setup_context=_co_pacrr_setup)
 torch.library.register_autocast(_NS + "::co_pacrr_kmax", "cuda", torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- DRMM
+@torch.library.custom_op(_NS + "::drmm_hist", mutates_args=(), device_types="cuda")
+def drmm_hist(q: Tensor, d: Tensor, bins: int = 10, pairs_per_query: int = 1, d_len: Optional[Tensor] = None,
+              clamp: bool = False) -> Tensor:
+    """hist [n_pairs, Q, bins] of DRMM (drmm.py:66-74).  Piecewise constant in q and d: no gradient flows through it."""
+    return ops.drmm_hist(q, d, bins, pairs_per_query, d_len, clamp)
+
+
+@drmm_hist.register_fake
+def _(q, d, bins=10, pairs_per_query=1, d_len=None, clamp=False):
+    return q.new_empty((d.shape[0], q.shape[1], bins), dtype=torch.float32)
+
+
+def _drmm_hist_setup(ctx, inputs, output):
+    ctx.mark_non_differentiable(output)
+
+
+def _drmm_hist_backward(ctx, g):
+    return None, None, None, None, None, None
+
+
+drmm_hist.register_autograd(_drmm_hist_backward, setup_context=_drmm_hist_setup)
+torch.library.register_autocast(_NS + "::drmm_hist", "cuda", torch.float32)
+
+
+@torch.library.custom_op(_NS + "::drmm_score", mutates_args=(), device_types="cuda")
+def drmm_score(q: Tensor, d: Tensor, gate: Tensor, W1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor,
+               pairs_per_query: int = 1, d_len: Optional[Tensor] = None, clamp: bool = False) -> Tensor:
+    """score [n_pairs] of DRMM with the head fused (inference only: no autograd formula is registered, so a call whose
+    inputs require grad raises; train through drmm_hist + the torch head)."""
+    return ops.drmm_score(q, d, gate, W1, b1, w2, b2, pairs_per_query, d_len, clamp)
+
+
+@drmm_score.register_fake
+def _(q, d, gate, W1, b1, w2, b2, pairs_per_query=1, d_len=None, clamp=False):
+    return q.new_empty((d.shape[0],), dtype=torch.float32)
+
+
+def _drmm_score_setup(ctx, inputs, output):
+    pass
+
+
+def _drmm_score_backward(ctx, g):
+    raise ops.NativeError("mm_native::drmm_score is inference-only (the head is fused into the histogram kernel); "
+                          "for training call mm_native::drmm_hist and apply the head in torch")
+
+
+drmm_score.register_autograd(_drmm_score_backward, setup_context=_drmm_score_setup)
+torch.library.register_autocast(_NS + "::drmm_score", "cuda", torch.float32)
