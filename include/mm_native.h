@@ -407,6 +407,33 @@ int mm_topk_merge(const float* in_scores, const int64_t* in_ids, int nq, int n_i
                   float* out_scores, int64_t* out_ids, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * IVF list scan: exact inner-product top-k over the inverted lists a query probes (dense retrieval,
+ * faiss_index_type: ivf).
+ *
+ * Replaces: the list scan of FaissIVFIndexer.search      matchmaker/retrieval/faiss_indices.py:106-145
+ *           (an inner-product IVF index cloned to the GPUs with co.shard and useFloat16); the coarse
+ *           quantiser (centroid assignment, probe selection) is mm_dot_topk_fwd over the centroids.
+ *
+ *   queries [nq, E], vectors [n_vectors, E]  float16 / bfloat16, E in {128, 256, 384, 512, 768}; the
+ *   vectors are stored list by list: list l is the rows list_begin[l] .. list_begin[l + 1] (list_begin
+ *   [nlist + 1] int64, non-decreasing; lists may be empty).
+ *   probes [nq, nprobe] int32 list numbers, -1 = no list; a list named twice in one row is an error
+ *   (the row then never holds more than n_vectors candidates: the surplus is dropped).
+ *   out_scores [nq, k] float32 descending = fp32-accumulated inner products of the 16-bit values;
+ *   out_rows [nq, k] int64 = row of `vectors`; (-inf, -1) pads a probed union of fewer than k vectors.
+ *   The result is the EXACT top-k of the union of the probed lists; equal scores: lower row first.
+ *   k <= 4096, nprobe <= 4096, n_vectors and nq * nprobe below 2^31.  Every launch goes to `stream`,
+ *   nothing is read back or allocated: the call can be captured into a graph.
+ *   workspace: mm_ivf_scan_workspace_bytes(...) bytes = min(nq n_vectors, max(2^28, 2 n_vectors))
+ *   floats of candidate scores (at most 1 GiB below 2^27 vectors; the queries are scored in rounds
+ *   that fit) + 12 bytes per (query, probe) pair + 20 per query + 12 per list + 4 per 32 vectors. */
+size_t mm_ivf_scan_workspace_bytes(int64_t n_vectors, int nlist, int nq, int nprobe, int k);
+
+int mm_ivf_scan_fwd(const void* queries, const void* vectors, const int64_t* list_begin, const int32_t* probes,
+                    int64_t n_vectors, int nlist, int nq, int nprobe, int E, int dtype, int k,
+                    float* out_scores, int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * PACRR: cosine match matrix -> n-gram convolutions + channel max -> per-row k-max pooling, fused.
  *
  *   cos[i,j]  = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))            (allennlp cosine, pacrr.py:78)

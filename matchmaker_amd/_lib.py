@@ -59,6 +59,8 @@ SIGNATURES = {
     "mm_tkl_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
     "mm_tkl_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_tkl_fwd_peaks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mm_ivf_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "mm_ivf_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mm_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
     "mm_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -757,6 +757,49 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
                       "(more than 4k documents tie at the k-th score?)")
 
 
+def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Tensor, probes: torch.Tensor, k: int):
+    """Exact inner-product top-k over the inverted lists each query probes (the list scan of an IVF index:
+    matchmaker/retrieval/faiss_indices.py:106-145; native mm_ivf_scan_fwd).
+
+    queries [nq, E], vectors [n, E] float16 / bfloat16 of one dtype, E in {128,...,768} (pad otherwise); the vectors are
+    stored list by list, list l = rows list_begin[l] .. list_begin[l + 1] (list_begin [nlist + 1] int64).  probes
+    [nq, nprobe] int32 list numbers, -1 = no list.  A list named twice in one row is a caller error that is not detected:
+    the result of that row is then undefined (copies of a vector may be returned, or lists dropped; memory stays in
+    bounds).  Returns (scores [nq, k] float32 descending,
+    rows [nq, k] int64 rows of `vectors`; -inf / -1 padded when the probed lists hold fewer than k vectors; equal scores:
+    lower row first).  One enqueue on the current stream, no read-back: graph-capturable."""
+    dev = _dev_check(queries, vectors, list_begin, probes)
+    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
+        raise NativeError(f"ivf_scan: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
+    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"ivf_scan: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
+    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
+        raise NativeError(f"ivf_scan: list_begin must be int64 [nlist + 1], got {list_begin.dtype} {tuple(list_begin.shape)}")
+    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != queries.shape[0] or probes.shape[1] < 1:
+        raise NativeError(f"ivf_scan: probes must be int32 [nq, nprobe], got {probes.dtype} {tuple(probes.shape)}")
+    if not 1 <= k <= 4096 or probes.shape[1] > 4096:
+        raise NativeError(f"ivf_scan: k={k} / nprobe={probes.shape[1]} outside 1 .. 4096")
+    queries = queries if queries.is_contiguous() else queries.contiguous()
+    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
+    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
+    probes = probes if probes.is_contiguous() else probes.contiguous()
+    nq, E = queries.shape
+    n, nlist, nprobe = vectors.shape[0], list_begin.shape[0] - 1, probes.shape[1]
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    if nq == 0:
+        return out_s, out_r
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_ivf_scan_workspace_bytes, n, nlist, nq, nprobe, k)
+        ws = _workspace(dev, wsb)
+        rc = L.mm_ivf_scan_fwd(queries.data_ptr(), vectors.data_ptr() if n else None, list_begin.data_ptr(), probes.data_ptr(),
+                               n, nlist, nq, nprobe, E, _DT[queries.dtype], k, out_s.data_ptr(), out_r.data_ptr(),
+                               ws.data_ptr(), wsb, _stream(dev))
+    _lib.check(rc, "mm_ivf_scan_fwd")
+    return out_s, out_r
+
+
 def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
     """Rows of (score, id) candidates [nq, n_in] -> the k best per row (score descending, input order on
     ties); ids < 0 are padding.  The sharded index's final merge (mm_topk_merge)."""

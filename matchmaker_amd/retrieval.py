@@ -1,4 +1,4 @@
-"""Drop-in for matchmaker's brute-force faiss index on MI355X: same surface as
+"""Drop-ins for matchmaker's GPU faiss indices on MI355X.  FlatIPIndexer (brute force): same surface as
 `FaissIdIndexer` (matchmaker/retrieval/faiss_indices.py:49-74; base class :13-36) —
 `prepare(data_chunks)`, `index(ids, data_chunks)`, `search(query_vec, top_n) -> (scores, ids)` —
 with the collection resident in HBM as float16 (what `co.useFloat16` stores on the reference's GPUs)
@@ -8,6 +8,10 @@ Multi-GPU = the reference's `co.shard = True` (:62-66): every rank holds a conti
 vectors; `search` runs the local top-k, all-gathers the [nq, k] (score, id) lists over RCCL and
 merges them natively (mm_topk_merge).  Used from dense_retrieval.py:308-328 (construction),
 :333-336 (prepare / index) and :391 (search).
+
+IVFFlatIPIndexer (faiss_index_type: ivf) has the surface of `FaissIVFIndexer` (faiss_indices.py:106-145): spherical
+k-means centroids, the shard stored list by list, probe selection with the same top-k kernel and the exact scan of
+the probed lists by mm_ivf_scan_fwd.
 """
 from typing import List, Optional
 
@@ -24,6 +28,36 @@ def _pad_dim(E: int) -> int:
         if E <= e:
             return e
     raise ops.NativeError(f"token_dim {E} > 768 is not supported by the native flat index")
+
+
+def _device_queries(query_vec, dtype, E_pad: int, token_dim: int, device) -> torch.Tensor:
+    """The queries as the index stores its vectors: [nq, E_pad] `dtype` on `device` (a single vector becomes one row;
+    a tensor that already has that form is used as it is)."""
+    q = torch.as_tensor(query_vec)
+    if q.dim() == 1:
+        q = q[None, :]
+    if q.is_cuda and q.dtype == dtype and q.shape[1] == E_pad and q.is_contiguous():
+        return q
+    qd = torch.zeros((q.shape[0], E_pad), dtype=dtype, device=device)
+    qd[:, : token_dim] = q.to(device).to(dtype)
+    return qd
+
+
+def _merge_shards(s: torch.Tensor, ids: torch.Tensor, top_n: int, group, merge_fn, merge_single_rank: bool = False):
+    """co.shard's final step: all-gather every rank's [nq, top_n] (score, id) lists and merge them; one rank (and no
+    rehearsal asked for) returns its own lists."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return s, ids
+    world = dist.get_world_size(group)
+    if world > 1 or merge_single_rank:
+        nq = s.shape[0]
+        gs = torch.empty((world * nq, top_n), dtype=s.dtype, device=s.device)        # rank-major concatenation
+        gi = torch.empty((world * nq, top_n), dtype=ids.dtype, device=ids.device)
+        dist.all_gather_into_tensor(gs, s.contiguous(), group=group)                  # RCCL over xGMI
+        dist.all_gather_into_tensor(gi, ids.contiguous(), group=group)
+        s, ids = merge_fn(gs.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1),
+                          gi.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1), top_n)
+    return s, ids
 
 
 class FlatIPIndexer:
@@ -95,23 +129,206 @@ class FlatIPIndexer:
     def search_device(self, query_vec, top_n: int):
         """search() without the final copy to the host: device tensors (what a caller that keeps working on the GPU wants,
         and what bench.py times)."""
-        q = torch.as_tensor(query_vec)
-        if q.dim() == 1:
-            q = q[None, :]
-        if q.is_cuda and q.dtype == self.dtype and q.shape[1] == self.E_pad and q.is_contiguous():
-            qd = q
-        else:
-            qd = torch.zeros((q.shape[0], self.E_pad), dtype=self.dtype, device=self.device)
-            qd[:, : self.token_dim] = q.to(self.device).to(self.dtype)
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
         s, idx = self._topk(qd, self.vectors, top_n)
         ids = torch.where(idx >= 0, self.ids[idx.clamp(min=0)], idx)
-        world, _ = self._world()
-        if world > 1 or (self.merge_single_rank and dist.is_available() and dist.is_initialized()):
-            nq = s.shape[0]
-            gs = torch.empty((world * nq, top_n), dtype=s.dtype, device=s.device)        # rank-major concatenation
-            gi = torch.empty((world * nq, top_n), dtype=ids.dtype, device=ids.device)
-            dist.all_gather_into_tensor(gs, s.contiguous(), group=self.group)             # RCCL over xGMI
-            dist.all_gather_into_tensor(gi, ids.contiguous(), group=self.group)
-            s, ids = self._merge(gs.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1),
-                                 gi.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1), top_n)
-        return s, ids
+        return _merge_shards(s, ids, top_n, self.group, self._merge, self.merge_single_rank)
+
+
+_IVF_MAGIC = "matchmaker_amd.IVFFlatIPIndexer"
+_IVF_FORMAT = 1
+
+
+class IVFFlatIPIndexer:
+    """Drop-in for the reference's GPU IVF index (`FaissIVFIndexer`, faiss_indices.py:106-145: inner-product inverted
+    lists, fp16 scalar quantiser for centroids and lists, `co.shard` over the GPUs): `prepare(data_chunks, subsample)`
+    trains `faiss_ivf_list_count` centroids by spherical k-means, `index(ids, data_chunks)` stores this rank's shard list
+    by list, `search(query_vec, top_n)` probes the `faiss_ivf_search_probe_count` best lists of every query and returns
+    the EXACT top_n of their union (ops.ivf_scan), merged over the ranks.  `save` / `load` use a file format of their own."""
+
+    KMEANS_ITERS = 20            # faiss ClusteringParameters.niter
+    ASSIGN_CHUNK = 1 << 14       # vectors per assignment call (bounds the top-k workspace)
+    SUM_CHUNK = 1 << 18          # vectors per fp32 conversion of the centroid update
+
+    def __init__(self, config, device=None, group=None, topk_fn=None, scan_fn=None, merge_fn=None):
+        """topk_fn(queries, vectors, k) / scan_fn(queries, vectors, list_begin, probes, k) / merge_fn(scores, ids, k)
+        default to ops.dot_topk / ops.ivf_scan / ops.topk_merge; the CPU test-suite injects stand-ins."""
+        self._topk = topk_fn if topk_fn is not None else ops.dot_topk
+        self._scan = scan_fn if scan_fn is not None else ops.ivf_scan
+        self._merge = merge_fn if merge_fn is not None else ops.topk_merge
+        self.token_dim = config["token_dim"]
+        self.use_fp16 = config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16")
+        if not self.use_fp16:
+            raise ops.NativeError("IVFFlatIPIndexer stores float16 centroids and lists and rounds queries to float16 (the "
+                                  "reference's fp16 IVF: an fp16 scalar quantiser): set token_dtype: float16, or keep faiss "
+                                  "for an fp32 index")
+        self.nlist = int(config["faiss_ivf_list_count"])
+        self.nprobe = int(config["faiss_ivf_search_probe_count"])
+        if self.nlist < 1 or self.nprobe < 1:
+            raise ops.NativeError("faiss_ivf_list_count and faiss_ivf_search_probe_count must be positive")
+        self.seed = int(config.get("random_seed", 208973249))
+        self.dtype = torch.float16
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
+        self.group = group
+        self.E_pad = _pad_dim(self.token_dim)
+        self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
+        self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad] list by list
+        self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids, same order
+        self.list_begin: Optional[torch.Tensor] = None        # [nlist + 1] int64
+
+    def _world(self):
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group), dist.get_rank(self.group)
+        return 1, 0
+
+    def _to_device(self, data_chunks: List[np.ndarray], lo: int, hi: int) -> torch.Tensor:
+        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
+        off = 0
+        for c in data_chunks:
+            a, b = max(lo, off), min(hi, off + c.shape[0])
+            if a < b:
+                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
+                    self.device).to(self.dtype)
+            off += c.shape[0]
+        return vec
+
+    def _assign(self, x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+        """[n] int64: the centroid of maximum inner product for every row of x."""
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
+        for a in range(0, x.shape[0], self.ASSIGN_CHUNK):
+            out[a: a + self.ASSIGN_CHUNK] = self._topk(x[a: a + self.ASSIGN_CHUNK], centroids, 1)[1][:, 0]
+        return out
+
+    @staticmethod
+    def _unit(c: torch.Tensor) -> torch.Tensor:
+        return c / c.norm(dim=1, keepdim=True).clamp_min(1e-20)
+
+    def _train_rows(self, n: int, subsample, gen) -> Optional[torch.Tensor]:
+        """The seeded, sorted rows a subsample in (0, 1) trains on (host int64), or None for all of them."""
+        if not 0 < subsample < 1:
+            return None
+        return torch.randperm(n, generator=gen)[: max(1, int(n * subsample))].sort().values
+
+    def _check_train_size(self, n: int):
+        if n < self.nlist:
+            raise ops.NativeError(f"IVFFlatIPIndexer.prepare: {n} training vectors for faiss_ivf_list_count = {self.nlist}")
+
+    def prepare(self, data_chunks: List[np.ndarray], subsample=-1):
+        """Spherical k-means (faiss sets `spherical` for inner-product IVF), KMEANS_ITERS iterations from a seeded sample
+        of the training vectors; subsample in (0, 1] trains on a seeded fraction of them: the rows are chosen on the host
+        and only they are copied to the device.  An empty cluster is re-seeded from a vector of the largest cluster.
+        Under torch.distributed rank 0 trains and its centroids are broadcast."""
+        n_all = sum(c.shape[0] for c in data_chunks)
+        gen = torch.Generator().manual_seed(self.seed)
+        keep = self._train_rows(n_all, subsample, gen)
+        self._check_train_size(n_all if keep is None else keep.numel())     # on every rank, before any collective
+        x = None
+        if self._world()[1] == 0:
+            if keep is None:
+                x = self._to_device(data_chunks, 0, n_all)
+            else:
+                k, off, parts = keep.numpy(), 0, []
+                for c in data_chunks:
+                    a, b = np.searchsorted(k, [off, off + c.shape[0]])
+                    parts.append(np.ascontiguousarray(c[k[a:b] - off]))
+                    off += c.shape[0]
+                x = self._to_device(parts, 0, k.shape[0])
+        self._train(x, gen)
+
+    def train_resident(self, x: torch.Tensor, subsample=-1):
+        """prepare() on training vectors that already are a device tensor [n, E_pad] float16."""
+        gen = torch.Generator().manual_seed(self.seed)
+        keep = self._train_rows(x.shape[0], subsample, gen)
+        self._check_train_size(x.shape[0] if keep is None else keep.numel())
+        self._train(x if keep is None else x[keep.to(x.device)], gen)
+
+    def _train(self, x: Optional[torch.Tensor], gen):
+        """k-means on rank 0 (x is None elsewhere), then the broadcast."""
+        world, rank = self._world()
+        if rank == 0:
+            n = x.shape[0]
+            cent = self._unit(x[torch.randperm(n, generator=gen)[: self.nlist].to(x.device)].float()).to(self.dtype)
+            for _ in range(self.KMEANS_ITERS):
+                a = self._assign(x, cent)
+                sums = torch.zeros((self.nlist, self.E_pad), dtype=torch.float32, device=x.device)
+                for lo in range(0, n, self.SUM_CHUNK):      # fp32 copies of SUM_CHUNK rows at a time, in input order
+                    sums.index_add_(0, a[lo: lo + self.SUM_CHUNK], x[lo: lo + self.SUM_CHUNK].float())
+                counts = torch.bincount(a, minlength=self.nlist)
+                empty = torch.nonzero(counts == 0).flatten()
+                if empty.numel():
+                    members = torch.nonzero(a == counts.argmax()).flatten()
+                    sums[empty] = x[members[torch.arange(empty.numel(), device=x.device) % members.numel()]].float()
+                cent = self._unit(sums).to(self.dtype)
+        else:
+            cent = torch.empty((self.nlist, self.E_pad), dtype=self.dtype, device=self.device)
+        if world > 1:
+            dist.broadcast(cent, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
+        self.centroids = cent.contiguous()
+
+    def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
+        """Every vector of this rank's contiguous shard goes to the list of its maximum-inner-product centroid; the shard
+        is then stored list by list (stable: input order inside a list)."""
+        if self.centroids is None:
+            raise ops.NativeError("IVFFlatIPIndexer.index: prepare() (or load()) first")
+        i = np.concatenate(ids).astype(np.int64)
+        world, rank = self._world()
+        lo, hi = shard_range(i.shape[0], world, rank)
+        self.index_resident(torch.from_numpy(i[lo:hi]).to(self.device), self._to_device(data_chunks, lo, hi))
+
+    def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64)."""
+        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
+            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        a = self._assign(vectors, self.centroids)
+        order = torch.sort(a, stable=True).indices
+        self.vectors = vectors[order].contiguous()
+        self.ids = ids.to(torch.int64)[order].contiguous()
+        lb = torch.zeros(self.nlist + 1, dtype=torch.int64, device=vectors.device)
+        lb[1:] = torch.cumsum(torch.bincount(a, minlength=self.nlist), 0)
+        self.list_begin = lb
+
+    def search(self, query_vec, top_n: int):
+        """(scores [nq, top_n] float32 descending, ids [nq, top_n] int64; -inf / -1 where the probed lists ran out)."""
+        s, ids = self.search_device(query_vec, top_n)
+        return s.cpu().numpy(), ids.cpu().numpy()
+
+    def search_device(self, query_vec, top_n: int, return_probes: bool = False):
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
+        probes = self._topk(qd, self.centroids, min(self.nprobe, self.nlist))[1].to(torch.int32)
+        s, rows = self._scan(qd, self.vectors, self.list_begin, probes, top_n)
+        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0)], rows) if self.ids.numel() else rows
+        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        return (s, ids, probes) if return_probes else (s, ids)
+
+    def _rank_path(self, path: str) -> str:
+        world, rank = self._world()
+        return path if world == 1 else f"{path}.rank{rank}"
+
+    def save(self, path: str):
+        """One numpy .npz archive (this rank's shard; `path + ".rank<r>"` with several ranks)."""
+        with open(self._rank_path(path), "wb") as f:
+            np.savez(f, magic=np.array(_IVF_MAGIC), format=np.array(_IVF_FORMAT), token_dim=np.array(self.token_dim),
+                     nprobe=np.array(self.nprobe), centroids=self.centroids.cpu().numpy(),
+                     list_begin=self.list_begin.cpu().numpy(), vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy())
+
+    def load(self, path: str, config_overwrites=None):
+        """faiss_indices.py:143-145: the probe count comes from config_overwrites["faiss_ivf_search_probe_count"]."""
+        p = self._rank_path(path)
+        with open(p, "rb") as f:
+            head = f.read(4)
+        if head[:2] != b"PK":
+            raise ops.NativeError(f"{p} is not an IVFFlatIPIndexer file (an index written by faiss cannot be read: build the "
+                                  "index again with prepare() / index())")
+        z = np.load(p, allow_pickle=False)
+        if "magic" not in z.files or str(z["magic"]) != _IVF_MAGIC or int(z["format"]) != _IVF_FORMAT:
+            raise ops.NativeError(f"{p} is not an IVFFlatIPIndexer file of format {_IVF_FORMAT}")
+        if int(z["token_dim"]) != self.token_dim or z["centroids"].shape[1] != self.E_pad:
+            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        self.centroids = torch.from_numpy(z["centroids"]).to(self.device)
+        self.list_begin = torch.from_numpy(z["list_begin"]).to(self.device)
+        self.vectors = torch.from_numpy(z["vectors"]).to(self.device)
+        self.ids = torch.from_numpy(z["ids"]).to(self.device)
+        self.nlist = self.centroids.shape[0]
+        self.nprobe = int(z["nprobe"])
+        if config_overwrites is not None and "faiss_ivf_search_probe_count" in config_overwrites:
+            self.nprobe = int(config_overwrites["faiss_ivf_search_probe_count"])
