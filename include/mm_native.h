@@ -556,6 +556,41 @@ int mm_drmm_fwd(const float* q, const float* d, const int32_t* d_len, float* his
                 int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int bins, int clamp,
                 void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * MatchPyramid: cosine match matrix -> L x (zero pad, Conv2d, ReLU, AdaptiveMaxPool2d) -> flattened features, one launch.
+ *
+ *   x_0[0,i,j]  = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))           (allennlp cosine, matchpyramid.py:74; a zero row
+ *                 gives exactly 0; no mask enters: padded document columns are convolved and pooled like real ones)
+ *   layer l     : x_l [C_{l-1}, H, W] is padded with k0 - 1 zero COLUMNS on the right and k1 - 1 zero ROWS below
+ *                 (ConstantPad2d((0, k[0] - 1, 0, k[1] - 1)), :50) and convolved with a k0-row x k1-column kernel
+ *                 (Conv2d(kernel_size = k), :51): the conv output is (H + k1 - k0) x (W + k0 - k1); the bias is added at
+ *                 every output position; ReLU (:52); AdaptiveMaxPool2d((ph, pw)) (:53): output i of an axis of length n
+ *                 covers [floor(i n / ph), ceil((i + 1) n / ph)) (windows overlap, ph > n is legal)
+ *   features[p] = x_L flattened channel-major, C_L ph_L pw_L floats             (conv_result.view(B, -1), :92)
+ *
+ * Replaces: MatchPyramid.forward up to conv_result_flat   matchmaker/models/matchpyramid.py:74-92
+ *           (the three dense layers of :99-101 stay torch).  Forward only.
+ *
+ *   q [n_queries, Q, E], d [n_pairs, D, E] float32, E a multiple of 4; pair p uses query p / pairs_per_query
+ *   layers    HOST array int32 [n_layers, 5]: (C_l, k0, k1, ph, pw) per layer
+ *   conv_w    float32, the Conv2d weights [C_l, C_{l-1}, k0, k1] of the layers packed in order (C_0's input is 1 channel);
+ *             conv_b the biases packed in the same order
+ *   features  [n_pairs, C_L ph_L pw_L] float32
+ *   workspace mm_matchpyramid_workspace_bytes(n_pairs, Q, D, n_layers, layers) bytes (0 when every activation plane fits the
+ *             LDS): one slot per resident workgroup for the planes that do not fit, at most 256 MiB however large n_pairs is
+ *             (the workgroups walk the batch).  Returns 0 for an unsupported shape as well.
+ *   Exact fp32 (v_mfma_f32_32x32x2_f32 / v_mfma_f32_16x16x4_f32), no atomics, bit-reproducible; a pair's result does not
+ *   depend on the rest of the batch.  MM_MP_GENERIC=1 runs the generic kernel at the reference config too (same bits).
+ *   Limits: 1 <= Q <= 64, 1 <= D <= 2048, 4 <= E <= 1024 (a multiple of 4), 1 <= n_layers <= 8, 1 <= C_l <= 32, kernel
+ *   sides 1 .. 5, 1 <= ph <= 64, 1 <= pw <= 256, every conv output at least 1 x 1; anything else returns MM_EUNSUPPORTED
+ *   before any launch; NULL pointers or pairs_per_query < 1 return MM_EINVAL.
+ */
+size_t mm_matchpyramid_workspace_bytes(int64_t n_pairs, int Q, int D, int n_layers, const int32_t* layers);
+
+int mm_matchpyramid_fwd(const float* q, const float* d, const float* conv_w, const float* conv_b, float* features,
+                        int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int n_layers, const int32_t* layers,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ MASK_NONE, MASK_LEN_I32, MASK_U8, MASK_I64, MASK_F32 = 0, 1, 2, 3, 4
 TKL_SAT_EMBEDDING, TKL_SAT_LOG = 0, 1
 SIM_ROUND, SUM_ROUND = 1, 2          # MM_SIM_ROUND / MM_SUM_ROUND
 ABI_VERSION = 4
+MM_OK, MM_EINVAL, MM_EUNSUPPORTED, MM_EWORKSPACE, MM_ELAUNCH = 0, -1, -2, -3, -4
 
 _c = ctypes
 _vp, _i64, _i, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t
@@ -71,13 +72,19 @@ SIGNATURES = {
                              _vp, _sz, _vp]),
     "mm_drmm_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "mm_drmm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    "mm_matchpyramid_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
+    "mm_matchpyramid_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
 
 
 class NativeError(RuntimeError):
-    pass
+    """.code: the C return code (MM_E*) when the error came from libmm_native.so or restates one of its checks, else None."""
+
+    def __init__(self, msg="", code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 def lib():
@@ -103,4 +110,4 @@ def lib():
 def check(code: int, what: str):
     if code != 0:
         msg = lib().mm_last_error().decode("utf-8", "replace")
-        raise NativeError(f"{what} failed ({code}): {msg}")
+        raise NativeError(f"{what} failed ({code}): {msg}", code)

@@ -53,6 +53,7 @@ struct EnvCfg {
   int tkl_bwd_nosplit = 0;    // MM_TKL_BWD_NOSPLIT=1: TKL's backward with one workgroup per document at every batch size (A/B runs)
   int tkl_fold_regions = 0;   // MM_TKL_FOLD_REGIONS=1: TKL's region top-k in the last window workgroup of each document (round 4's default) instead of
                               // its own launch (A/B runs: the hand-off written to the memory model costs +50 us per 256-document call, see tkl.hip)
+  int mp_generic = 0;       // MM_MP_GENERIC=1: MatchPyramid on the generic kernel also at the reference config (bit-equal twin, A/B runs)
   int tkl_pairsums = 0;     // MM_TKL_PAIRSUMS: TKL stage 1 emits pair sums (round-2 data path) instead of cosines (A/B runs)
 };
 const EnvCfg& env();

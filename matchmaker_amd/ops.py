@@ -1116,3 +1116,61 @@ def drmm_score(q: torch.Tensor, d: torch.Tensor, gate: torch.Tensor, W1: torch.T
     bins = b1.numel()
     hist, score = _drmm_call("drmm_score", q, d, bins, pairs_per_query, d_len, clamp, return_hist, (gate, W1, b1, w2, b2))
     return (score, hist) if return_hist else score
+
+
+# ---------------------------------------------------------------------------------------------- MatchPyramid
+def _mp_layers(Q, D, weights, biases, pool_sizes, what):
+    """-> (host int32 array [L, 5] of (C, k0, k1, ph, pw), feature count).  Only the consistency of the lists is checked
+    here; the envelope is mm_matchpyramid_fwd's to judge (MM_EUNSUPPORTED before any launch)."""
+    L = len(weights)
+    if L < 1 or len(biases) != L or len(pool_sizes) != L:
+        raise NativeError(f"{what}: {L} weights, {len(biases)} biases, {len(pool_sizes)} pool sizes")
+    rows, cin = [], 1
+    for wt, bs, pool in zip(weights, biases, pool_sizes):
+        if wt.dim() != 4 or wt.shape[1] != cin or bs.numel() != wt.shape[0]:
+            raise NativeError(f"{what}: conv weight {tuple(wt.shape)} / bias {tuple(bs.shape)} after {cin} channels")
+        cin = int(wt.shape[0])
+        rows.append((cin, int(wt.shape[2]), int(wt.shape[3]), int(pool[0]), int(pool[1])))
+    return (ctypes.c_int32 * (5 * L))(*[x for r in rows for x in r]), max(cin * rows[-1][3] * rows[-1][4], 0)
+
+
+def matchpyramid_pack(weights, biases):
+    """The conv weights / biases of every layer in mm_matchpyramid_fwd's packing (two float32 vectors)."""
+    w = torch.cat([t.detach().to(torch.float32).reshape(-1) for t in weights])
+    b = torch.cat([t.detach().to(torch.float32).reshape(-1) for t in biases])
+    return w, b
+
+
+def matchpyramid_features(q: torch.Tensor, d: torch.Tensor, weights, biases, pool_sizes, pairs_per_query: int = 1,
+                          packed=None) -> torch.Tensor:
+    """MatchPyramid's forward up to the flattened conv result (matchmaker/models/matchpyramid.py:74-92) in ONE launch
+    (mm_matchpyramid_fwd): features [n_pairs, C_L ph_L pw_L] float32, channel-major as `.view(B, -1)` gives.
+
+    q [n_queries, Q, E], d [n_pairs, D, E] float32 (no mask enters, as in the reference); pair p scores against query
+    p // pairs_per_query.  weights[l] [C_l, C_{l-1}, k0, k1], biases[l] [C_l], pool_sizes[l] (ph, pw).  packed (optional):
+    matchpyramid_pack(weights, biases) made earlier.  Inference only.  Raises NativeError whose .code is the C return code
+    (MM_EUNSUPPORTED outside the envelope, before any launch)."""
+    dev = _dev_check(q, d, *weights, *biases)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("matchpyramid_features: float32 embeddings only (the reference cosine rejects bf16)")
+    nq, Q, E = q.shape
+    B, D, E2 = d.shape
+    if E != E2:
+        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
+        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    layers, feat = _mp_layers(Q, D, weights, biases, pool_sizes, "matchpyramid_features")
+    out = torch.empty((B, feat), dtype=torch.float32, device=dev)
+    if B:
+        w, b = packed if packed is not None else matchpyramid_pack(weights, biases)
+        q, d, E = _pad_rows(q, d, 4)
+        L = len(weights)
+        need = _lib.lib().mm_matchpyramid_workspace_bytes(B, Q, D, L, layers)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        with _on(dev):
+            rc = _lib.lib().mm_matchpyramid_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), B,
+                                                pairs_per_query, Q, D, E, L, layers, ws.data_ptr() if need else None, need,
+                                                _stream(dev))
+        _lib.check(rc, "mm_matchpyramid_fwd")
+    return out

@@ -23,6 +23,7 @@ _TABLE = [
     ("matchmaker.models.pacrr", "PACRR", "matchmaker_amd.pacrr", "PACRR"),
     ("matchmaker.models.co_pacrr", "CO_PACRR", "matchmaker_amd.co_pacrr", "CO_PACRR"),
     ("matchmaker.models.drmm", "DRMM", "matchmaker_amd.drmm", "DRMM"),
+    ("matchmaker.models.matchpyramid", "MatchPyramid", "matchmaker_amd.matchpyramid", "MatchPyramid"),
     # IDCM is NOT rebound: only its passage sampler (sigir21_idcm.py:182-186) lies on the scoring path, the block is inline
     # in IDCM.forward (no module boundary to hook) and restating that forward here would be a copy of an out-of-scope method.
     # INTEGRATION.md shows the three-line edit a maintainer makes there to call matchmaker_amd.idcm.sampler_scores.

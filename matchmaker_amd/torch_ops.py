@@ -313,3 +313,32 @@ def _drmm_score_backward(ctx, g):
 
 drmm_score.register_autograd(_drmm_score_backward, setup_context=_drmm_score_setup)
 torch.library.register_autocast(_NS + "::drmm_score", "cuda", torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- MatchPyramid
+@torch.library.custom_op(_NS + "::matchpyramid_features", mutates_args=(), device_types="cuda")
+def matchpyramid_features(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor], pool_sizes: List[int],
+                          pairs_per_query: int = 1) -> Tensor:
+    """features [n_pairs, C_L ph_L pw_L] of MatchPyramid (matchpyramid.py:74-92); pool_sizes is flat: ph_0, pw_0, ph_1, ...
+    Inference only: no autograd formula exists, so a backward through it raises; train through the module's torch layers."""
+    pools = [(pool_sizes[2 * i], pool_sizes[2 * i + 1]) for i in range(len(pool_sizes) // 2)]
+    return ops.matchpyramid_features(q, d, weights, biases, pools, pairs_per_query)
+
+
+@matchpyramid_features.register_fake
+def _(q, d, weights, biases, pool_sizes, pairs_per_query=1):
+    return q.new_empty((d.shape[0], weights[-1].shape[0] * pool_sizes[-2] * pool_sizes[-1]), dtype=torch.float32)
+
+
+def _matchpyramid_setup(ctx, inputs, output):
+    pass
+
+
+def _matchpyramid_backward(ctx, g):
+    raise ops.NativeError("mm_native::matchpyramid_features is inference-only (forward kernel only); for training run the "
+                          "module's own torch layers (matchmaker_amd.matchpyramid.MatchPyramid does so when anything "
+                          "requires a gradient)")
+
+
+matchpyramid_features.register_autograd(_matchpyramid_backward, setup_context=_matchpyramid_setup)
+torch.library.register_autocast(_NS + "::matchpyramid_features", "cuda", torch.float32)

@@ -1,0 +1,249 @@
+"""CPU tests of MatchPyramid (no GPU): the restatement (tests/matchpyramid_reference.py) against the real class's goldens
+and, where the reference tree exists, against live instances; the drop-in's constructor, state_dict, returns, torch path and
+gradients; patch_matchmaker's rebinding; the ABI symbols, the fake (meta) rule and the autograd refusal of
+torch.ops.mm_native.matchpyramid_features; the rank-order list the GPU test shares.
+
+Agreement everywhere to measured_tol = 4 x max |x32 - x64| + 16 x 2^-24 x max |x64| of the restatement itself."""
+import importlib
+import os
+import sys
+import types
+
+import pytest
+import torch
+
+from oracle import ref_harness as R
+from tests import matchpyramid_reference as MR
+from tests import util
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = ["ref", "b1", "padded", "up", "one", "rect", "chan", "hot"]
+
+
+def module_from_golden(g):
+    from matchmaker_amd.matchpyramid import MatchPyramid
+    sd = {k[len("param."):]: torch.tensor(v) for k, v in g.items() if k.startswith("param.")}
+    L = int(g["shape"][4])
+    channels = [int(sd[f"conv_layers.conv {l}.weight"].shape[0]) for l in range(L)]
+    kernels = [[int(x) for x in sd[f"conv_layers.conv {l}.weight"].shape[2:]] for l in range(L)]
+    m = MatchPyramid(channels, kernels, [[int(x) for x in r] for r in g["pools"]])
+    m.load_state_dict(sd, strict=True)
+    return m
+
+
+def _close(got, x32, x64, label):
+    tol = MR.measured_tol(x32, x64)
+    err = float((torch.as_tensor(got).double() - x64.double()).abs().max())
+    print(f"{label}: tol = {tol:.3e}, err = {err:.3e}")
+    assert err <= tol, (label, err, tol)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_restatement_matches_the_real_class_goldens(name):
+    g = util.load(f"matchpyramid_{name}.npz")
+    p = MR.params_from_golden(g)
+    q, d = torch.tensor(g["q"]), torch.tensor(g["d"])
+    f32, f64 = MR.features(q, d, p, torch.float32), MR.features(q, d, p, torch.float64)
+    assert tuple(g["features"].shape) == tuple(f64.shape)
+    _close(g["features"], f32, f64, f"{name} features")
+    p32, p64 = MR.pyramid(q, d, p, torch.float32, upto=0), MR.pyramid(q, d, p, torch.float64, upto=0)
+    assert tuple(g["pool0"].shape) == tuple(p64.shape)
+    _close(g["pool0"], p32, p64, f"{name} pool0")
+    s32, s64 = MR.score(q, d, p, torch.float32), MR.score(q, d, p, torch.float64)
+    _close(g["score"], s32, s64, f"{name} score")
+    if name == "hot":
+        assert float(abs(g["features"]).max()) >= 1.0
+    if name == "padded":                          # zero document rows give exactly 0 cosines and are still pooled
+        lens = [int(x) for x in g["doc_len"]]
+        assert all(float(abs(g["d"][b, n:]).max()) == 0 for b, n in enumerate(lens) if n < g["d"].shape[1])
+
+
+def _reference_class(monkeypatch):
+    from tests.golden import gen_golden_matchpyramid as G
+    G.install_stubs(lambda k, v: monkeypatch.setitem(sys.modules, k, v))
+    monkeypatch.delitem(sys.modules, "matchmaker.models.matchpyramid", raising=False)
+    return importlib.import_module("matchmaker.models.matchpyramid").MatchPyramid, G
+
+
+LIVE = [(2, 30, 200, 32, MR.DEFAULT), (2, 5, 7, 16, ([3, 4], [[3, 3], [3, 3]], [[7, 4], [2, 3]])),
+        (2, 6, 9, 8, ([3, 2], [[2, 3], [3, 2]], [[4, 5], [2, 2]])), (2, 1, 2, 8, ([2], [[3, 3]], [[1, 1]]))]
+
+
+@pytest.mark.skipif(not R.available(), reason="live parity needs the reference tree; the goldens cover the rest")
+@pytest.mark.parametrize("B, Q, D, E, pyramid", LIVE)
+def test_restatement_and_dropin_match_the_live_class(monkeypatch, B, Q, D, E, pyramid):
+    Ref, G = _reference_class(monkeypatch)
+    from matchmaker_amd.matchpyramid import MatchPyramid
+    torch.manual_seed(Q + D)
+    ref = Ref(*pyramid).eval()
+    q, d = G.make_inputs(B, Q, D, E, None, seed=E)
+    s, feat, _ = G.run_reference(ref, q, d)
+    p = MR.params_from_module(ref)
+    _close(feat, MR.features(q, d, p, torch.float32), MR.features(q, d, p, torch.float64), "live features")
+    _close(s, MR.score(q, d, p, torch.float32), MR.score(q, d, p, torch.float64), "live score")
+    mine = MatchPyramid(*pyramid).eval()
+    assert list(mine.state_dict()) == list(ref.state_dict())
+    mine.load_state_dict(ref.state_dict(), strict=True)
+    ref.load_state_dict(mine.state_dict(), strict=True)
+    with torch.no_grad():
+        assert torch.equal(mine(q, d, None, None), s)           # the torch path runs the same layers
+
+
+def test_constructor_from_config_returns_and_state_dict():
+    from matchmaker_amd.matchpyramid import MatchPyramid
+    cfg = {"match_pyramid_conv_output_size": MR.DEFAULT[0], "match_pyramid_conv_kernel_size": MR.DEFAULT[1],
+           "match_pyramid_adaptive_pooling_size": MR.DEFAULT[2]}
+    m = MatchPyramid.from_config(cfg, 300)
+    assert m.dense.in_features == 16 * 3 * 10
+    with pytest.raises(Exception, match="must have the same length"):
+        MatchPyramid([16, 16], [[3, 3]], [[3, 3], [2, 2]])
+    with pytest.raises(Exception, match="must have the same length"):
+        MatchPyramid([16], [[3, 3]], [[3, 3], [2, 2]])
+    g = util.load("matchpyramid_ref.npz")
+    keys = [k[len("param."):] for k in g if k.startswith("param.")]
+    assert sorted(m.state_dict()) == sorted(keys)
+    assert {k: tuple(v.shape) for k, v in m.state_dict().items()} == {k: tuple(g["param." + k].shape) for k in keys}
+    assert list(dict(m.conv_layers.named_children()))[:4] == ["pad 0", "conv 0", "relu 0", "pool 0"]
+    m = module_from_golden(g)                    # strict=True
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, torch.tensor(g["param." + k]))
+    assert m.get_param_stats() == "MP: / " and m.get_param_secondary() == {}
+    q, d = torch.tensor(g["q"]), torch.tensor(g["d"])
+    with torch.no_grad():
+        s = m(q, d, torch.ones(3, 30), torch.ones(3, 200))
+        s2, sec = m(q, d, torch.ones(3, 30), torch.ones(3, 200), output_secondary_output=True)
+    assert tuple(s.shape) == (3,) and sec == {} and torch.equal(s, s2)
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_dropin_on_cpu_tensors_takes_the_torch_path_and_reproduces_the_golden_scores(name):
+    g = util.load(f"matchpyramid_{name}.npz")
+    m = module_from_golden(g).eval()
+    p = MR.params_from_golden(g)
+    q, d = torch.tensor(g["q"]), torch.tensor(g["d"])
+    with torch.no_grad():
+        s = m(q, d, None, None)
+    _close(s, MR.score(q, d, p, torch.float32), MR.score(q, d, p, torch.float64), f"{name} drop-in score")
+    # the torch path runs the reference's own layers on the same parameters: the golden score, to the fp32 yardstick
+    _close(s, MR.score(q, d, p, torch.float32), torch.tensor(g["score"]), f"{name} drop-in against the golden")
+
+
+def test_dropin_gives_finite_gradients_for_every_parameter():
+    g = util.load("matchpyramid_hot.npz")
+    m = module_from_golden(g).train()
+    q = torch.tensor(g["q"]).requires_grad_(True)
+    s = m(q, torch.tensor(g["d"]), None, None)
+    s.sum().backward()
+    for n, x in m.named_parameters():
+        assert x.grad is not None and torch.isfinite(x.grad).all(), n
+    assert float(m.dense.weight.grad.abs().max()) > 0 and torch.isfinite(q.grad).all()
+
+
+def test_patch_matchmaker_rebinds_matchpyramid(monkeypatch):
+    """on the real module where the reference tree is present, on a stand-in with the same name otherwise"""
+    from matchmaker_amd import patch
+    from matchmaker_amd.matchpyramid import MatchPyramid
+    row = ("matchmaker.models.matchpyramid", "MatchPyramid", "matchmaker_amd.matchpyramid", "MatchPyramid")
+    assert row in patch._TABLE
+    if R.available():
+        Ref, _ = _reference_class(monkeypatch)
+        ref_mod = sys.modules["matchmaker.models.matchpyramid"]
+    else:
+        for name in ("matchmaker", "matchmaker.models"):
+            monkeypatch.setitem(sys.modules, name, sys.modules.get(name) or types.ModuleType(name))
+        ref_mod = types.ModuleType("matchmaker.models.matchpyramid")
+        Ref = type("MatchPyramid", (), {})
+        ref_mod.MatchPyramid = Ref
+        monkeypatch.setitem(sys.modules, "matchmaker.models.matchpyramid", ref_mod)
+    all_mod = types.ModuleType("matchmaker.models.all")
+    all_mod.MatchPyramid = Ref
+    monkeypatch.setitem(sys.modules, "matchmaker.models.all", all_mod)
+    for mod_name, attr, _, _ in patch._TABLE:           # every rebinding is undone afterwards
+        try:
+            mod = importlib.import_module(mod_name)
+        except Exception:
+            continue
+        monkeypatch.setattr(mod, attr, getattr(mod, attr))
+    monkeypatch.setattr(patch, "_idcm_note_given", True)
+    done = patch.patch_matchmaker()
+    assert "matchmaker.models.matchpyramid.MatchPyramid" in done
+    assert ref_mod.MatchPyramid is MatchPyramid and all_mod.MatchPyramid is MatchPyramid
+    cfg = {"match_pyramid_conv_output_size": [4], "match_pyramid_conv_kernel_size": [[3, 3]],
+           "match_pyramid_adaptive_pooling_size": [[2, 2]]}
+    assert type(all_mod.MatchPyramid.from_config(cfg, 300)).__module__ == "matchmaker_amd.matchpyramid"   # models/all.py:153
+
+
+def test_abi_symbols_in_the_header_and_the_binding():
+    from matchmaker_amd import _lib
+    header = open(os.path.join(ROOT, "include", "mm_native.h")).read()
+    for sym in ("mm_matchpyramid_workspace_bytes", "mm_matchpyramid_fwd"):
+        assert sym + "(" in header and sym in _lib.SIGNATURES
+    assert "#define MM_ABI_VERSION 4" in header and _lib.ABI_VERSION == 4
+    L = _lib.lib()                               # resolves every symbol
+    import ctypes
+    rows = [x for c, k, p in zip(*MR.DEFAULT) for x in (c, k[0], k[1], p[0], p[1])]
+    arr = (ctypes.c_int32 * len(rows))(*rows)
+    one = L.mm_matchpyramid_workspace_bytes(1, 30, 200, 5, arr)
+    assert one == (16 * 38 * 92 + 16) * 4        # layer 0's pooled plane, stored with layer 1's padding, + the tile slack
+    assert L.mm_matchpyramid_workspace_bytes(10 ** 6, 30, 200, 5, arr) <= 256 << 20      # bounded however large the batch
+    assert L.mm_matchpyramid_workspace_bytes(4, 65, 200, 5, arr) == 0
+    buf = (ctypes.c_float * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    assert L.mm_matchpyramid_fwd(None, p, p, p, p, 2, 1, 30, 200, 64, 5, arr, None, 0, None) == _lib.MM_EINVAL
+    assert L.mm_matchpyramid_fwd(p, p, p, p, p, 2, 0, 30, 200, 64, 5, arr, None, 0, None) == _lib.MM_EINVAL
+    assert L.mm_matchpyramid_fwd(p, p, p, p, p, 2, 1, 65, 200, 64, 5, arr, None, 0, None) == _lib.MM_EUNSUPPORTED
+    assert L.mm_matchpyramid_fwd(p, p, p, p, p, 2, 1, 30, 200, 64, 5, arr, None, 0, None) == _lib.MM_EWORKSPACE
+    assert L.mm_matchpyramid_fwd(p, p, p, p, p, 0, 1, 30, 200, 64, 5, arr, None, 0, None) == _lib.MM_OK
+
+
+@pytest.mark.parametrize("nq, ppq, B", [(4, 1, 4), (2, 1000, 1500)])
+def test_fake_tensor_shape_and_autograd_refusal(nq, ppq, B):
+    from torch._subclasses.fake_tensor import FakeTensorMode
+    from matchmaker_amd import torch_ops, NativeError  # noqa: F401
+    channels, kernels, pools = MR.DEFAULT
+    flat = [x for p in pools for x in p]
+
+    def params(device, grad=False):
+        cin, w, b = 1, [], []
+        for c, k in zip(channels, kernels):
+            w.append(torch.empty(c, cin, k[0], k[1], device=device, requires_grad=grad))
+            b.append(torch.empty(c, device=device, requires_grad=grad))
+            cin = c
+        return w, b
+
+    with FakeTensorMode():
+        w, b = params("cuda")
+        f = torch.ops.mm_native.matchpyramid_features(torch.empty(nq, 30, 300, device="cuda"),
+                                                      torch.empty(B, 200, 300, device="cuda"), w, b, flat, ppq)
+        assert tuple(f.shape) == (B, 16 * 3 * 10) and f.dtype == torch.float32
+    w, b = params("meta", grad=True)
+    f = torch.ops.mm_native.matchpyramid_features(torch.empty(nq, 30, 64, device="meta"), torch.empty(B, 200, 64, device="meta"),
+                                                  w, b, flat, ppq)
+    with pytest.raises(NativeError, match="inference-only"):
+        f.sum().backward()
+
+
+def test_host_op_rejects_cpu_tensors_and_inconsistent_lists():
+    from matchmaker_amd import ops, NativeError
+    p = MR.random_params([4, 3], [[3, 3], [2, 2]], [[2, 2], [1, 2]], seed=1)
+    w, b = MR.conv_lists(p)
+    with pytest.raises(NativeError):
+        ops.matchpyramid_features(torch.zeros(1, 4, 16), torch.zeros(1, 9, 16), w, b, p["pools"])
+    arr, feat = ops._mp_layers(4, 9, w, b, p["pools"], "t")
+    assert list(arr) == [4, 3, 3, 2, 2, 3, 2, 2, 1, 2] and feat == 3 * 1 * 2
+    with pytest.raises(NativeError, match="pool sizes"):
+        ops._mp_layers(4, 9, w, b, p["pools"][:1], "t")
+    with pytest.raises(NativeError, match="after 4 channels"):
+        ops._mp_layers(4, 9, [w[0], w[0]], b, p["pools"], "t")
+
+
+def test_rank_list_is_decided_before_use():
+    q, d, p = MR.rank_inputs()
+    B = d.shape[0]
+    assert (q.shape[0], B, q.shape[1], d.shape[1], q.shape[2]) == MR.RANK_SHAPE
+    s64 = MR.score(q, d, p, torch.float64, B)
+    tol = MR.measured_tol(MR.score(q, d, p, torch.float32, B), s64)
+    share = MR.undecided_share(s64, tol)
+    print(f"rank list: tol = {tol:.3e}, undecided share = {share:.4f}")
+    assert share <= 0.01
+    assert float(s64.std()) > 100 * tol
