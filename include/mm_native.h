@@ -591,6 +591,37 @@ int mm_matchpyramid_fwd(const float* q, const float* d, const float* conv_w, con
                         int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int n_layers, const int32_t* layers,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ColBERT retrieval, candidate generation: token hits -> per query the documents that own a hit, with their row ranges.
+ *
+ * Replaces: the step between the token search and the aggregate of the ColBERT retrieval branch
+ *           matchmaker/dense_retrieval.py:391-412 (`current_ids`, read there before it is assigned, is meant to be the set
+ *           of documents of the token hits); the ranges feed mm_maxsim_ragged_fwd = forward_aggregation,
+ *           matchmaker/models/colbert.py:100-112.
+ *
+ *   hit_rows         [nq, H] int64 rows of the token matrix (the out_idx / out_rows of the token search); -1 = no hit
+ *   doc_begin_sorted, doc_end_sorted [n_docs] int64: the documents' row ranges sorted by (begin, end); non-empty ranges are
+ *                    disjoint; a zero-length range may share its begin with a document but not lie inside one
+ *   doc_of_sorted    [n_docs] int32: the document index (position in the store's seq_ids) of every sorted range, a permutation
+ *   A hit belongs to document j when begin[j] <= row < end[j]; hits of -1, rows outside [0, T) and rows no document owns are
+ *   dropped; a zero-length document owns nothing.
+ *   cand_doc   [nq, C_cap] int32: the distinct owning documents of the query, ASCENDING by document index, then -1
+ *   cand_begin, cand_end [nq, C_cap] int64: their row ranges, then (0, 0): with pairs_per_query = C_cap they are the doc_begin /
+ *              doc_end of mm_maxsim_ragged_fwd (an empty range costs nothing there)
+ *   cand_count [nq] int32: candidates of the query
+ *   One workgroup per query: binary search per hit, two int32 bitonic sorts in LDS, prefix sum, compaction.  Every output
+ *   element is written exactly once; no atomics, nothing read back or allocated: graph-capturable and bit-reproducible.
+ *   Limits: 1 <= H <= 16384, 1 <= n_docs < 2^31, T >= 0, C_cap >= min(H, n_docs); anything else returns MM_EUNSUPPORTED before
+ *   any launch; NULL pointers or nq < 0 return MM_EINVAL.  Whatever the hit values are, memory accesses stay in bounds.
+ *   workspace: mm_colbert_candidates_workspace_bytes(nq, H) bytes = 4 bytes per hit slot of the queries in flight.
+ */
+size_t mm_colbert_candidates_workspace_bytes(int nq, int H);
+
+int mm_colbert_candidates(const int64_t* hit_rows, const int64_t* doc_begin_sorted, const int64_t* doc_end_sorted,
+                          const int32_t* doc_of_sorted, int64_t n_docs, int64_t T, int nq, int H, int C_cap,
+                          int32_t* cand_doc, int64_t* cand_begin, int64_t* cand_end, int32_t* cand_count,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -817,6 +817,58 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
     return out_s, out_i
 
 
+COLBERT_MAX_HITS = 16384      # hits per query of mm_colbert_candidates (64 KB of int32 keys in LDS) = mm_topk_merge's n_in limit
+
+
+def colbert_candidates(hit_rows: torch.Tensor, begin_sorted: torch.Tensor, end_sorted: torch.Tensor,
+                       doc_of_sorted: torch.Tensor, T: int, c_cap: Optional[int] = None):
+    """Token hits -> candidate documents (the step between the token search and the aggregate of ColBERT retrieval,
+    matchmaker/dense_retrieval.py:391-412 + colbert.py:100-112; native mm_colbert_candidates).
+
+    hit_rows [nq, H] int64 rows of a T-row token matrix (-1 = no hit; rows outside [0, T) or owned by no document are
+    dropped); begin_sorted / end_sorted [n_docs] int64 = the documents' row ranges sorted by (begin, end), non-empty ranges
+    disjoint; doc_of_sorted [n_docs] int32 = the document index of every sorted range.  c_cap (default and minimum:
+    min(H, n_docs)) = slots per query.  Returns (cand_doc [nq, c_cap] int32 ascending then -1, cand_begin, cand_end
+    [nq, c_cap] int64 then (0, 0), count [nq] int32).  One enqueue on the current stream, no read-back: graph-capturable."""
+    dev = _dev_check(hit_rows, begin_sorted, end_sorted, doc_of_sorted)
+    if hit_rows.dim() != 2 or hit_rows.dtype != torch.int64:
+        raise NativeError(f"colbert_candidates: hit_rows must be int64 [nq, H], got {hit_rows.dtype} {tuple(hit_rows.shape)}")
+    n_docs = begin_sorted.numel()
+    if (begin_sorted.dim() != 1 or end_sorted.shape != begin_sorted.shape or doc_of_sorted.shape != begin_sorted.shape
+            or begin_sorted.dtype != torch.int64 or end_sorted.dtype != torch.int64 or doc_of_sorted.dtype != torch.int32):
+        raise NativeError("colbert_candidates: begin_sorted / end_sorted must be int64 [n_docs] and doc_of_sorted int32 [n_docs], "
+                          f"got {begin_sorted.dtype} {tuple(begin_sorted.shape)}, {end_sorted.dtype} {tuple(end_sorted.shape)}, "
+                          f"{doc_of_sorted.dtype} {tuple(doc_of_sorted.shape)}")
+    nq, H = hit_rows.shape
+    if not 1 <= H <= COLBERT_MAX_HITS:
+        raise NativeError(f"colbert_candidates: {H} hits per query outside 1 .. {COLBERT_MAX_HITS}", _lib.MM_EUNSUPPORTED)
+    if not 1 <= n_docs < 2 ** 31:
+        raise NativeError(f"colbert_candidates: {n_docs} documents outside 1 .. 2^31-1", _lib.MM_EUNSUPPORTED)
+    need = min(H, n_docs)
+    c_cap = need if c_cap is None else int(c_cap)
+    if c_cap < need:
+        raise NativeError(f"colbert_candidates: c_cap={c_cap} is below min(H, n_docs)={need}", _lib.MM_EUNSUPPORTED)
+    hit_rows = hit_rows if hit_rows.is_contiguous() else hit_rows.contiguous()
+    begin_sorted = begin_sorted if begin_sorted.is_contiguous() else begin_sorted.contiguous()
+    end_sorted = end_sorted if end_sorted.is_contiguous() else end_sorted.contiguous()
+    doc_of_sorted = doc_of_sorted if doc_of_sorted.is_contiguous() else doc_of_sorted.contiguous()
+    cand_doc = torch.empty((nq, c_cap), dtype=torch.int32, device=dev)
+    cand_begin = torch.empty((nq, c_cap), dtype=torch.int64, device=dev)
+    cand_end = torch.empty((nq, c_cap), dtype=torch.int64, device=dev)
+    count = torch.empty(nq, dtype=torch.int32, device=dev)
+    if nq == 0:
+        return cand_doc, cand_begin, cand_end, count
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_colbert_candidates_workspace_bytes, nq, H)
+        ws = _workspace(dev, wsb)
+        rc = L.mm_colbert_candidates(hit_rows.data_ptr(), begin_sorted.data_ptr(), end_sorted.data_ptr(), doc_of_sorted.data_ptr(),
+                                     n_docs, int(T), nq, H, c_cap, cand_doc.data_ptr(), cand_begin.data_ptr(),
+                                     cand_end.data_ptr(), count.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
+    _lib.check(rc, "mm_colbert_candidates")
+    return cand_doc, cand_begin, cand_end, count
+
+
 def _pacrr_params(weights, biases, C: int, dev):
     """Packs the conv weights ([C, 1, n, n] or [C, n, n], widths 2 .. N in order) and biases ([C] each) into the two float
     buffers of mm_pacrr_fwd: C * (4 + .. + N^2) weights, (N - 1) * C biases.  Returns (w, b) or (None, None) for N = 1."""

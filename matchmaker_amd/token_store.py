@@ -11,10 +11,14 @@ Here the filled parts of all files live in one device tensor [T, E] (8.8 M MSMAR
 tokens x 128 dims x 2 B = 158 GB fits one MI355X's 288 GB) and a whole batch of
 (query, candidate list) pairs is scored by ONE mm_maxsim_ragged_fwd launch that reads the candidate
 rows in place (no gather, no padding).
+
+`search` is the whole ColBERT retrieval of :391-412 on the device: token search over the resident matrix
+(ops.dot_topk, or an IVFFlatIPIndexer over the token rows), the documents that own the hits
+(ops.colbert_candidates), their MaxSim (ops.maxsim_ragged) and the top_n selection (ops.topk_merge).
 """
 import glob
 import os
-from typing import Dict, Iterable, List, Sequence, Tuple
+from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -23,7 +27,16 @@ from . import ops
 
 
 class TokenStore:
-    def __init__(self, tokens: torch.Tensor, seq_ids: Sequence, begin: np.ndarray, end: np.ndarray):
+    def __init__(self, tokens: torch.Tensor, seq_ids: Sequence, begin: np.ndarray, end: np.ndarray,
+                 topk_fn=None, candidates_fn=None, maxsim_fn=None, merge_fn=None):
+        """topk_fn(queries, matrix, k) / candidates_fn(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap) /
+        maxsim_fn(q, tokens, begin, end, None, pairs_per_query=, check_ranges=, sim_round=) / merge_fn(scores, ids, k) are what
+        search() runs; they default to ops.dot_topk / ops.colbert_candidates / ops.maxsim_ragged / ops.topk_merge (the CPU
+        test-suite injects stand-ins, as for the indexers of retrieval.py)."""
+        self._topk = topk_fn if topk_fn is not None else ops.dot_topk
+        self._candidates = candidates_fn if candidates_fn is not None else ops.colbert_candidates
+        self._maxsim = maxsim_fn if maxsim_fn is not None else ops.maxsim_ragged
+        self._merge = merge_fn if merge_fn is not None else ops.topk_merge
         self._tokens = tokens                         # [T, E] on the scoring device (read-only: the ranges below were validated against it)
         self._tokens_lowp = None                      # fp16 image of an fp32 store, built on the first use_fp16 aggregate()
         self.seq_ids = list(seq_ids)
@@ -34,6 +47,27 @@ class TokenStore:
         if self._begin.size and (self._begin.min() < 0 or self._end.max() > tokens.shape[0] or (self._begin > self._end).any()):
             raise ops.NativeError(f"TokenStore: document ranges leave the {tokens.shape[0]}-row token matrix "
                                   "(doc_infos of another store?)")
+        self._build_sorted_view()
+
+    def _build_sorted_view(self):
+        """The documents that hold rows, sorted by (begin, end): what search() finds the owner of a token row in.
+        Zero-length documents own no row and are left out; gaps between documents are allowed; two non-empty ranges that
+        overlap are refused, because a row of the overlap would have two owners."""
+        keep = np.nonzero(self._end > self._begin)[0]
+        order = keep[np.lexsort((self._end[keep], self._begin[keep]))]
+        b, e = self._begin[order], self._end[order]
+        clash = np.nonzero(b[1:] < e[:-1])[0]
+        if clash.size:
+            i, j = int(order[clash[0]]), int(order[clash[0] + 1])
+            raise ops.NativeError(f"TokenStore: documents {self.seq_ids[i]!r} (rows {self._begin[i]}..{self._end[i]}) and "
+                                  f"{self.seq_ids[j]!r} (rows {self._begin[j]}..{self._end[j]}) overlap: a token row must "
+                                  "belong to one document")
+        if len(self.seq_ids) >= 2 ** 31:
+            raise ops.NativeError("TokenStore: more than 2^31-1 documents")
+        dev = self._tokens.device
+        self._begin_sorted = torch.from_numpy(np.ascontiguousarray(b)).to(dev)
+        self._end_sorted = torch.from_numpy(np.ascontiguousarray(e)).to(dev)
+        self._doc_of_sorted = torch.from_numpy(order.astype(np.int32)).to(dev)
 
     @property
     def tokens(self) -> torch.Tensor:
@@ -109,16 +143,95 @@ class TokenStore:
         for i, n in enumerate(counts):
             bb[i, :n], ee[i, :n] = b[off: off + n], e[off: off + n]
             off += n
-        tokens = self.tokens
-        if use_fp16 and tokens.dtype == torch.float32:
-            if self._tokens_lowp is None:
-                self._tokens_lowp = tokens.to(torch.float16)
-            tokens = self._tokens_lowp
+        tokens = self._scoring_tokens(use_fp16)
         q = query_vecs.to(tokens.dtype)
         scores = ops.maxsim_ragged(q, tokens, bb.view(-1), ee.view(-1), None, pairs_per_query=C, check_ranges=False,
                                    sim_round=bool(use_fp16)).view(nq, C)
         scores = scores.cpu()
         return [[(candidates[i][j], float(scores[i, j])) for j in range(counts[i])] for i in range(nq)]
+
+    def _scoring_tokens(self, use_fp16: bool) -> torch.Tensor:
+        """The matrix the MaxSim reads: the store, or the fp16 image of an fp32 store under use_fp16 (see aggregate())."""
+        tokens = self.tokens
+        if use_fp16 and tokens.dtype == torch.float32:
+            if self._tokens_lowp is None:
+                self._tokens_lowp = tokens.to(torch.float16)
+            tokens = self._tokens_lowp
+        return tokens
+
+    # ------------------------------------------------------------------ retrieval: query token vectors -> ranked documents
+    def token_hits(self, query_vecs: torch.Tensor, token_top_k: int, index=None,
+                   query_chunk: Optional[int] = None) -> torch.Tensor:
+        """Steps 1-3 of search_device: hit_rows [nq, Q * token_top_k] int64 = for every LIVE query token (a vector with a
+        non-zero element; `search_type="encode"` multiplies by the mask, so padding is zero rows) the exact token_top_k rows of
+        the store by inner product of the 16-bit values (ops.dot_topk: equal scores go to the lower row), -1 for dead tokens.
+        index: an IVFFlatIPIndexer built with index_resident(ids=arange(T), vectors=tokens), so that its ids are token rows
+        (its probed lists are then searched instead of the whole matrix).  query_chunk bounds the tokens per search call."""
+        nq, Q, E = query_vecs.shape
+        k = int(token_top_k)
+        if k < 1 or Q * k > ops.COLBERT_MAX_HITS:
+            raise ops.NativeError(f"TokenStore.search: Q * token_top_k = {Q} * {k} hits per query outside 1 .. "
+                                  f"{ops.COLBERT_MAX_HITS} (the candidate kernel sorts a query's hits in 64 KB of LDS)",
+                                  ops._lib.MM_EUNSUPPORTED)
+        dev = self._tokens.device
+        q = query_vecs.to(dev).reshape(nq * Q, E)
+        live = torch.nonzero((q != 0).any(dim=1)).flatten()
+        hits = torch.full((nq * Q, k), -1, dtype=torch.int64, device=dev)
+        matrix = self._scoring_tokens(True)              # the 16-bit matrix: the store, or an fp32 store's fp16 image
+        qs = q.to(matrix.dtype)
+        step = int(query_chunk) if query_chunk else max(int(live.numel()), 1)
+        for a in range(0, int(live.numel()), step):
+            sel = live[a: a + step]
+            rows = index.search_device(qs[sel], k)[1] if index is not None else self._topk(qs[sel].contiguous(), matrix, k)[1]
+            hits[sel] = rows
+        return hits.view(nq, Q * k)
+
+    def rank_hits(self, query_vecs: torch.Tensor, hit_rows: torch.Tensor, top_n: int, use_fp16: bool = True,
+                  trim: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Steps 4-7 of search_device: the documents that own hit_rows [nq, H], their MaxSim against query_vecs, the top_n.
+        trim=False keeps min(H, documents) candidate slots per query instead of reading the largest count back: nothing
+        then synchronises and the four launches can be captured into a graph (one chain, no parallel branches)."""
+        nq = query_vecs.shape[0]
+        dev = self._tokens.device
+        n_docs = int(self._begin_sorted.numel())
+        if nq == 0 or n_docs == 0:
+            return (torch.full((nq, top_n), float("-inf"), dtype=torch.float32, device=dev),
+                    torch.full((nq, top_n), -1, dtype=torch.int64, device=dev))
+        cand_doc, cb, ce, count = self._candidates(hit_rows, self._begin_sorted, self._end_sorted, self._doc_of_sorted,
+                                                   int(self._tokens.shape[0]), min(hit_rows.shape[1], n_docs))
+        if trim:
+            C = max(int(count.max()), 1)                 # the one read-back: the slots behind it are padding in every query
+            cand_doc, cb, ce = cand_doc[:, :C].contiguous(), cb[:, :C].contiguous(), ce[:, :C].contiguous()
+        C = cand_doc.shape[1]
+        tokens = self._scoring_tokens(use_fp16)
+        scores = self._maxsim(query_vecs.to(dev).to(tokens.dtype), tokens, cb.view(-1), ce.view(-1), None, pairs_per_query=C,
+                              check_ranges=False, sim_round=bool(use_fp16)).view(nq, C)
+        scores = scores.masked_fill(cand_doc < 0, float("-inf"))
+        # ascending cand_doc + the merge's input order on ties = equal scores go to the lower document index
+        return self._merge(scores, cand_doc.to(torch.int64), int(top_n))
+
+    def search_device(self, query_vecs: torch.Tensor, top_n: int, token_top_k: int, use_fp16: bool = True, index=None,
+                      query_chunk: Optional[int] = None, trim: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+        """ColBERT retrieval (dense_retrieval.py:391-412) for query_vecs [nq, Q, E], without a host round trip per query:
+          1-3. token_hits(): the token_top_k best token rows of every live query token;
+          4.   the candidates = the documents that own at least one hit row (ops.colbert_candidates);
+          5.   one read-back of the largest candidate count, to trim the slots (trim=False: none, see rank_hits());
+          6.   forward_aggregation of the query against every candidate, exactly as aggregate() computes it (use_fp16 as
+               there; dead query tokens add 0);
+          7.   the top_n by score, equal scores to the lower document index.
+        Returns (scores [nq, top_n] float32 descending, doc_idx [nq, top_n] int64 = positions in self.seq_ids); (-inf, -1)
+        where a query has fewer than top_n candidates."""
+        hits = self.token_hits(query_vecs, token_top_k, index=index, query_chunk=query_chunk)
+        return self.rank_hits(query_vecs, hits, top_n, use_fp16=use_fp16, trim=trim)
+
+    def search(self, query_vecs: torch.Tensor, top_n: int, token_top_k: int, use_fp16: bool = True, index=None,
+               query_chunk: Optional[int] = None) -> List[List[Tuple[object, float]]]:
+        """search_device() mapped to the reference's result shape: per query [(seq_id, score)] best first, like
+        `validation_results[query_id]` (:410-412); shorter than top_n when the query has fewer candidates."""
+        s, d = self.search_device(query_vecs, top_n, token_top_k, use_fp16=use_fp16, index=index, query_chunk=query_chunk)
+        s, d = s.cpu().numpy(), d.cpu().numpy()
+        ids = self.seq_ids
+        return [[(ids[j], float(x)) for x, j in zip(s[i], d[i]) if j >= 0] for i in range(s.shape[0])]
 
 
 def write_reference_store(folder: str, docs: Sequence[np.ndarray], seq_ids: Sequence, token_block_size: int,

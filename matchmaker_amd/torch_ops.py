@@ -10,6 +10,8 @@ Importing this module defines
                                     pairs_per_query=1, d_gate=None, clamp_min=1e-10) -> [n_pairs]
     torch.ops.mm_native.tkl_window_pool(q_ctx, chunks, chunk_mask, chunk_slot, q_mask, params,
                                         B, C, K, saturation)                        -> (score [B], windows [B, W])
+    torch.ops.mm_native.colbert_candidates(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T,
+                                           c_cap=None)          -> (cand_doc, cand_begin, cand_end, count)
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
@@ -342,3 +344,20 @@ def _matchpyramid_backward(ctx, g):
 
 matchpyramid_features.register_autograd(_matchpyramid_backward, setup_context=_matchpyramid_setup)
 torch.library.register_autocast(_NS + "::matchpyramid_features", "cuda", torch.float32)
+
+
+# ---------------------------------------------------------------------------------------------- ColBERT retrieval
+@torch.library.custom_op(_NS + "::colbert_candidates", mutates_args=(), device_types="cuda")
+def colbert_candidates(hit_rows: Tensor, begin_sorted: Tensor, end_sorted: Tensor, doc_of_sorted: Tensor, T: int,
+                       c_cap: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """(cand_doc [nq, c_cap] int32, cand_begin, cand_end [nq, c_cap] int64, count [nq] int32): the documents that own the token
+    hits of every query (dense_retrieval.py:391-412).  Integer in, integer out: no autograd formula."""
+    return ops.colbert_candidates(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap)
+
+
+@colbert_candidates.register_fake
+def _(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap=None):
+    nq, H = hit_rows.shape
+    C = min(H, begin_sorted.shape[0]) if c_cap is None else c_cap
+    return (hit_rows.new_empty((nq, C), dtype=torch.int32), hit_rows.new_empty((nq, C), dtype=torch.int64),
+            hit_rows.new_empty((nq, C), dtype=torch.int64), hit_rows.new_empty((nq,), dtype=torch.int32))
