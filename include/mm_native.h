@@ -434,6 +434,43 @@ int mm_ivf_scan_fwd(const void* queries, const void* vectors, const int64_t* lis
                     float* out_scores, int64_t* out_rows, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * k-means building blocks: maximum-inner-product assignment against a centroid table, and the
+ * per-list sums of rows (IVF training, TAS-Balanced query clustering).
+ *
+ * Replaces: FaissDynamicIndexer.prepare / .search_single   matchmaker/retrieval/faiss_indices.py:323-352, 401-428
+ *           (faiss k-means over the query vectors; the quantizer's nearest centroid with nprobe = 1)
+ *           and the per-query assignment loop               matchmaker/distillation/query_clusterer.py:218-221
+ *
+ * mm_kmeans_assign
+ *   x [n, E], centroids [nlist, E]  float16 / bfloat16 of one dtype, E in {128, 256, 384, 512, 768}.
+ *   out_list [n] int32 = the centroid of maximum inner product, out_score [n] float32 = that product
+ *   (fp32-accumulated products of the 16-bit values).  Equal scores: the LOWEST centroid number wins
+ *   (the "lower row first" rule of mm_dot_topk_fwd); an all-zero row goes to centroid 0.
+ *   1 <= nlist <= 65536, 0 <= n < 2^31 (else MM_EUNSUPPORTED, before any launch); n = 0 succeeds
+ *   without a launch.  One launch on `stream`: a workgroup reads its 128 rows of x once, walks the
+ *   centroid table in blocks of 32 and keeps a running (max, arg) per row in registers; no [n, nlist]
+ *   score matrix, no workspace, no status word.  Graph-capturable.
+ *
+ * mm_kmeans_segment_sum
+ *   x [n, E] as above; order [n] int64 = the rows of x list by list; list_begin [nlist + 1] int64,
+ *   non-decreasing, lists may be empty (values are clamped to [0, n]).
+ *   sums [nlist, E] float32: sums[l] = sum of x[order[j]], list_begin[l] <= j < list_begin[l + 1], in
+ *   fp32; a row of zeros for an empty list.  order[j] outside [0, n) is skipped.
+ *   Every element of sums is written exactly once, without atomics, and the result is a pure function
+ *   of the inputs (bit-equal run to run): a list is cut into chunks of 512 rows, a chunk is summed by
+ *   one workgroup in a fixed order, the chunks of a list are added in ascending order.
+ *   workspace: mm_kmeans_segment_sum_workspace_bytes(n, nlist, E) bytes = 4 (nlist + 1) + 4 E
+ *   (n / 512 + nlist), each rounded up to 256.  Same limits as above.  Three launches on `stream`,
+ *   nothing read back: graph-capturable. */
+int mm_kmeans_assign(const void* x, const void* centroids, int64_t n, int nlist, int E, int dtype,
+                     int32_t* out_list, float* out_score, void* stream);
+
+size_t mm_kmeans_segment_sum_workspace_bytes(int64_t n, int nlist, int E);
+
+int mm_kmeans_segment_sum(const void* x, const int64_t* order, const int64_t* list_begin, int64_t n, int nlist, int E,
+                          int dtype, float* sums, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * PACRR: cosine match matrix -> n-gram convolutions + channel max -> per-row k-max pooling, fused.
  *
  *   cos[i,j]  = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))            (allennlp cosine, pacrr.py:78)

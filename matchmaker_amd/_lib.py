@@ -62,6 +62,9 @@ SIGNATURES = {
     "mm_tkl_fwd_peaks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_ivf_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "mm_ivf_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mm_kmeans_assign": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
+    "mm_kmeans_segment_sum_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "mm_kmeans_segment_sum": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "mm_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
     "mm_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),

@@ -800,6 +800,79 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     return out_s, out_r
 
 
+_KMEANS_DIMS = (128, 256, 384, 512, 768)
+
+
+def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
+    """Maximum-inner-product assignment against a centroid table (the coarse quantiser of an IVF index with nprobe = 1:
+    matchmaker/retrieval/faiss_indices.py:401-428, the loop of matchmaker/distillation/query_clusterer.py:218-221; native
+    mm_kmeans_assign).
+
+    x [n, E], centroids [nlist, E] float16 / bfloat16 of one dtype, E in {128,...,768} (pad otherwise), 1 <= nlist <= 65536.
+    Returns (list [n] int32, score [n] float32 = the fp32-accumulated inner product with that centroid); equal scores: the
+    lowest centroid number.  One enqueue on the current stream, no workspace, no read-back: graph-capturable."""
+    dev = _dev_check(x, centroids)
+    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
+        raise NativeError(f"kmeans_assign: expected [n, E] and [nlist, E], got {tuple(x.shape)} {tuple(centroids.shape)}")
+    if x.dtype != centroids.dtype or x.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"kmeans_assign: float16 / bfloat16 vectors of one dtype needed, got {x.dtype} / {centroids.dtype}")
+    n, E = x.shape
+    nlist = centroids.shape[0]
+    if E not in _KMEANS_DIMS:
+        raise NativeError(f"kmeans_assign: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    if not 1 <= nlist <= 65536 or n >= 1 << 31:
+        raise NativeError(f"kmeans_assign: nlist={nlist} outside 1 .. 65536, or n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
+    x = x if x.is_contiguous() else x.contiguous()
+    centroids = centroids if centroids.is_contiguous() else centroids.contiguous()
+    out_l = torch.empty(n, dtype=torch.int32, device=dev)
+    out_s = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out_l, out_s
+    L = _lib.lib()
+    with _on(dev):
+        rc = L.mm_kmeans_assign(x.data_ptr(), centroids.data_ptr(), n, nlist, E, _DT[x.dtype], out_l.data_ptr(),
+                                out_s.data_ptr(), _stream(dev))
+    _lib.check(rc, "mm_kmeans_assign")
+    return out_l, out_s
+
+
+def kmeans_segment_sum(x: torch.Tensor, order: torch.Tensor, list_begin: torch.Tensor):
+    """Per-list fp32 sums of rows (the centroid update of k-means; native mm_kmeans_segment_sum).
+
+    x [n, E] float16 / bfloat16, E in {128,...,768}; order [n] int64 = the rows of x list by list; list_begin [nlist + 1]
+    int64, non-decreasing (lists may be empty).  Returns sums [nlist, E] float32, sums[l] = the sum of x[order[j]] for
+    list_begin[l] <= j < list_begin[l + 1]; zeros for an empty list; rows of `order` outside [0, n) are skipped.  No
+    atomics: the result is a pure function of the inputs, bit-equal run to run.  Enqueued on the current stream, no
+    read-back: graph-capturable."""
+    dev = _dev_check(x, order, list_begin)
+    if x.dim() != 2 or x.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"kmeans_segment_sum: expected float16 / bfloat16 [n, E], got {x.dtype} {tuple(x.shape)}")
+    if order.dim() != 1 or order.dtype != torch.int64 or order.shape[0] != x.shape[0]:
+        raise NativeError(f"kmeans_segment_sum: order must be int64 [n], got {order.dtype} {tuple(order.shape)}")
+    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
+        raise NativeError(f"kmeans_segment_sum: list_begin must be int64 [nlist + 1], got {list_begin.dtype} "
+                          f"{tuple(list_begin.shape)}")
+    n, E = x.shape
+    nlist = list_begin.shape[0] - 1
+    if E not in _KMEANS_DIMS:
+        raise NativeError(f"kmeans_segment_sum: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)",
+                          _lib.MM_EUNSUPPORTED)
+    if nlist > 65536 or n >= 1 << 31:
+        raise NativeError(f"kmeans_segment_sum: nlist={nlist} outside 1 .. 65536, or n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
+    x = x if x.is_contiguous() else x.contiguous()
+    order = order if order.is_contiguous() else order.contiguous()
+    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
+    sums = torch.empty((nlist, E), dtype=torch.float32, device=dev)
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_kmeans_segment_sum_workspace_bytes, n, nlist, E)
+        ws = _workspace(dev, wsb)
+        rc = L.mm_kmeans_segment_sum(x.data_ptr() if n else None, order.data_ptr() if n else None, list_begin.data_ptr(), n,
+                                     nlist, E, _DT[x.dtype], sums.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
+    _lib.check(rc, "mm_kmeans_segment_sum")
+    return sums
+
+
 def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
     """Rows of (score, id) candidates [nq, n_in] -> the k best per row (score descending, input order on
     ties); ids < 0 are padding.  The sharded index's final merge (mm_topk_merge)."""

@@ -12,6 +12,11 @@ merges them natively (mm_topk_merge).  Used from dense_retrieval.py:308-328 (con
 IVFFlatIPIndexer (faiss_index_type: ivf) has the surface of `FaissIVFIndexer` (faiss_indices.py:106-145): spherical
 k-means centroids, the shard stored list by list, probe selection with the same top-k kernel and the exact scan of
 the probed lists by mm_ivf_scan_fwd.
+
+DynamicIVFIndexer has the surface of `FaissDynamicIndexer` (faiss_indices.py:307-428), the index behind TAS-Balanced query
+clustering (matchmaker/distillation/query_clusterer.py:187-221): k-means over the query vectors, one probe, entries that
+can be replaced.  Its k-means (`spherical_kmeans`) runs on mm_kmeans_assign / mm_kmeans_segment_sum; IVFFlatIPIndexer
+takes the same path with `native_kmeans=True`.
 """
 from typing import List, Optional
 
@@ -58,6 +63,62 @@ def _merge_shards(s: torch.Tensor, ids: torch.Tensor, top_n: int, group, merge_f
         s, ids = merge_fn(gs.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1),
                           gi.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1), top_n)
     return s, ids
+
+
+def _unit_rows(c: torch.Tensor) -> torch.Tensor:
+    return c / c.norm(dim=1, keepdim=True).clamp_min(1e-20)
+
+
+def _lists_of(a: torch.Tensor, nlist: int):
+    """An assignment [n] -> (order [n] int64 = the rows list by list, input order inside a list; list_begin [nlist + 1]
+    int64; counts [nlist] int64)."""
+    a = a.to(torch.int64)
+    order = torch.sort(a, stable=True).indices
+    counts = torch.bincount(a, minlength=nlist)
+    lb = torch.zeros(nlist + 1, dtype=torch.int64, device=a.device)
+    lb[1:] = torch.cumsum(counts, 0)
+    return order, lb, counts
+
+
+def spherical_kmeans(x: torch.Tensor, nlist: int, iters: int = 20, seed: int = 208973249, init: Optional[torch.Tensor] = None,
+                     assign_fn=None, sum_fn=None) -> torch.Tensor:
+    """Spherical k-means for inner-product lists: -> centroids [nlist, E_pad] float16 of unit length.
+
+    x [n, E] float16 (zero-padded to E_pad here when E is not one of the native widths).  The start is `init`
+    ([nlist, E_pad]) when given, else a sample of nlist rows drawn with `seed`; every iteration assigns each row to its
+    maximum-inner-product centroid (ops.kmeans_assign: lowest centroid on equal scores), sums the rows of every list in
+    fp32 (ops.kmeans_segment_sum over a stable sort of the assignment: no atomics) and normalises the sums; an empty
+    cluster is re-seeded from a vector of the largest one.  Every step is a pure function of its inputs, so two runs from
+    one seed give bit-equal centroids.  assign_fn(x, centroids) -> (list, score) / sum_fn(x, order, list_begin) -> sums
+    default to the native operators; the CPU test-suite injects stand-ins."""
+    assign_fn = assign_fn if assign_fn is not None else ops.kmeans_assign
+    sum_fn = sum_fn if sum_fn is not None else ops.kmeans_segment_sum
+    if x.dim() != 2 or x.dtype != torch.float16:
+        raise ops.NativeError(f"spherical_kmeans: expected float16 [n, E], got {x.dtype} {tuple(x.shape)}")
+    E_pad = _pad_dim(x.shape[1])
+    if x.shape[1] != E_pad:
+        x = torch.nn.functional.pad(x, (0, E_pad - x.shape[1]))
+    x = x.contiguous()
+    n = x.shape[0]
+    if not 1 <= nlist <= n:
+        raise ops.NativeError(f"spherical_kmeans: {n} training vectors for {nlist} centroids")
+    if init is None:
+        gen = torch.Generator().manual_seed(int(seed))
+        init = _unit_rows(x[torch.randperm(n, generator=gen)[:nlist].to(x.device)].float())
+    elif tuple(init.shape) != (nlist, E_pad):
+        raise ops.NativeError(f"spherical_kmeans: init must be [{nlist}, {E_pad}], got {tuple(init.shape)}")
+    cent = init.to(device=x.device, dtype=torch.float16).contiguous()
+    for _ in range(iters):
+        a = assign_fn(x, cent)[0]
+        order, lb, counts = _lists_of(a, nlist)
+        sums = sum_fn(x, order, lb)
+        empty = torch.nonzero(counts == 0).flatten()
+        if empty.numel():
+            big = int(counts.argmax())
+            members = order[lb[big]: lb[big + 1]]                 # ascending rows of the largest cluster
+            sums[empty] = x[members[torch.arange(empty.numel(), device=x.device) % members.numel()]].float()
+        cent = _unit_rows(sums).to(torch.float16).contiguous()
+    return cent
 
 
 class FlatIPIndexer:
@@ -150,9 +211,16 @@ class IVFFlatIPIndexer:
     ASSIGN_CHUNK = 1 << 14       # vectors per assignment call (bounds the top-k workspace)
     SUM_CHUNK = 1 << 18          # vectors per fp32 conversion of the centroid update
 
-    def __init__(self, config, device=None, group=None, topk_fn=None, scan_fn=None, merge_fn=None):
+    def __init__(self, config, device=None, group=None, topk_fn=None, scan_fn=None, merge_fn=None, native_kmeans: bool = False,
+                 assign_fn=None, sum_fn=None):
         """topk_fn(queries, vectors, k) / scan_fn(queries, vectors, list_begin, probes, k) / merge_fn(scores, ids, k)
-        default to ops.dot_topk / ops.ivf_scan / ops.topk_merge; the CPU test-suite injects stand-ins."""
+        default to ops.dot_topk / ops.ivf_scan / ops.topk_merge; the CPU test-suite injects stand-ins.
+        native_kmeans (opt-in): training and list assignment go through `spherical_kmeans` = ops.kmeans_assign /
+        ops.kmeans_segment_sum (assign_fn / sum_fn stand in for them) instead of the top-k operator and index_add_: same
+        sample, same loop, and centroids that are bit-equal from run to run."""
+        self.native_kmeans = bool(native_kmeans)
+        self._kassign = assign_fn if assign_fn is not None else ops.kmeans_assign
+        self._ksum = sum_fn if sum_fn is not None else ops.kmeans_segment_sum
         self._topk = topk_fn if topk_fn is not None else ops.dot_topk
         self._scan = scan_fn if scan_fn is not None else ops.ivf_scan
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
@@ -194,6 +262,8 @@ class IVFFlatIPIndexer:
 
     def _assign(self, x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
         """[n] int64: the centroid of maximum inner product for every row of x."""
+        if self.native_kmeans:
+            return self._kassign(x, centroids)[0].to(torch.int64)
         out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
         for a in range(0, x.shape[0], self.ASSIGN_CHUNK):
             out[a: a + self.ASSIGN_CHUNK] = self._topk(x[a: a + self.ASSIGN_CHUNK], centroids, 1)[1][:, 0]
@@ -248,7 +318,10 @@ class IVFFlatIPIndexer:
         if rank == 0:
             n = x.shape[0]
             cent = self._unit(x[torch.randperm(n, generator=gen)[: self.nlist].to(x.device)].float()).to(self.dtype)
-            for _ in range(self.KMEANS_ITERS):
+            if self.native_kmeans:
+                cent = spherical_kmeans(x, self.nlist, iters=self.KMEANS_ITERS, init=cent, assign_fn=self._kassign,
+                                        sum_fn=self._ksum)
+            for _ in range(0 if self.native_kmeans else self.KMEANS_ITERS):
                 a = self._assign(x, cent)
                 sums = torch.zeros((self.nlist, self.E_pad), dtype=torch.float32, device=x.device)
                 for lo in range(0, n, self.SUM_CHUNK):      # fp32 copies of SUM_CHUNK rows at a time, in input order
@@ -332,3 +405,174 @@ class IVFFlatIPIndexer:
         self.nprobe = int(z["nprobe"])
         if config_overwrites is not None and "faiss_ivf_search_probe_count" in config_overwrites:
             self.nprobe = int(config_overwrites["faiss_ivf_search_probe_count"])
+
+
+class DynamicIVFIndexer:
+    """Drop-in for the reference's dynamic IVF index (`FaissDynamicIndexer`, faiss_indices.py:307-428), the index behind
+    TAS-Balanced query clustering (matchmaker/distillation/query_clusterer.py:187-221): `prepare` trains
+    `faiss_ivf_list_count` centroids by spherical k-means (mm_kmeans_assign / mm_kmeans_segment_sum), `index_all` and
+    `update` put every vector into the list of its maximum-inner-product centroid (`list_n_probe` = 1),
+    `search_single` returns the exact top_n of the query's list together with the centroid it hit.  Single process, as
+    the reference's.
+
+    Storage: vectors, ids and list numbers are kept in ARRIVAL order on the device; the list-by-list view that the scan
+    needs (`vectors`, `ids`, `list_begin`) is rebuilt by a stable sort the first time it is read after `index_all` /
+    `update`.  That makes an update O(n), which is right for the clusterer's sizes (hundreds of thousands of queries,
+    updated a batch at a time), not for a collection of billions.  Order inside a list (faiss promises none): arrival
+    order; an updated entry moves to the end of its new list.
+
+    Differences from the reference: centroids and vectors are float16 (faiss keeps fp32 centroids beside its fp16
+    lists) and queries are rounded to float16; `prepare(subsample >= 0)` trains on the sampled rows only, not on the zero
+    rows the reference's integer division leaves at the end of its training matrix."""
+
+    KMEANS_ITERS = 20            # faiss ClusteringParameters.niter
+
+    def __init__(self, config, device=None, assign_fn=None, sum_fn=None, scan_fn=None):
+        """assign_fn(x, centroids) / sum_fn(x, order, list_begin) / scan_fn(queries, vectors, list_begin, probes, k) default
+        to ops.kmeans_assign / ops.kmeans_segment_sum / ops.ivf_scan; the CPU test-suite injects stand-ins."""
+        self._kassign = assign_fn if assign_fn is not None else ops.kmeans_assign
+        self._ksum = sum_fn if sum_fn is not None else ops.kmeans_segment_sum
+        self._scan = scan_fn if scan_fn is not None else ops.ivf_scan
+        self.list_n_probe = 1
+        self.token_dim = config["token_dim"]
+        self.faiss_ivf_list_count = int(config["faiss_ivf_list_count"])
+        self.nlist = self.faiss_ivf_list_count
+        if not 1 <= self.nlist <= 65536:
+            raise ops.NativeError("faiss_ivf_list_count must be in 1 .. 65536")
+        if not config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16"):
+            raise ops.NativeError("DynamicIVFIndexer stores float16 centroids and lists and rounds queries to float16: set "
+                                  "token_dtype: float16, or keep faiss for an fp32 index")
+        self.seed = int(config.get("random_seed", 208973249))
+        self.dtype = torch.float16
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
+        self.E_pad = _pad_dim(self.token_dim)
+        self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
+        self._vec = torch.zeros((0, self.E_pad), dtype=self.dtype, device=self.device)      # arrival order
+        self._ids = torch.zeros(0, dtype=torch.int64, device=self.device)
+        self._lists = torch.zeros(0, dtype=torch.int64, device=self.device)
+        self._view = None                                      # (vectors, ids, list_begin, ids on the host, list_begin on the host)
+
+    # ---- training -----------------------------------------------------------------------------------------------------
+    def _to_device(self, a: np.ndarray) -> torch.Tensor:
+        vec = torch.zeros((a.shape[0], self.E_pad), dtype=self.dtype, device=self.device)
+        vec[:, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(a)).to(self.device).to(self.dtype)
+        return vec
+
+    @staticmethod
+    def train_rows(chunk_sizes: List[int], subsample) -> List[np.ndarray]:
+        """The rows of every chunk but the last that `prepare(subsample > -1)` trains on: faiss_indices.py:335-345 —
+        RandomState(123), one choice(..., replace=False) of int(total * subsample) // (len(chunks) - 1) rows per chunk, in
+        chunk order."""
+        if len(chunk_sizes) < 2:
+            raise ops.NativeError("DynamicIVFIndexer.prepare: subsample needs at least two chunks (rows are drawn from every "
+                                  "chunk but the last; the reference divides by len(data_chunks) - 1 = 0 here)")
+        per_chunk = int(sum(chunk_sizes) * subsample) // (len(chunk_sizes) - 1)
+        rs = np.random.RandomState(123)
+        return [rs.choice(c, size=per_chunk, replace=False) for c in chunk_sizes[:-1]]
+
+    def prepare(self, data_chunks: List[np.ndarray], subsample=-1):
+        """subsample = -1 trains on every vector; subsample > -1 on the rows `train_rows` names."""
+        if subsample > -1:
+            rows = self.train_rows([c.shape[0] for c in data_chunks], subsample)
+            parts = [c[r] for c, r in zip(data_chunks, rows)]
+        else:
+            parts = list(data_chunks)
+        n = sum(p.shape[0] for p in parts)
+        if n < self.nlist:
+            raise ops.NativeError(f"DynamicIVFIndexer.prepare: {n} training vectors for faiss_ivf_list_count = {self.nlist}")
+        x = torch.cat([self._to_device(p) for p in parts])
+        self.centroids = spherical_kmeans(x, self.nlist, iters=self.KMEANS_ITERS, seed=self.seed, assign_fn=self._kassign,
+                                          sum_fn=self._ksum)
+
+    # ---- entries ------------------------------------------------------------------------------------------------------
+    def _add(self, ids: np.ndarray, data: np.ndarray):
+        if self.centroids is None:
+            raise ops.NativeError("DynamicIVFIndexer: prepare() first")
+        if data.shape[0] != ids.shape[0]:
+            raise ops.NativeError(f"DynamicIVFIndexer: {ids.shape[0]} ids for {data.shape[0]} vectors")
+        if ids.shape[0] == 0:
+            return
+        vec = self._to_device(data)
+        self._vec = torch.cat([self._vec, vec])
+        self._ids = torch.cat([self._ids, torch.from_numpy(ids).to(self.device)])
+        self._lists = torch.cat([self._lists, self._kassign(vec, self.centroids)[0].to(torch.int64)])
+        self._view = None
+
+    def index_all(self, ids, data_chunks):
+        """faiss_indices.py:355-359: chunk i adds its first len(ids[i]) vectors under ids[i]."""
+        i = [np.array(x, dtype=np.int64) for x in ids]
+        self._add(np.concatenate(i) if i else np.zeros(0, np.int64),
+                  np.concatenate([np.asarray(c)[: len(k)] for c, k in zip(data_chunks, i)]) if i else np.zeros((0, self.token_dim)))
+
+    def update(self, ids, data):
+        """faiss_indices.py:368-375: every stored entry whose id is in `ids` is removed, then data[:len(ids)] is added under
+        those ids, assigned to the unchanged centroids (unknown ids are simply added)."""
+        ids = np.array(ids, dtype=np.int64)
+        keep = ~torch.isin(self._ids, torch.from_numpy(ids).to(self.device))
+        self._vec, self._ids, self._lists = self._vec[keep], self._ids[keep], self._lists[keep]
+        self._view = None
+        self._add(ids, np.asarray(data)[: len(ids)])
+
+    def _lists_view(self):
+        if self._view is None:
+            order, lb, _ = _lists_of(self._lists, self.nlist)
+            ids = self._ids[order].contiguous()
+            self._view = (self._vec[order].contiguous(), ids, lb, ids.cpu().numpy(), lb.cpu().numpy())
+        return self._view
+
+    @property
+    def vectors(self) -> torch.Tensor:
+        """[n, E_pad] float16, list by list"""
+        return self._lists_view()[0]
+
+    @property
+    def ids(self) -> torch.Tensor:
+        """[n] int64 external ids, in the order of `vectors`"""
+        return self._lists_view()[1]
+
+    @property
+    def list_begin(self) -> torch.Tensor:
+        """[nlist + 1] int64"""
+        return self._lists_view()[2]
+
+    def get_entries_from_centroids(self, centroid_ids) -> list:
+        """faiss_indices.py:383-393: the ids stored in the named lists, list after list (arrival order inside a list)."""
+        _, _, _, ids, lb = self._lists_view()
+        out = []
+        for l in centroid_ids:
+            out.extend(ids[lb[int(l)]: lb[int(l) + 1]].tolist())
+        return out
+
+    def get_all_cluster_assignments(self) -> list:
+        return [self.get_entries_from_centroids([c]) for c in range(self.nlist)]
+
+    # ---- search -------------------------------------------------------------------------------------------------------
+    def assign(self, query_vecs) -> torch.Tensor:
+        """[nq] int64 (device): the centroid of maximum inner product of every query (lowest number on equal scores)."""
+        if self.centroids is None:
+            raise ops.NativeError("DynamicIVFIndexer: prepare() first")
+        qd = _device_queries(query_vecs, self.dtype, self.E_pad, self.token_dim, self.device)
+        return self._kassign(qd, self.centroids)[0].to(torch.int64)
+
+    def cluster_assignments(self, query_vecs, seq_ids) -> List[list]:
+        """The loop of query_clusterer.py:205-221 as one device call: clusters[c] = the seq_ids whose query hits centroid c,
+        in input order."""
+        a = self.assign(query_vecs).cpu().tolist()
+        if len(a) != len(seq_ids):
+            raise ops.NativeError(f"cluster_assignments: {len(seq_ids)} seq_ids for {len(a)} queries")
+        clusters = [[] for _ in range(self.nlist)]
+        for c, sid in zip(a, seq_ids):
+            clusters[c].append(sid)
+        return clusters
+
+    def search_single(self, query_vec, top_n: int):
+        """faiss_indices.py:401-428: (scores [nq, top_n] float32 descending, ids [nq, top_n] int64, centroid_ids [nq, 1]
+        int64) as numpy arrays; (-inf, -1) where the list holds fewer than top_n entries."""
+        if self.centroids is None:
+            raise ops.NativeError("DynamicIVFIndexer: prepare() first")
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
+        cids = self._kassign(qd, self.centroids)[0]
+        vectors, ids, lb = self._lists_view()[:3]
+        s, rows = self._scan(qd, vectors, lb, cids.to(torch.int32)[:, None].contiguous(), top_n)
+        out = torch.where(rows >= 0, ids[rows.clamp(min=0)], rows) if ids.numel() else rows
+        return s.cpu().numpy(), out.cpu().numpy(), cids.to(torch.int64)[:, None].cpu().numpy()
