@@ -25,7 +25,6 @@ namespace mm {
 namespace {
 
 constexpr int kDQmax = 64, kDEmax = 1024, kDDmax = 65535, kDBmax = 16;
-constexpr float kTiny = 1e-13f;   // allennlp's cosine (mm_native.h, kernel pooling)
 
 struct DrmmArgs {
   const float* q;
@@ -141,10 +140,6 @@ __device__ __forceinline__ float finish_rows(const DrmmArgs& a, int64_t pair, Bi
     if (own) s = a.gate[g * a.Q + row] * tanhf(o);
   }
   return s;
-}
-
-__device__ __forceinline__ f32x4 load4_or0(const float* p, bool ok) {
-  return ok ? *(const f32x4*)p : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
 }
 
 __device__ __forceinline__ int pair_len(const DrmmArgs& a, int64_t p) {

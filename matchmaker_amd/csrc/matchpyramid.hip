@@ -4,8 +4,8 @@
 // own slice ("slot") of the workspace.  The number of slots is bounded, so the workspace does not grow with the batch.
 //
 // Arithmetic:
-//   cosine   as pacrr.hip: <q_i, d_j> * 1/(|q_i| + 1e-13) * 1/(|d_j| + 1e-13), the dot on v_mfma_f32_32x32x2_f32, the four
-//            wavefronts split E and their partial tiles are summed in fixed order;
+//   cosine   the PACRR family's block (pacrr_device.h): <q_i, d_j> * 1/(|q_i| + 1e-13) * 1/(|d_j| + 1e-13), the dot on
+//            v_mfma_f32_32x32x2_f32, the four wavefronts split E and their partial tiles are summed in fixed order;
 //   conv     an im2col product [C_l x C_{l-1} kh kw] x [C_{l-1} kh kw x 16 positions] on v_mfma_f32_16x16x4_f32 (exact fp32, a
 //            k-ordered fma chain), k = (in-channel, kernel row, kernel column) in the weight tensor's own order, the accumulator
 //            initialised with the bias;
@@ -28,10 +28,9 @@ namespace mm {
 
 namespace {
 
-using pacrr_dev::kPB;
-using pacrr_dev::kTiny;
-using pacrr_dev::load4_or0;
-using pacrr_dev::mfma32;
+using pacrr_dev::cosine_block_finish;
+using pacrr_dev::cosine_block_partials;
+using pacrr_dev::query_rnorms;
 
 constexpr int kMpLmax = 8, kMpCmax = 32, kMpKmax = 5, kMpQmax = 64, kMpDmax = 2048, kMpEmax = 1024, kMpPHmax = 64,
               kMpPWmax = 256;
@@ -155,7 +154,7 @@ template <bool FAST>
 __global__ void __launch_bounds__(256) matchpyramid_kernel(MpArgs a) {
   extern __shared__ float lds[];
   const int Q = a.Q, D = a.D, E = a.E, L = a.L;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r32 = lane & 31, h = lane >> 5;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   float* rq = lds;
   float* rd = lds + 64;
   float* dn = lds + 96;
@@ -165,7 +164,7 @@ __global__ void __launch_bounds__(256) matchpyramid_kernel(MpArgs a) {
   float* wt = lds + kFixed + 4 * kScr + kKoff;
   float* arena = lds + kFixed + kUnion;
   float* slot = a.ws ? a.ws + (int64_t)blockIdx.x * a.slot_floats : nullptr;
-  const int nrt = (Q + 31) / 32, nch = (E + 7) / 8, nb = (D + 31) / 32;
+  const int nb = (D + 31) / 32;
 
   for (int64_t pair = blockIdx.x; pair < a.n_pairs; pair += gridDim.x) {
     const float* q = a.q + (pair / a.ppq) * (int64_t)Q * E;
@@ -181,70 +180,17 @@ __global__ void __launch_bounds__(256) matchpyramid_kernel(MpArgs a) {
       X0[r * Wp0 + D + i - r * (Wp0 - D)] = 0.0f;
     }
     for (int i = tid; i < (g0.Hp - Q) * Wp0; i += 256) X0[Q * Wp0 + i] = 0.0f;
-    for (int i = w; i < Q; i += 4) {
-      float s = 0.0f;
-      for (int e = lane; e < E; e += 64) s += q[(int64_t)i * E + e] * q[(int64_t)i * E + e];
-      s = wave_sum(s);
-      if (lane == 0) rq[i] = 1.0f / (sqrtf(s) + kTiny);
-    }
+    query_rnorms(q, Q, E, rq, w, lane);
     __syncthreads();
 
-    // ---- cosine, 32 document columns per step (pacrr.hip's block, written to plane 0 instead of its ring)
+    // ---- cosine, 32 document columns per step (the PACRR family's block, pacrr_device.h), written to plane 0
     for (int s = 0; s < nb; ++s) {
       const int j0 = 32 * s;
-      f32x16 acc[2];
-      acc[0] = f32x16{};
-      acc[1] = f32x16{};
-      float dsq = 0.0f;
-      const bool drow = j0 + r32 < D;
-      const float* dp = d + (int64_t)(j0 + r32) * E;
-      for (int m0 = w; m0 < nch; m0 += 4 * kPB) {
-        f32x4 dv[kPB], qv[2][kPB];
-#pragma unroll
-        for (int u = 0; u < kPB; ++u) {
-          const int k0 = 8 * (m0 + 4 * u) + 4 * h;
-          const bool kin = m0 + 4 * u < nch && k0 < E;
-          dv[u] = load4_or0(dp + k0, drow && kin);
-#pragma unroll
-          for (int rt = 0; rt < 2; ++rt) {
-            const int qi = rt * 32 + r32;
-            qv[rt][u] = load4_or0(q + (int64_t)qi * E + k0, rt < nrt && qi < Q && kin);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < kPB; ++u) {
-          dsq += dv[u][0] * dv[u][0] + dv[u][1] * dv[u][1] + dv[u][2] * dv[u][2] + dv[u][3] * dv[u][3];
-#pragma unroll
-          for (int rt = 0; rt < 2; ++rt) {
-            if (rt >= nrt) break;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) acc[rt] = mfma32(qv[rt][u][e], dv[u][e], acc[rt]);
-          }
-        }
-      }
-#pragma unroll
-      for (int rt = 0; rt < 2; ++rt) {
-        if (rt >= nrt) break;
-        float* pp = part + (w * nrt + rt) * 32 * 33;
-#pragma unroll
-        for (int e = 0; e < 16; ++e) pp[((e & 3) + 8 * (e >> 2) + 4 * h) * 33 + r32] = acc[rt][e];
-      }
-      dn[(w * 2 + h) * 32 + r32] = dsq;
+      cosine_block_partials(q, d, Q, D, E, j0, part, dn, w, lane);
       __syncthreads();
-      if (tid < 32) {
-        float t = 0.0f;
-        for (int u = 0; u < 8; ++u) t += dn[u * 32 + tid];
-        rd[tid] = 1.0f / (sqrtf(t) + kTiny);
-      }
-      __syncthreads();
-      for (int c = tid; c < Q * 32; c += 256) {
-        const int i = c >> 5, j = c & 31, rt = i >> 5, ii = i & 31;
-        float v = part[(0 * nrt + rt) * 32 * 33 + ii * 33 + j];
-        v += part[(1 * nrt + rt) * 32 * 33 + ii * 33 + j];
-        v += part[(2 * nrt + rt) * 32 * 33 + ii * 33 + j];
-        v += part[(3 * nrt + rt) * 32 * 33 + ii * 33 + j];
-        if (j0 + j < D) X0[i * Wp0 + j0 + j] = (v * rq[i]) * rd[j];
-      }
+      cosine_block_finish(Q, part, dn, rq, rd, tid, [&](int i, int j, float v) {
+        if (j0 + j < D) X0[i * Wp0 + j0 + j] = v;
+      });
       __syncthreads();
     }
 

@@ -197,4 +197,11 @@ __device__ __forceinline__ void wait_vm(int n) {
 
 __device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }
 
+constexpr float kTiny = 1e-13f;   // allennlp's cosine (mm_native.h, kernel pooling): x / (|x| + kTiny)
+
+// guarded 16-byte load: zeros where the row or the chunk does not exist
+__device__ __forceinline__ f32x4 load4_or0(const float* p, bool ok) {
+  return ok ? *(const f32x4*)p : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+}
+
 }  // namespace mm

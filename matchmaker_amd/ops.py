@@ -975,56 +975,48 @@ def _pacrr_shapes(q, d, pairs_per_query, k):
     return nq, Q, E, B, D
 
 
-def pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, pairs_per_query: int = 1, save: bool = False):
-    """PACRR's match matrix + n-gram convolutions + k-max pooling (matchmaker/models/pacrr.py:78-97) in ONE launch
-    (mm_pacrr_fwd): per_query_results [n_pairs, Q, k N], paths 0, 2, .., N.
-
-    q [n_queries, Q, E], d [n_pairs, D, E] float32; pair p scores against query p // pairs_per_query.
-    weights / biases: the Conv2d parameters of widths 2 .. N (convolutions.<n-2>.1.weight [C, 1, n, n] / .bias [C]), N - 1
-    of each (empty for N = 1).  save=True also returns the int32 indices [n_pairs, Q, k N] (column | channel << 16) that
-    pacrr_kmax_bwd takes; the values are the same bits either way."""
+def _pacrr_fwd_setup(what, q, d, weights, biases, k, pairs_per_query, check=None):
+    """What pacrr_kmax and co_pacrr_kmax share before their launch: device / dtype / shape validation (`check`: the
+    model's own, on the true E), the packed parameters, E padded to a multiple of 4.
+    Returns (dev, q, d, w_ptr, b_ptr, B, Q, D, E, C, N)."""
     dev = _dev_check(q, d)
     q, d = _emb(q, "q"), _emb(d, "d")
     if q.dtype != torch.float32 or d.dtype != torch.float32:
-        raise NativeError("pacrr_kmax: float32 embeddings only (the reference cosine rejects bf16)")
+        raise NativeError(f"{what}: float32 embeddings only (the reference cosine rejects bf16)")
     nq, Q, E, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    if check is not None:
+        check(B, Q, D, E)
     weights, biases = list(weights), list(biases)
     C = weights[0].shape[0] if weights else 1
     N = len(weights) + 1
     w, b = _pacrr_params(weights, biases, C, dev)
-    out = torch.empty((B, Q, k * N), dtype=torch.float32, device=dev)
-    idx = torch.empty((B, Q, k * N), dtype=torch.int32, device=dev) if save else None
     if B:
         q, d, E = _pad_rows(q, d, 4)
-        L = _lib.lib()
-        with _on(dev):
-            rc = L.mm_pacrr_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None,
-                                b.data_ptr() if b is not None else None, out.data_ptr(),
-                                idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
-                                None, 0, _stream(dev))
-        _lib.check(rc, "mm_pacrr_fwd")
-    return (out, idx) if save else out
+    return (dev, q, d, w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None, B, Q, D, E, C, N)
 
 
-def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor, grad_out: torch.Tensor, k: int,
-                   pairs_per_query: int = 1):
-    """Backward of pacrr_kmax (mm_pacrr_bwd): idx as returned by pacrr_kmax(..., save=True) on the same inputs, grad_out
-    [n_pairs, Q, k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w, grad_b) with grad_w /
-    grad_b lists shaped like `weights` / their biases ([C]), summed over the pairs in a fixed order (no atomics)."""
+def _pacrr_bwd(name, q, d, weights, idx, grad_out, k, pairs_per_query, idx_shape, go_shape, launch, check=None):
+    """The backward both models share around their launch.  idx_shape / go_shape: (B, Q, N) -> the shapes idx / grad_out
+    must have; launch(L, ptrs, dims, dev) runs the model's workspace query and mm_*_bwd and returns its code, ptrs =
+    (q, d, w, idx, go, gq, gd, gw, gb) and dims = (B, pairs_per_query, Q, D, E, C, N, k).  After it: E un-padded, the
+    per-pair grad_q rows summed per query in group order, grad_w / grad_b summed over the pairs and split per width."""
+    what = name + "_kmax_bwd"
     dev = _dev_check(q, d, idx, grad_out)
     q, d = _emb(q, "q"), _emb(d, "d")
     if q.dtype != torch.float32 or d.dtype != torch.float32:
-        raise NativeError("pacrr_kmax_bwd: float32 embeddings only")
+        raise NativeError(f"{what}: float32 embeddings only")
     nq, Q, E0, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
+    if check is not None:
+        check(B, Q, D, E0)
     weights = list(weights)
     C = weights[0].shape[0] if weights else 1
     N = len(weights) + 1
     w, _ = _pacrr_params(weights, [t.new_zeros(C) for t in weights], C, dev)
-    if tuple(idx.shape) != (B, Q, k * N) or idx.dtype != torch.int32:
-        raise NativeError(f"pacrr_kmax_bwd: idx must be int32 {(B, Q, k * N)}, got {idx.dtype} {tuple(idx.shape)}")
+    if tuple(idx.shape) != idx_shape(B, Q, N) or idx.dtype != torch.int32:
+        raise NativeError(f"{what}: idx must be int32 {idx_shape(B, Q, N)}, got {idx.dtype} {tuple(idx.shape)}")
     go = grad_out.detach().to(torch.float32).contiguous()
-    if tuple(go.shape) != (B, Q, k * N):
-        raise NativeError(f"pacrr_kmax_bwd: grad_out must be {(B, Q, k * N)}, got {tuple(go.shape)}")
+    if tuple(go.shape) != go_shape(B, Q, N):
+        raise NativeError(f"{what}: grad_out must be {go_shape(B, Q, N)}, got {tuple(go.shape)}")
     idx = idx.contiguous()
     q, d, E = _pad_rows(q, d, 4)
     S = sum(n * n for n in range(2, N + 1))
@@ -1033,15 +1025,11 @@ def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor,
     gw = torch.empty((B, C * S), dtype=torch.float32, device=dev)
     gb = torch.empty((B, C * (N - 1)), dtype=torch.float32, device=dev)
     if B:
-        L = _lib.lib()
+        ptrs = (q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(), go.data_ptr(),
+                gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None, gb.data_ptr() if N > 1 else None)
         with _on(dev):
-            wsb = L.mm_pacrr_workspace_bytes(B, Q, D, C, N, k)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-            rc = L.mm_pacrr_bwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(),
-                                go.data_ptr(), gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None,
-                                gb.data_ptr() if N > 1 else None, B, pairs_per_query, Q, D, E, C, N, k,
-                                ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-        _lib.check(rc, "mm_pacrr_bwd")
+            rc = launch(_lib.lib(), ptrs, (B, pairs_per_query, Q, D, E, C, N, k), dev)
+        _lib.check(rc, f"mm_{name}_bwd")
     if E != E0:
         gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
     if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
@@ -1057,6 +1045,41 @@ def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor,
         grad_b.append(gb[C * i:C * (i + 1)].clone())
         off += n * n
     return gq, gd, grad_w, grad_b
+
+
+def pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, pairs_per_query: int = 1, save: bool = False):
+    """PACRR's match matrix + n-gram convolutions + k-max pooling (matchmaker/models/pacrr.py:78-97) in ONE launch
+    (mm_pacrr_fwd): per_query_results [n_pairs, Q, k N], paths 0, 2, .., N.
+
+    q [n_queries, Q, E], d [n_pairs, D, E] float32; pair p scores against query p // pairs_per_query.
+    weights / biases: the Conv2d parameters of widths 2 .. N (convolutions.<n-2>.1.weight [C, 1, n, n] / .bias [C]), N - 1
+    of each (empty for N = 1).  save=True also returns the int32 indices [n_pairs, Q, k N] (column | channel << 16) that
+    pacrr_kmax_bwd takes; the values are the same bits either way."""
+    dev, q, d, w, b, B, Q, D, E, C, N = _pacrr_fwd_setup("pacrr_kmax", q, d, weights, biases, k, pairs_per_query)
+    out = torch.empty((B, Q, k * N), dtype=torch.float32, device=dev)
+    idx = torch.empty((B, Q, k * N), dtype=torch.int32, device=dev) if save else None
+    if B:
+        with _on(dev):
+            rc = _lib.lib().mm_pacrr_fwd(q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
+                                         idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
+                                         None, 0, _stream(dev))
+        _lib.check(rc, "mm_pacrr_fwd")
+    return (out, idx) if save else out
+
+
+def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor, grad_out: torch.Tensor, k: int,
+                   pairs_per_query: int = 1):
+    """Backward of pacrr_kmax (mm_pacrr_bwd): idx as returned by pacrr_kmax(..., save=True) on the same inputs, grad_out
+    [n_pairs, Q, k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w, grad_b) with grad_w /
+    grad_b lists shaped like `weights` / their biases ([C]), summed over the pairs in a fixed order (no atomics)."""
+    def launch(L, ptrs, dims, dev):
+        B, _, Q, D, _, C, N, _ = dims
+        wsb = L.mm_pacrr_workspace_bytes(B, Q, D, C, N, k)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+        return L.mm_pacrr_bwd(*ptrs, *dims, ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
+
+    shape = lambda B, Q, N: (B, Q, k * N)
+    return _pacrr_bwd("pacrr", q, d, weights, idx, grad_out, k, pairs_per_query, shape, shape, launch)
 
 
 def co_pacrr_views(unified_document_length: int):
@@ -1083,27 +1106,16 @@ def co_pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, vie
     q / d / weights / biases as pacrr_kmax; views: the four view sizes (co_pacrr_views(U)).  save=True also returns the
     int32 positions [n_pairs, Q, N, 4 k] (column | channel << 16) that co_pacrr_kmax_bwd takes; the values are the same
     bits either way."""
-    dev = _dev_check(q, d)
-    q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != torch.float32 or d.dtype != torch.float32:
-        raise NativeError("co_pacrr_kmax: float32 embeddings only (the reference cosine rejects bf16)")
-    nq, Q, E, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
     views = [int(v) for v in views]
-    _co_pacrr_check(B, Q, D, E, k, views)
-    weights, biases = list(weights), list(biases)
-    C = weights[0].shape[0] if weights else 1
-    N = len(weights) + 1
-    w, b = _pacrr_params(weights, biases, C, dev)
+    dev, q, d, w, b, B, Q, D, E, C, N = _pacrr_fwd_setup("co_pacrr_kmax", q, d, weights, biases, k, pairs_per_query,
+                                                         lambda B, Q, D, E: _co_pacrr_check(B, Q, D, E, k, views))
     out = torch.empty((B, Q, 8 * k * N), dtype=torch.float32, device=dev)
     idx = torch.empty((B, Q, N, 4 * k), dtype=torch.int32, device=dev) if save else None
     if B:
-        q, d, E = _pad_rows(q, d, 4)
-        L = _lib.lib()
         with _on(dev):
-            rc = L.mm_co_pacrr_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None,
-                                   b.data_ptr() if b is not None else None, out.data_ptr(),
-                                   idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
-                                   *views, None, 0, _stream(dev))
+            rc = _lib.lib().mm_co_pacrr_fwd(q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
+                                            idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N,
+                                            k, *views, None, 0, _stream(dev))
         _lib.check(rc, "mm_co_pacrr_fwd")
     return (out, idx) if save else out
 
@@ -1113,54 +1125,17 @@ def co_pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tens
     """Backward of co_pacrr_kmax (mm_co_pacrr_bwd, one launch): idx as returned by co_pacrr_kmax(..., save=True) on the same
     inputs, grad_out [n_pairs, Q, 8 k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w,
     grad_b) as pacrr_kmax_bwd."""
-    dev = _dev_check(q, d, idx, grad_out)
-    q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != torch.float32 or d.dtype != torch.float32:
-        raise NativeError("co_pacrr_kmax_bwd: float32 embeddings only")
-    nq, Q, E0, B, D = _pacrr_shapes(q, d, pairs_per_query, k)
     views = [int(v) for v in views]
-    _co_pacrr_check(B, Q, D, E0, k, views)
-    weights = list(weights)
-    C = weights[0].shape[0] if weights else 1
-    N = len(weights) + 1
-    w, _ = _pacrr_params(weights, [t.new_zeros(C) for t in weights], C, dev)
-    if tuple(idx.shape) != (B, Q, N, 4 * k) or idx.dtype != torch.int32:
-        raise NativeError(f"co_pacrr_kmax_bwd: idx must be int32 {(B, Q, N, 4 * k)}, got {idx.dtype} {tuple(idx.shape)}")
-    go = grad_out.detach().to(torch.float32).contiguous()
-    if tuple(go.shape) != (B, Q, 8 * k * N):
-        raise NativeError(f"co_pacrr_kmax_bwd: grad_out must be {(B, Q, 8 * k * N)}, got {tuple(go.shape)}")
-    idx = idx.contiguous()
-    q, d, E = _pad_rows(q, d, 4)
-    S = sum(n * n for n in range(2, N + 1))
-    gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
-    gd = torch.empty((B, D, E), dtype=torch.float32, device=dev)
-    gw = torch.empty((B, C * S), dtype=torch.float32, device=dev)
-    gb = torch.empty((B, C * (N - 1)), dtype=torch.float32, device=dev)
-    if B:
-        L = _lib.lib()
-        with _on(dev):
-            wsb = L.mm_co_pacrr_workspace_bytes(B, Q, D, E, C, N, k)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            rc = L.mm_co_pacrr_bwd(q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(),
-                                   go.data_ptr(), gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None,
-                                   gb.data_ptr() if N > 1 else None, B, pairs_per_query, Q, D, E, C, N, k, *views,
-                                   ws.data_ptr(), wsb, _stream(dev))
-        _lib.check(rc, "mm_co_pacrr_bwd")
-    if E != E0:
-        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
-    if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
-        pad = nq * pairs_per_query - B
-        if pad:
-            gq = torch.cat([gq, gq.new_zeros((pad, Q, E0))])
-        gq = gq.view(nq, pairs_per_query, Q, E0).sum(1)
-    gw, gb = gw.sum(0), gb.sum(0)
-    grad_w, grad_b, off = [], [], 0
-    for i, t in enumerate(weights):
-        n = i + 2
-        grad_w.append(gw[C * off:C * (off + n * n)].view(t.shape).clone())
-        grad_b.append(gb[C * i:C * (i + 1)].clone())
-        off += n * n
-    return gq, gd, grad_w, grad_b
+
+    def launch(L, ptrs, dims, dev):
+        B, _, Q, D, E, C, N, _ = dims
+        wsb = L.mm_co_pacrr_workspace_bytes(B, Q, D, E, C, N, k)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        return L.mm_co_pacrr_bwd(*ptrs, *dims, *views, ws.data_ptr(), wsb, _stream(dev))
+
+    return _pacrr_bwd("co_pacrr", q, d, weights, idx, grad_out, k, pairs_per_query,
+                      lambda B, Q, N: (B, Q, N, 4 * k), lambda B, Q, N: (B, Q, 8 * k * N), launch,
+                      lambda B, Q, D, E: _co_pacrr_check(B, Q, D, E, k, views))
 
 
 # ---------------------------------------------------------------------------------------------- DRMM

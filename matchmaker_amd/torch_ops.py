@@ -166,6 +166,19 @@ torch.library.register_autocast(_NS + "::tkl_window_pool", "cuda", torch.float32
 
 
 # ---------------------------------------------------------------------------------------------- PACRR
+def _pacrr_bwd_fake(q, d, weights):
+    """Fake outputs of pacrr_kmax_backward and co_pacrr_kmax_backward: float32 gradients shaped like q, d, the weights, [C]."""
+    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
+            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
+            [w.new_empty((w.shape[0],), dtype=torch.float32) for w in weights])
+
+
+def _pacrr_grads(q, d, weights, bshapes, gq, gd, gw, gb):
+    """The native float32 gradients in the dtypes and bias shapes of the inputs."""
+    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
+            [t.view(s) for t, s in zip(gb, bshapes)])
+
+
 @torch.library.custom_op(_NS + "::pacrr_kmax", mutates_args=(), device_types="cuda")
 def pacrr_kmax(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor], k: int,
                pairs_per_query: int) -> Tuple[Tensor, Tensor]:
@@ -191,9 +204,7 @@ def pacrr_kmax_backward(q: Tensor, d: Tensor, weights: List[Tensor], idx: Tensor
 
 @pacrr_kmax_backward.register_fake
 def _(q, d, weights, idx, grad_out, k, pairs_per_query=1):
-    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
-            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
-            [w.new_empty((w.shape[0],), dtype=torch.float32) for w in weights])
+    return _pacrr_bwd_fake(q, d, weights)
 
 
 def _pacrr_setup(ctx, inputs, output):
@@ -207,8 +218,7 @@ def _pacrr_backward(ctx, g, _gidx):
     q, d, idx, *weights = ctx.saved_tensors
     k, ppq, bshapes = ctx.meta
     gq, gd, gw, gb = torch.ops.mm_native.pacrr_kmax_backward(q, d, weights, idx, g.contiguous(), k, ppq)
-    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
-            [t.view(s) for t, s in zip(gb, bshapes)], None, None)
+    return _pacrr_grads(q, d, weights, bshapes, gq, gd, gw, gb) + (None, None)
 
 
 pacrr_kmax.register_autograd(_pacrr_backward, setup_context=_pacrr_setup)
@@ -242,9 +252,7 @@ def co_pacrr_kmax_backward(q: Tensor, d: Tensor, weights: List[Tensor], idx: Ten
 
 @co_pacrr_kmax_backward.register_fake
 def _(q, d, weights, idx, grad_out, k, views, pairs_per_query=1):
-    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
-            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
-            [w.new_empty((w.shape[0],), dtype=torch.float32) for w in weights])
+    return _pacrr_bwd_fake(q, d, weights)
 
 
 def _co_pacrr_setup(ctx, inputs, output):
@@ -258,8 +266,7 @@ def _co_pacrr_backward(ctx, g, _gidx):
     q, d, idx, *weights = ctx.saved_tensors
     k, views, ppq, bshapes = ctx.meta
     gq, gd, gw, gb = torch.ops.mm_native.co_pacrr_kmax_backward(q, d, weights, idx, g.contiguous(), k, views, ppq)
-    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
-            [t.view(s) for t, s in zip(gb, bshapes)], None, None, None)
+    return _pacrr_grads(q, d, weights, bshapes, gq, gd, gw, gb) + (None, None, None)
 
 
 co_pacrr_kmax.register_autograd(_co_pacrr_backward, setup_context=_co_pacrr_setup)
