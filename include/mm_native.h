@@ -471,6 +471,38 @@ int mm_kmeans_segment_sum(const void* x, const int64_t* order, const int64_t* li
                           int dtype, float* sums, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Graph search: beam search over a fixed-degree neighbour graph (dense retrieval,
+ * faiss_index_type: hnsw).
+ *
+ * Replaces: FaissHNSWIndexer.search (a CPU index)         matchmaker/retrieval/faiss_indices.py
+ *           The graph has ONE level and is built exactly from the shard's k-NN lists
+ *           (matchmaker_amd.retrieval.GraphIPIndexer); recall figures are this graph's, not HNSW's.
+ *
+ *   queries [nq, E], vectors [n, E]  float16 / bfloat16 of one dtype, E in {128, 256, ..., 768};
+ *   neighbors [n, M] int32 rows of `vectors`, -1 = no neighbour; entry_rows [nq, n_entry] int32.
+ *   Per query: the candidate list L starts as the entry rows (-1, rows outside [0, n) and duplicates
+ *   are ignored), scored; they form the visited set; L keeps the best ef entries, score descending,
+ *   lower row first on equal scores.  At most max_iters times: the `width` best entries of L that
+ *   have not been expanded are marked expanded (none left: stop); each of their neighbours that is
+ *   not -1 and not visited is marked visited and scored; the new pairs are merged into L, and L is
+ *   cut to ef.  out_scores / out_rows [nq, k] = the first k entries of L (fp32-accumulated inner
+ *   products of the 16-bit values; (-inf, -1) where L is shorter).  stats [nq, 2] int32 (may be
+ *   NULL) = (iterations run, rows scored).  The visited set is exact (full row numbers, no false
+ *   positives), so the result is a function of the inputs alone.
+ *   Envelope: 1 <= ef <= 2048, 1 <= k <= ef, 1 <= width <= 8, 1 <= n_entry <= ef, M even in
+ *   2 .. 128, 1 <= max_iters <= 65536, n < 2^31; anything else is MM_EUNSUPPORTED before any launch.
+ *   The visited table is open-addressed in LDS when 2 (n_entry + max_iters width M) <= 16384
+ *   slots; otherwise it is a slice of the workspace per workgroup (at most 1024 workgroups), which
+ *   the kernel clears itself.  workspace: mm_graph_search_workspace_bytes(...) (256 bytes for the LDS
+ *   placement).  One launch on `stream`, nothing read back or allocated: graph-capturable. */
+size_t mm_graph_search_workspace_bytes(int64_t n, int nq, int M, int ef, int width, int n_entry, int max_iters);
+
+int mm_graph_search_fwd(const void* queries, const void* vectors, const int32_t* neighbors, const int32_t* entry_rows,
+                        int64_t n, int nq, int E, int dtype, int M, int n_entry, int ef, int width, int max_iters, int k,
+                        float* out_scores, int64_t* out_rows, int32_t* stats /* [nq,2] or NULL */,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * PACRR: cosine match matrix -> n-gram convolutions + channel max -> per-row k-max pooling, fused.
  *
  *   cos[i,j]  = <q_i, d_j> / ((|q_i| + 1e-13)(|d_j| + 1e-13))            (allennlp cosine, pacrr.py:78)

@@ -62,6 +62,8 @@ SIGNATURES = {
     "mm_tkl_fwd_peaks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_ivf_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "mm_ivf_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mm_graph_search_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
+    "mm_graph_search_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mm_kmeans_assign": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "mm_kmeans_segment_sum_workspace_bytes": (_sz, [_i64, _i, _i]),
     "mm_kmeans_segment_sum": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),

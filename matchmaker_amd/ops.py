@@ -800,6 +800,55 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     return out_s, out_r
 
 
+def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.Tensor, entry_rows: torch.Tensor, ef: int, k: int,
+                 width: int = 4, max_iters: Optional[int] = None, return_stats: bool = False):
+    """Beam search over a fixed-degree neighbour graph (the search of a graph index, faiss_index_type: hnsw; native
+    mm_graph_search_fwd).
+
+    queries [nq, E], vectors [n, E] float16 / bfloat16 of one dtype (widths that are no multiple of 128 are zero-padded
+    here: a copy of both); neighbors [n, M] int32 rows of `vectors`, -1 = none, M even in 2 .. 128; entry_rows
+    [nq, n_entry] int32, -1 and duplicates ignored, 1 <= n_entry <= ef.  Per query the candidate list starts as the scored
+    entry rows and keeps the best ef (1 .. 2048); at most max_iters times (None: ceil(ef / width) + 8) the `width`
+    (1 .. 8) best entries not yet expanded are expanded: their unvisited neighbours are scored and merged.  Returns
+    (scores [nq, k] float32 descending, rows [nq, k] int64; lower row first on equal scores; -inf / -1 where fewer than k
+    rows were reached), and with return_stats also stats [nq, 2] int32 = (iterations run, rows scored).  One enqueue on
+    the current stream, no read-back: graph-capturable."""
+    dev = _dev_check(queries, vectors, neighbors, entry_rows)
+    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
+        raise NativeError(f"graph_search: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
+    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"graph_search: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
+    if neighbors.dim() != 2 or neighbors.dtype != torch.int32 or neighbors.shape[0] != vectors.shape[0]:
+        raise NativeError(f"graph_search: neighbors must be int32 [n, M], got {neighbors.dtype} {tuple(neighbors.shape)}")
+    if entry_rows.dim() != 2 or entry_rows.dtype != torch.int32 or entry_rows.shape[0] != queries.shape[0]:
+        raise NativeError(f"graph_search: entry_rows must be int32 [nq, n_entry], got {entry_rows.dtype} {tuple(entry_rows.shape)}")
+    nq, E = queries.shape
+    n, M, n_entry = vectors.shape[0], neighbors.shape[1], entry_rows.shape[1]
+    if max_iters is None:
+        max_iters = -(-int(ef) // max(1, int(width))) + 8
+    if E % 128:
+        queries, vectors, E = _pad_rows(queries, vectors, 128)
+    queries = queries if queries.is_contiguous() else queries.contiguous()
+    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
+    neighbors = neighbors if neighbors.is_contiguous() else neighbors.contiguous()
+    entry_rows = entry_rows if entry_rows.is_contiguous() else entry_rows.contiguous()
+    out_s = torch.empty((nq, max(int(k), 0)), dtype=torch.float32, device=dev)
+    out_r = torch.empty((nq, max(int(k), 0)), dtype=torch.int64, device=dev)
+    stats = torch.empty((nq, 2), dtype=torch.int32, device=dev) if return_stats else None
+    if nq == 0:
+        return (out_s, out_r, stats) if return_stats else (out_s, out_r)
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_graph_search_workspace_bytes, n, nq, M, int(ef), int(width), n_entry, int(max_iters))
+        ws = _workspace(dev, wsb)
+        rc = L.mm_graph_search_fwd(queries.data_ptr(), vectors.data_ptr(), neighbors.data_ptr(), entry_rows.data_ptr(), n, nq, E,
+                                   _DT[queries.dtype], M, n_entry, int(ef), int(width), int(max_iters), int(k),
+                                   out_s.data_ptr(), out_r.data_ptr(), stats.data_ptr() if return_stats else None,
+                                   ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
+    _lib.check(rc, "mm_graph_search_fwd")
+    return (out_s, out_r, stats) if return_stats else (out_s, out_r)
+
+
 _KMEANS_DIMS = (128, 256, 384, 512, 768)
 
 

@@ -17,6 +17,10 @@ DynamicIVFIndexer has the surface of `FaissDynamicIndexer` (faiss_indices.py:307
 clustering (matchmaker/distillation/query_clusterer.py:187-221): k-means over the query vectors, one probe, entries that
 can be replaced.  Its k-means (`spherical_kmeans`) runs on mm_kmeans_assign / mm_kmeans_segment_sum; IVFFlatIPIndexer
 takes the same path with `native_kmeans=True`.
+
+GraphIPIndexer (faiss_index_type: hnsw) has the surface of `FaissHNSWIndexer` (a CPU index in the reference): a one-level
+neighbour graph built exactly from the shard's k-NN lists (the top-k kernel over the shard itself), searched by
+mm_graph_search_fwd from entry rows that the top-k kernel picks out of a strided sample.
 """
 from typing import List, Optional
 
@@ -576,3 +580,232 @@ class DynamicIVFIndexer:
         s, rows = self._scan(qd, vectors, lb, cids.to(torch.int32)[:, None].contiguous(), top_n)
         out = torch.where(rows >= 0, ids[rows.clamp(min=0)], rows) if ids.numel() else rows
         return s.cpu().numpy(), out.cpu().numpy(), cids.to(torch.int64)[:, None].cpu().numpy()
+
+
+_GRAPH_MAGIC = "matchmaker_amd.GraphIPIndexer"
+_GRAPH_FORMAT = 1
+
+
+_KNN_EXACT_ROWS = 16          # query rows per sorted fallback of _knn_block
+
+
+def _knn_block(vectors: torch.Tensor, lo: int, hi: int, k: int, topk_fn) -> torch.Tensor:
+    """[hi - lo, k] int64: topk_fn(vectors[lo:hi], vectors, k)[1].  ops.dot_topk thresholds every query from a sample of the
+    shard and gives up on a query it cannot decide in its re-runs (met on a clustered 1.1 M x 768 shard searched against
+    itself: 6 rows of 1.1 M); it then raises for the whole call.  The block is halved until the undecided rows are isolated
+    in pieces of at most _KNN_EXACT_ROWS rows, and those are ranked in full: fp32 inner products of the stored 16-bit rows
+    with the whole shard, stable sort = score descending, lower row first — the same rule, without a threshold."""
+    try:
+        return topk_fn(vectors[lo:hi], vectors, k)[1]
+    except ops.NativeError:
+        if hi - lo > _KNN_EXACT_ROWS:
+            mid = (lo + hi) // 2
+            return torch.cat([_knn_block(vectors, lo, mid, k, topk_fn), _knn_block(vectors, mid, hi, k, topk_fn)])
+    N = vectors.shape[0]
+    q = vectors[lo:hi].float()
+    scores = torch.empty((hi - lo, N), dtype=torch.float32, device=vectors.device)
+    for a in range(0, N, 1 << 18):
+        scores[:, a: a + (1 << 18)] = q @ vectors[a: a + (1 << 18)].float().t()
+    idx = torch.sort(scores, dim=1, descending=True, stable=True).indices[:, :k]
+    if idx.shape[1] < k:
+        idx = torch.nn.functional.pad(idx, (0, k - idx.shape[1]), value=-1)
+    return idx
+
+
+def build_graph(vectors: torch.Tensor, M: int, topk_fn=None, block: int = 1 << 14) -> torch.Tensor:
+    """The neighbour graph of a shard: vectors [N, E_pad] float16 / bfloat16 -> neighbors [N, M] int32, -1 padded.
+
+    1. knn[v] = the M rows of highest inner product with row v without v itself, score descending, lower row first on
+       ties: topk_fn(k = M + 1) over the stored vectors in query blocks (rows the top-k operator cannot decide are ranked
+       in full, `_knn_block`); v is dropped from its own list when present, otherwise the last entry is; -1 padded when
+       N - 1 < M.
+    2. forward edges fwd[v] = knn[v][:M/2].
+    3. reverse edges: v receives u for every edge u -> v of fwd, ordered by (rank of v in fwd[u], u), skipping any u
+       already in the row, until the row holds M entries.
+    4. fill: knn[v][M/2:] in order, skipping entries already present, until the row holds M entries.
+    Steps 2-4 are sorted torch ops on the vectors' device: the three sources are laid out in priority order, one stable
+    sort by destination row gives every row its sequence, a second stable sort by (row, value) finds repeats."""
+    topk_fn = topk_fn if topk_fn is not None else ops.dot_topk
+    if M % 2 or not 2 <= M <= 128:
+        raise ops.NativeError(f"faiss_hnsw_graph_neighbors = {M} must be an even number in 2 .. 128")
+    N, dev = vectors.shape[0], vectors.device
+    if N >= 1 << 31:
+        raise ops.NativeError("build_graph: more than 2^31-1 vectors in one shard")
+    H = M // 2
+    knn = torch.empty((N, M), dtype=torch.int64, device=dev)
+    for lo in range(0, N, block):
+        idx = _knn_block(vectors, lo, min(N, lo + block), M + 1, topk_fn)
+        own = idx == torch.arange(lo, lo + idx.shape[0], device=dev)[:, None]
+        own[:, -1] |= ~own.any(dim=1)
+        knn[lo: lo + block] = idx[~own].view(-1, M)            # exactly one entry leaves every row, the order stays
+    rows = torch.arange(N, device=dev)
+    # (destination row, value) in priority order: forward edges by rank, reverse edges by (rank, source), fill by rank
+    dest = torch.cat([rows.repeat(H), knn[:, :H].t().reshape(-1), rows.repeat(M - H)])
+    val = torch.cat([knn[:, :H].t().reshape(-1), rows.repeat(H), knn[:, H:].t().reshape(-1)])
+    ok = (dest >= 0) & (val >= 0)
+    dest, val = dest[ok], val[ok]
+    order = torch.sort(dest, stable=True).indices
+    dest, val = dest[order], val[order]
+    by_pair = torch.sort(dest * N + val, stable=True)
+    first = torch.ones_like(dest, dtype=torch.bool)
+    first[1:] = by_pair.values[1:] != by_pair.values[:-1]
+    keep = torch.empty_like(first)
+    keep[by_pair.indices] = first                                # the first occurrence of a value in its row stays
+    dest, val = dest[keep], val[keep]
+    begin = torch.searchsorted(dest, rows)
+    rank = torch.arange(dest.shape[0], device=dev) - begin[dest]
+    fits = rank < M
+    out = torch.full((N, M), -1, dtype=torch.int32, device=dev)
+    out[dest[fits], rank[fits]] = val[fits].to(torch.int32)
+    return out
+
+
+class GraphIPIndexer:
+    """Drop-in for the reference's HNSW index (`FaissHNSWIndexer`, faiss_indices.py: IndexHNSWFlat with
+    `faiss_hnsw_graph_neighbors` links, `efSearch`, inner product; a CPU index there — "HNSW does not support GPUs"):
+    `prepare` has nothing to train, `index(ids, data_chunks)` stores this rank's shard and builds its neighbour graph
+    (`build_graph`), `search(query_vec, top_n)` picks `graph_entry_count` entry rows out of a strided sample of
+    `graph_entry_sample` rows with the top-k kernel and runs the beam search (ops.graph_search) with
+    ef = max(faiss_hnsw_efSearch, top_n), merged over the ranks.  `save` / `load` use a file format of their own.
+
+    Differences from the reference: ONE level, no hierarchy; the construction is exact (no incremental insertion), so
+    `faiss_hnsw_efConstruction` is accepted and ignored; vectors are float16 and queries are rounded to float16; equal
+    scores come lower row first.  Recall figures are this graph's, not HNSW's."""
+
+    def __init__(self, config, device=None, group=None, topk_fn=None, search_fn=None, merge_fn=None):
+        """topk_fn(queries, vectors, k) / search_fn(queries, vectors, neighbors, entry_rows, ef, k, width) /
+        merge_fn(scores, ids, k) default to ops.dot_topk / ops.graph_search / ops.topk_merge; the CPU test-suite injects
+        stand-ins."""
+        self._topk = topk_fn if topk_fn is not None else ops.dot_topk
+        self._search = search_fn if search_fn is not None else ops.graph_search
+        self._merge = merge_fn if merge_fn is not None else ops.topk_merge
+        self.token_dim = config["token_dim"]
+        self.use_fp16 = config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16")
+        if not self.use_fp16:
+            raise ops.NativeError("GraphIPIndexer stores float16 vectors and rounds queries to float16: set token_dtype: "
+                                  "float16, or keep faiss for an fp32 index")
+        self.M = int(config["faiss_hnsw_graph_neighbors"])
+        self.ef_search = int(config["faiss_hnsw_efSearch"])
+        self.ef_construction = config.get("faiss_hnsw_efConstruction")       # accepted, ignored: the construction is exact
+        self.entry_sample = int(config.get("graph_entry_sample", 4096))
+        self.entry_count = int(config.get("graph_entry_count", 32))
+        self.width = int(config.get("graph_search_width", 4))
+        if self.M % 2 or not 2 <= self.M <= 128:
+            raise ops.NativeError(f"faiss_hnsw_graph_neighbors = {self.M} must be an even number in 2 .. 128")
+        if self.ef_search < 1 or self.entry_sample < 1 or self.entry_count < 1 or not 1 <= self.width <= 8:
+            raise ops.NativeError("faiss_hnsw_efSearch, graph_entry_sample and graph_entry_count must be positive, "
+                                  "graph_search_width in 1 .. 8")
+        self.dtype = torch.float16
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
+        self.group = group
+        self.E_pad = _pad_dim(self.token_dim)
+        self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad]
+        self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids
+        self.neighbors: Optional[torch.Tensor] = None         # [n_local, M] int32, -1 padded
+        self.sample_rows: Optional[torch.Tensor] = None       # [S] int64 rows of the entry sample
+        self.sample_vectors: Optional[torch.Tensor] = None    # [S, E_pad] their vectors, contiguous
+
+    def _world(self):
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group), dist.get_rank(self.group)
+        return 1, 0
+
+    def prepare(self, data_chunks: List[np.ndarray] = None, subsample=-1):      # nothing to train
+        pass
+
+    def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
+        """This rank's contiguous shard of the vectors (every rank is given the same full lists) and its graph."""
+        i = np.concatenate(ids).astype(np.int64)
+        world, rank = self._world()
+        lo, hi = shard_range(i.shape[0], world, rank)
+        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
+        off = 0
+        for c in data_chunks:
+            a, b = max(lo, off), min(hi, off + c.shape[0])
+            if a < b:
+                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
+                    self.device).to(self.dtype)
+            off += c.shape[0]
+        self.index_resident(torch.from_numpy(i[lo:hi]).to(self.device), vec)
+
+    def _set_sample(self):
+        n = self.vectors.shape[0]
+        S = min(n, self.entry_sample)
+        self.sample_rows = (torch.arange(S, dtype=torch.int64, device=self.vectors.device) * n) // max(S, 1)
+        self.sample_vectors = self.vectors[self.sample_rows].contiguous()
+
+    def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64)."""
+        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
+            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        self.vectors, self.ids = vectors.contiguous(), ids.to(torch.int64).contiguous()
+        self.neighbors = build_graph(self.vectors, self.M, self._topk)
+        self._set_sample()
+
+    def search(self, query_vec, top_n: int):
+        """(scores [nq, top_n] float32 descending, ids [nq, top_n] int64; -inf / -1 where the search reached fewer rows)."""
+        s, ids = self.search_device(query_vec, top_n)
+        return s.cpu().numpy(), ids.cpu().numpy()
+
+    def entry_rows(self, qd: torch.Tensor, ef: int) -> torch.Tensor:
+        """[nq, min(graph_entry_count, ef, S)] int32: the rows of the sample with the highest inner product."""
+        S = self.sample_rows.shape[0]
+        i = self._topk(qd, self.sample_vectors, min(self.entry_count, ef, S))[1]
+        return torch.where(i >= 0, self.sample_rows[i.clamp(min=0)], i).to(torch.int32)
+
+    def search_device(self, query_vec, top_n: int, return_rows: bool = False):
+        if self.neighbors is None:
+            raise ops.NativeError("GraphIPIndexer.search: index() (or load()) first")
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
+        ef = max(self.ef_search, int(top_n))                      # as faiss: efSearch never below k
+        if self.vectors.shape[0] == 0:
+            s = torch.full((qd.shape[0], top_n), float("-inf"), dtype=torch.float32, device=qd.device)
+            rows = torch.full((qd.shape[0], top_n), -1, dtype=torch.int64, device=qd.device)
+        else:
+            s, rows = self._search(qd, self.vectors, self.neighbors, self.entry_rows(qd, ef), ef, top_n, self.width)
+        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0)], rows) if self.ids.numel() else rows
+        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        return (s, ids, rows) if return_rows else (s, ids)
+
+    def _rank_path(self, path: str) -> str:
+        world, rank = self._world()
+        return path if world == 1 else f"{path}.rank{rank}"
+
+    def save(self, path: str):
+        """One numpy .npz archive (this rank's shard; `path + ".rank<r>"` with several ranks)."""
+        with open(self._rank_path(path), "wb") as f:
+            np.savez(f, magic=np.array(_GRAPH_MAGIC), format=np.array(_GRAPH_FORMAT), token_dim=np.array(self.token_dim),
+                     M=np.array(self.M), vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy(),
+                     neighbors=self.neighbors.cpu().numpy(), sample_rows=self.sample_rows.cpu().numpy())
+
+    def load(self, path: str, config_overwrites=None):
+        """The file decides what was built (vectors, ids, graph, M, entry sample); the config decides how it is searched
+        (efSearch, graph_entry_count, graph_search_width), and config_overwrites["faiss_hnsw_efSearch"] overrides efSearch."""
+        p = self._rank_path(path)
+        with open(p, "rb") as f:
+            head = f.read(4)
+        if head[:2] != b"PK":
+            raise ops.NativeError(f"{p} is not a GraphIPIndexer file (an index written by faiss cannot be read: build the "
+                                  "index again with index())")
+        z = np.load(p, allow_pickle=False)
+        if "magic" not in z.files or str(z["magic"]) != _GRAPH_MAGIC or int(z["format"]) != _GRAPH_FORMAT:
+            raise ops.NativeError(f"{p} is not a GraphIPIndexer file of format {_GRAPH_FORMAT}")
+        if int(z["token_dim"]) != self.token_dim or z["vectors"].shape[1] != self.E_pad:
+            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        n, M = z["vectors"].shape[0], int(z["M"])
+        nb, sr = z["neighbors"], z["sample_rows"]
+        if (z["ids"].shape != (n,) or nb.shape != (n, M) or nb.dtype != np.int32 or z["vectors"].dtype != np.float16 or M % 2
+                or not 2 <= M <= 128 or sr.ndim != 1 or (n > 0 and (sr.size == 0 or sr.min() < 0 or sr.max() >= n))
+                or (nb.size and (nb.min() < -1 or nb.max() >= n))):
+            raise ops.NativeError(f"{p} is damaged: vectors {z['vectors'].shape} {z['vectors'].dtype}, ids {z['ids'].shape}, "
+                                  f"neighbors {nb.shape} {nb.dtype} for M = {M}, sample rows outside the shard or none")
+        self.vectors = torch.from_numpy(z["vectors"]).to(self.device)
+        self.ids = torch.from_numpy(z["ids"].astype(np.int64)).to(self.device)
+        self.neighbors = torch.from_numpy(nb).to(self.device)
+        self.sample_rows = torch.from_numpy(sr.astype(np.int64)).to(self.device)
+        self.sample_vectors = self.vectors[self.sample_rows].contiguous()
+        # the graph and its sample are what the file holds: M and the sample size come from the file; the search knobs
+        # (efSearch, entry count, width) stay the config's
+        self.M, self.entry_sample = M, int(sr.size)
+        if config_overwrites is not None and "faiss_hnsw_efSearch" in config_overwrites:
+            self.ef_search = int(config_overwrites["faiss_hnsw_efSearch"])

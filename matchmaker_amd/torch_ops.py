@@ -368,3 +368,20 @@ def _(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap=None):
     C = min(H, begin_sorted.shape[0]) if c_cap is None else c_cap
     return (hit_rows.new_empty((nq, C), dtype=torch.int32), hit_rows.new_empty((nq, C), dtype=torch.int64),
             hit_rows.new_empty((nq, C), dtype=torch.int64), hit_rows.new_empty((nq,), dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- graph index
+@torch.library.custom_op(_NS + "::graph_search", mutates_args=(), device_types="cuda")
+def graph_search(queries: Tensor, vectors: Tensor, neighbors: Tensor, entry_rows: Tensor, ef: int, k: int, width: int = 4,
+                 max_iters: Optional[int] = None) -> Tuple[Tensor, Tensor, Tensor]:
+    """(scores [nq, k] float32, rows [nq, k] int64, stats [nq, 2] int32 = (iterations run, rows scored)): the beam search of
+    the graph index (ops.graph_search).  A search, not a differentiable function: no autograd formula."""
+    s, r, st = ops.graph_search(queries, vectors, neighbors, entry_rows, ef, k, width, max_iters, return_stats=True)
+    return s, r, st
+
+
+@graph_search.register_fake
+def _(queries, vectors, neighbors, entry_rows, ef, k, width=4, max_iters=None):
+    nq = queries.shape[0]
+    return (queries.new_empty((nq, k), dtype=torch.float32), queries.new_empty((nq, k), dtype=torch.int64),
+            queries.new_empty((nq, 2), dtype=torch.int32))
