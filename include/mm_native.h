@@ -471,6 +471,67 @@ int mm_kmeans_segment_sum(const void* x, const int64_t* order, const int64_t* li
                           int dtype, float* sums, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Quantized index: anisotropic 4-bit encoder, scan of the codes, exact re-score (dense retrieval,
+ * faiss_index_type: scann).
+ *
+ * Replaces: ScaNNIndexer.index / .search                   matchmaker/retrieval/scann_index.py:24-47
+ *           (scann builder .tree(...).score_ah(2, anisotropic_quantization_threshold=0.2)
+ *           .reorder(top_n): leaves, 4-bit codes of 2-dimensional blocks, exact re-score).  ScaNN is a
+ *           third-party CPU library that is not part of the reference tree: what follows is this
+ *           library's restatement, not ScaNN's code path; INTEGRATION.md lists the differences.
+ *
+ * Common: E in {128, 256, 384, 512, 768}, dtype float16 / bfloat16; S = E / 2 blocks of 2 dimensions;
+ *   codebook [S, 16, 2] of the vectors' dtype; codes [n, E / 4] uint8, byte i of a row = the code of
+ *   block 2 i in the LOW nibble and of block 2 i + 1 in the high nibble.
+ *   decode(codes[i]) = the concatenation of codebook[s][code_s], s = 0 .. S - 1.
+ *
+ * mm_ah_encode                                              scann_index.py:32-35 (score_ah)
+ *   x [n, E], list [n] int32 (the row's leaf; outside [0, nlist): a zero centre), centroids [nlist, E].
+ *   Per row, every step ONE rounded fp32 operation, in this order (16-bit values widen exactly):
+ *     r_s = x_s - centroids[list]_s per element.
+ *     |x|^2: sixteen partial sums, partial c = blocks c, c + 16, ... ascending, per block + x0 x0 then
+ *       + x1 x1; the partials are combined by the butterfly t_c += t_(c ^ 8), then ^ 4, ^ 2, ^ 1.
+ *       inv = 1 / sqrt(|x|^2), xhat = x inv per element; an all-zero row: xhat = 0 and eta = 1.
+ *     per block s and codeword k:  e = (r_s - codebook[s][k]) per element,
+ *       n_k = e0 e0 + e1 e1,  t_k = e0 xhat0 + e1 xhat1.
+ *     start: blocks ascending, code_s = the k of least n_k (lowest k on equal n_k); p = p + t_code_s,
+ *       from p = 0.
+ *     then `passes` sweeps, blocks ascending: po = p - t_code_s; u_k = po + t_k;
+ *       cost_k = n_k + (eta - 1) (u_k u_k)  (u_k u_k first, then x (eta - 1), then + n_k);
+ *       code_s = the k of least cost_k (lowest k on equal cost); p = po + t_code_s.
+ *   This is coordinate descent on L = sum_s |e_s|^2 + (eta - 1) (sum_s <e_s, xhat_s>)^2 with the other
+ *   blocks' parallel error held fixed; eta = 1 or passes = 0 is plain nearest-codeword quantisation.
+ *   eta finite and >= 0, 0 <= passes <= 64.  The result is a pure function of the inputs: no atomics,
+ *   one launch on `stream`, no workspace: graph-capturable.  n = 0 succeeds without a launch.
+ *
+ * mm_ah_scan_fwd                                            scann_index.py:44 (search_batched, AH stage)
+ *   queries [nq, E]; codes stored list by list as the vectors of mm_ivf_scan_fwd are (list_begin
+ *   [nlist + 1] int64); probes [nq, nprobe] int32, -1 = no list; probe_scores [nq, nprobe] float32.
+ *   score(q, i) = probe_scores[q, j] + <queries[q], decode(codes[i])> for row i of the list probes[q, j]
+ *   (products of 16-bit values accumulated in fp32, the probe score added last).
+ *   out_scores / out_rows [nq, k]: the EXACT top-k of those scores over the probed union, descending,
+ *   lower row first on equal scores, (-inf, -1) padded.  Limits, workspace formula and launch
+ *   behaviour are mm_ivf_scan_fwd's (k <= 4096, nprobe <= 4096; no read-back, no allocation:
+ *   graph-capturable); queries and codes 16-byte aligned.
+ *
+ * mm_gather_dot                                             scann_index.py:35 (reorder)
+ *   queries [nq, E], vectors [n_vectors, E], rows [nq, R] int64.  out [nq, R] float32 =
+ *   <queries[q], vectors[rows[q, j]]>, products of 16-bit values accumulated in fp32; -inf where the
+ *   row is -1 (or outside [0, n_vectors)).  One launch on `stream`: graph-capturable. */
+int mm_ah_encode(const void* x, const int32_t* list, const void* centroids, const void* codebook, int64_t n, int nlist,
+                 int E, int dtype, float eta, int passes, uint8_t* codes, void* stream);
+
+size_t mm_ah_scan_workspace_bytes(int64_t n_vectors, int nlist, int nq, int nprobe, int k);
+
+int mm_ah_scan_fwd(const void* queries, const uint8_t* codes, const void* codebook, const int64_t* list_begin,
+                   const int32_t* probes, const float* probe_scores, int64_t n_vectors, int nlist, int nq, int nprobe,
+                   int E, int dtype, int k, float* out_scores, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                   void* stream);
+
+int mm_gather_dot(const void* queries, const void* vectors, const int64_t* rows, int64_t n_vectors, int nq, int R, int E,
+                  int dtype, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Graph search: beam search over a fixed-degree neighbour graph (dense retrieval,
  * faiss_index_type: hnsw).
  *

@@ -62,6 +62,10 @@ SIGNATURES = {
     "mm_tkl_fwd_peaks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_ivf_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "mm_ivf_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mm_ah_encode": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _c.c_float, _i, _vp, _vp]),
+    "mm_ah_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "mm_ah_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mm_gather_dot": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "mm_graph_search_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
     "mm_graph_search_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mm_kmeans_assign": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),

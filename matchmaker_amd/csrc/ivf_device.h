@@ -1,0 +1,392 @@
+// Shared scaffolding of the list-major scans (ivf_scan.hip: 16-bit rows; ah_scan.hip: 4-bit codes): the ragged candidate
+// rows, the 32-row task table, the rounds, the counting sort of the (query, list) pairs by list and the exact radix
+// selection.  A scan supplies its own score kernel (one wavefront per 32-row block of a list, which writes every
+// candidate score of the round) and runs through ivf_run.  Kernels have internal linkage: every translation unit that
+// includes this header gets its own copy of the small ones.
+#pragma once
+#include "mm_internal.h"
+
+namespace mm {
+namespace ivf_dev {
+
+constexpr int kIvfMaxK = 4096;
+constexpr int kIvfMaxProbe = 4096;
+constexpr int64_t kIvfCapFloor = 1LL << 28;   // floats
+
+struct IvfGeom {
+  int64_t cap;      // floats in the candidate buffer
+  int64_t S;        // round width in candidates (a round holds the queries whose prefix falls into [r S, (r + 1) S))
+  int rounds;
+  int64_t max_tasks;  // bound on the 32-row blocks over all lists
+};
+
+inline IvfGeom ivf_geom(int64_t n, int nlist, int nq) {
+  IvfGeom g;
+  const int64_t worst = (int64_t)nq * n;
+  const int64_t cap_max = kIvfCapFloor > 2 * n ? kIvfCapFloor : 2 * n;
+  if (worst <= cap_max) {
+    g.cap = worst > 0 ? worst : 1;
+    g.S = g.cap + 1;
+    g.rounds = 1;
+  } else {
+    g.cap = cap_max;
+    g.S = cap_max - n + 1;
+    g.rounds = (int)((worst + g.S - 1) / g.S);
+  }
+  g.max_tasks = n / 32 + nlist + 1;
+  return g;
+}
+
+inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct IvfArgs {
+  const void* q;            // [nq, E]
+  const void* v;            // [n, E] rows (ivf_scan) / [n, E / 4] codes (ah_scan)
+  const int64_t* lb;        // [nlist + 1]
+  const int32_t* probes;    // [nq, nprobe]
+  const void* codebook;     // ah_scan: [E / 2, 16, 2], the dtype of q
+  const float* probe_scores;  // ah_scan: [nq, nprobe] added to every score of the pair's list
+  int64_t n;
+  int nlist, nq, nprobe, k;
+  int64_t S;
+  // once per call
+  int32_t* seg_off;         // [nq, nprobe] offset of the pair's list inside the query's ragged row
+  int32_t* total;           // [nq] candidates of the query
+  int64_t* prefix;          // [nq + 1] exclusive prefix of `total`: a row starts at prefix[q] - prefix[first query of its round]
+  int32_t* qbeg;            // [rounds + 1] first query of every round
+  int32_t* tstart;          // [nlist + 1] first task (32-row block) of every list
+  int32_t* blk_list;        // [max_tasks] list of every task
+  // per round
+  int32_t* cnt;             // [nlist] pairs of the round per list     } zeroed together before every round
+  int32_t* fill;            // [nlist] fill level of the counting sort }
+  int32_t* start;           // [nlist + 1]
+  int32_t* pairs;           // [nq * nprobe] pair ids (q * nprobe + j) grouped by list
+  float* cand;              // [cap]
+  float* out_s;             // [nq, k]
+  int64_t* out_r;           // [nq, k]
+};
+
+__device__ __forceinline__ void ivf_list_range(const IvfArgs& a, int l, int64_t* b, int64_t* len) {
+  int64_t lo = a.lb[l], hi = a.lb[l + 1];
+  lo = lo < 0 ? 0 : (lo > a.n ? a.n : lo);
+  hi = hi < lo ? lo : (hi > a.n ? a.n : hi);
+  *b = lo;
+  *len = hi - lo;
+}
+
+__device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int64_t t = __shfl_up((long long)v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// one wavefront per query
+static __global__ void __launch_bounds__(256) ivf_rows_kernel(const IvfArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= a.nq) return;
+  int64_t carry = 0;
+  for (int j0 = 0; j0 < a.nprobe; j0 += 64) {
+    const int j = j0 + lane;
+    int len = 0;
+    if (j < a.nprobe) {
+      const int l = a.probes[(int64_t)q * a.nprobe + j];
+      if (l >= 0 && l < a.nlist) {
+        int64_t b, ln;
+        ivf_list_range(a, l, &b, &ln);
+        len = (int)ln;
+      }
+    }
+    // a row never holds more than n_vectors candidates: lists named twice (an error) are dropped, not written past the buffer
+    int64_t incl = wave_incl_scan(len, lane);
+    if (carry + incl > a.n) len = 0;
+    incl = wave_incl_scan(len, lane);
+    if (j < a.nprobe) a.seg_off[(int64_t)q * a.nprobe + j] = (int32_t)(carry + incl - len);
+    carry += __shfl((long long)incl, 63, 64);
+  }
+  if (lane == 0) a.total[q] = (int32_t)carry;
+}
+
+// exclusive scan of f(i), i < n, by ONE workgroup of 1024 threads; out[n] = the total
+template <typename T, typename F, typename O>
+__device__ void block_excl_scan(F f, O out, int n, T* sh /* [1024] */) {
+  const int tid = threadIdx.x;
+  T carry = 0;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + tid;
+    const T v = i < n ? f(i) : (T)0;
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+      const T t = tid >= o ? sh[tid - o] : (T)0;
+      __syncthreads();
+      sh[tid] += t;
+      __syncthreads();
+    }
+    if (i < n) out(i, carry + sh[tid] - v);
+    const T tot = sh[1023];
+    __syncthreads();
+    carry += tot;
+  }
+  if (tid == 0) out(n, carry);
+}
+
+static __global__ void __launch_bounds__(1024) ivf_tasks_kernel(const IvfArgs a) {
+  __shared__ int sh[1024];
+  block_excl_scan<int>(
+      [&](int l) {
+        int64_t b, len;
+        ivf_list_range(a, l, &b, &len);
+        return (int)((len + 31) >> 5);
+      },
+      [&](int l, int v) { a.tstart[l] = v; }, a.nlist, sh);
+  __syncthreads();
+  __threadfence_block();
+  for (int l = threadIdx.x; l < a.nlist; l += 1024) {
+    const int t0 = a.tstart[l], t1 = a.tstart[l + 1];
+    for (int t = t0; t < t1; ++t) a.blk_list[t] = l;
+  }
+}
+
+static __global__ void __launch_bounds__(1024) ivf_chunks_kernel(const IvfArgs a, int rounds) {
+  __shared__ int64_t sh[1024];
+  for (int r = threadIdx.x; r <= rounds; r += 1024) a.qbeg[r] = r == 0 ? 0 : a.nq;
+  block_excl_scan<int64_t>([&](int q) { return (int64_t)a.total[q]; }, [&](int q, int64_t v) { a.prefix[q] = v; }, a.nq, sh);
+  __syncthreads();
+  __threadfence_block();
+  // a row holds at most n_vectors < S candidates: the round number grows by at most one from a query to the next
+  for (int q = threadIdx.x + 1; q < a.nq; q += 1024) {
+    const int64_t r0 = a.prefix[q - 1] / a.S, r1 = a.prefix[q] / a.S;
+    if (r1 != r0 && r1 < rounds) a.qbeg[r1] = q;
+  }
+}
+
+// counting sort of the round's probe pairs by list: FILL = false counts, FILL = true places
+template <bool FILL>
+static __global__ void __launch_bounds__(256) ivf_group_kernel(const IvfArgs a, int round) {
+  const int qa = a.qbeg[round], qb = a.qbeg[round + 1];
+  const int64_t p1 = (int64_t)qb * a.nprobe;
+  for (int64_t p = (int64_t)qa * a.nprobe + (int64_t)blockIdx.x * 256 + threadIdx.x; p < p1; p += (int64_t)gridDim.x * 256) {
+    const int q = (int)(p / a.nprobe), j = (int)(p - (int64_t)q * a.nprobe);
+    const int l = a.probes[p];
+    if (l < 0 || l >= a.nlist) continue;
+    const int end = j + 1 < a.nprobe ? a.seg_off[p + 1] : a.total[q];
+    if (end == a.seg_off[p]) continue;   // empty (or dropped) list
+    if (FILL) a.pairs[a.start[l] + atomicAdd(a.fill + l, 1)] = (int32_t)p;
+    else atomicAdd(a.cnt + l, 1);
+  }
+}
+
+static __global__ void __launch_bounds__(1024) ivf_lscan_kernel(const IvfArgs a, int round) {
+  __shared__ int sh[1024];
+  if (a.qbeg[round] >= a.qbeg[round + 1]) return;
+  block_excl_scan<int>([&](int l) { return a.cnt[l]; }, [&](int l, int v) { a.start[l] = v; }, a.nlist, sh);
+}
+
+template <int DT>
+struct IvfMfma;
+template <>
+struct IvfMfma<MM_BF16> {
+  static __device__ __forceinline__ f32x16 run(short8 x, short8 y, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
+  }
+};
+template <>
+struct IvfMfma<MM_F16> {
+  static __device__ __forceinline__ f32x16 run(short8 x, short8 y, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
+  }
+};
+
+// order-preserving key of a score, ASCENDING key = DESCENDING score (-0 counts as +0)
+__device__ __forceinline__ uint32_t ivf_key(float s) {
+  const uint32_t u = __float_as_uint(s + 0.0f);
+  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
+}
+__device__ __forceinline__ float ivf_unkey(uint32_t k) {
+  const uint32_t m = ~k;
+  return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
+}
+
+// The `want`-th smallest key (want >= 1) among the elements i < n with ok(i), by ONE workgroup: 4 passes of 8 bits.
+// Returns the key; *below = elements with a smaller key, *ties = elements with that key.
+template <typename OK, typename KEY>
+__device__ uint32_t ivf_radix_kth(int n, int want, OK ok, KEY key, int* hist /* [256] */, int* sh /* [4] */, int* below, int* ties) {
+  const int tid = threadIdx.x, nt = blockDim.x;
+  uint32_t prefix = 0, mask = 0;
+  int remaining = want, less = 0, eq = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    for (int i = tid; i < 256; i += nt) hist[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += nt) {
+      if (!ok(i)) continue;
+      const uint32_t kx = key(i);
+      if ((kx & mask) == prefix) atomicAdd(hist + ((kx >> shift) & 255u), 1);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      int cum = 0, b = 0;
+      for (; b < 255; ++b) {
+        if (cum + hist[b] >= remaining) break;
+        cum += hist[b];
+      }
+      sh[0] = b; sh[1] = cum; sh[2] = hist[b];
+    }
+    __syncthreads();
+    const int b = sh[0];
+    remaining -= sh[1];
+    less += sh[1];
+    eq = sh[2];
+    prefix |= (uint32_t)b << shift;
+    mask |= 255u << shift;
+    __syncthreads();
+  }
+  *below = less;
+  *ties = eq;
+  return prefix;
+}
+
+static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a, int round, int k2) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* sel = (unsigned long long*)smem;    // [k2] (key << 32 | row), ascending = the output order
+  int* hist = (int*)(sel + k2);                            // [256]
+  int* sh = hist + 256;                                    // [4]
+  int* nsel = sh + 4;                                      // [1]
+  const int tid = threadIdx.x;
+  const int qa = a.qbeg[round];
+  const int q = qa + blockIdx.x;
+  if (q >= a.qbeg[round + 1]) return;
+  const int C = a.total[q], k = a.k;
+  const float* row = a.cand + (a.prefix[q] - a.prefix[qa]);
+  const int32_t* so = a.seg_off + (int64_t)q * a.nprobe;
+  const int32_t* pr = a.probes + (int64_t)q * a.nprobe;
+  // position in the ragged row -> row of `vectors`: the last probe whose offset is <= pos has the position in its list
+  auto vrow = [&](int pos) -> uint32_t {
+    int lo = 0, hi = a.nprobe;   // first j with so[j] > pos
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (so[mid] <= pos) lo = mid + 1; else hi = mid;
+    }
+    const int j = lo - 1;
+    int64_t b, len;
+    ivf_list_range(a, pr[j], &b, &len);
+    return (uint32_t)(b + (pos - so[j]));
+  };
+  for (int i = tid; i < k2; i += 1024) sel[i] = ~0ull;
+  if (tid == 0) *nsel = 0;
+  __syncthreads();
+  const int kk = C < k ? C : k;
+  if (C <= k) {
+    for (int i = tid; i < C; i += 1024) sel[i] = ((unsigned long long)ivf_key(row[i]) << 32) | vrow(i);
+  } else {
+    int below, ties;
+    const uint32_t T = ivf_radix_kth(C, k, [&](int) { return true; }, [&](int i) { return ivf_key(row[i]); }, hist, sh, &below, &ties);
+    uint32_t Trow = 0xffffffffu;
+    if (below + ties > k) {   // more candidates tie with the k-th score than fit: the lower rows win
+      int b2, t2;
+      Trow = ivf_radix_kth(C, k - below, [&](int i) { return ivf_key(row[i]) == T; }, vrow, hist, sh, &b2, &t2);
+    }
+    for (int i = tid; i < C; i += 1024) {
+      const uint32_t kx = ivf_key(row[i]);
+      if (kx > T) continue;
+      const uint32_t vr = vrow(i);
+      if (kx == T && vr > Trow) continue;
+      const int slot = atomicAdd(nsel, 1);
+      if (slot < k) sel[slot] = ((unsigned long long)kx << 32) | vr;   // (slot >= k: only with a list probed twice)
+    }
+  }
+  __syncthreads();
+  // bitonic sort, ascending
+  for (int size = 2; size <= k2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < k2; i += 1024) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const unsigned long long x = sel[i], y = sel[j];
+          const bool up = (i & size) == 0;
+          if ((x > y) == up) { sel[i] = y; sel[j] = x; }
+        }
+      }
+      __syncthreads();
+    }
+  for (int i = tid; i < k; i += 1024) {
+    const unsigned long long e = sel[i];
+    const bool okv = i < kk && e != ~0ull;
+    a.out_s[(int64_t)q * k + i] = okv ? ivf_unkey((uint32_t)(e >> 32)) : neg_inf();
+    a.out_r[(int64_t)q * k + i] = okv ? (int64_t)(uint32_t)e : -1;
+  }
+}
+
+inline int pow2_ge_i(int v) {
+  int p = 1;
+  while (p < v) p <<= 1;
+  return p;
+}
+
+inline size_t ivf_workspace_bytes(int64_t n_vectors, int nlist, int nq, int nprobe) {
+  if (n_vectors < 0 || nlist <= 0 || nq <= 0 || nprobe <= 0) return 0;
+  const IvfGeom g = ivf_geom(n_vectors, nlist, nq);
+  const size_t pairs = (size_t)nq * nprobe;
+  return a256(pairs * 4) * 2 + a256((size_t)nq * 4) + a256(((size_t)nq + 1) * 8) + a256(((size_t)g.rounds + 1) * 4) +
+         a256(((size_t)nlist + 1) * 4) * 2 + a256((size_t)g.max_tasks * 4) + a256((size_t)nlist * 8) + a256((size_t)g.cap * 4);
+}
+
+// The checks both scans share (`what` names the caller), before any launch.
+inline int ivf_check(const char* what, int64_t n_vectors, int nlist, int nq, int nprobe, int E, int dtype, int k) {
+  if (n_vectors < 0 || nlist <= 0 || nq <= 0 || nprobe <= 0 || k <= 0) return set_error(MM_EINVAL, "%s: non-positive shape", what);
+  if (dtype != MM_F16 && dtype != MM_BF16) return set_error(MM_EUNSUPPORTED, "%s: float16 / bfloat16 vectors only", what);
+  if (k > kIvfMaxK || nprobe > kIvfMaxProbe)
+    return set_error(MM_EUNSUPPORTED, "%s: k=%d / nprobe=%d exceed %d / %d", what, k, nprobe, kIvfMaxK, kIvfMaxProbe);
+  if (n_vectors >= (1LL << 31) || (int64_t)nq * nprobe >= (1LL << 31))
+    return set_error(MM_EUNSUPPORTED, "%s: more than 2^31-1 vectors or (query, probe) pairs in one call", what);
+  if (E != 128 && E != 256 && E != 384 && E != 512 && E != 768)
+    return set_error(MM_EUNSUPPORTED, "%s: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", what, E);
+  return MM_OK;
+}
+
+// Carves the workspace, enqueues the preparation and every round.  `a` arrives with the inputs, the shape and the outputs
+// set; score(a, round, g) enqueues the caller's score kernel for one round and returns MM_OK or an error.
+template <typename Score>
+int ivf_run(IvfArgs a, void* workspace, hipStream_t stream, const char* what, Score score) {
+  const IvfGeom g = ivf_geom(a.n, a.nlist, a.nq);
+  const size_t pairs = (size_t)a.nq * a.nprobe;
+  const int nlist = a.nlist, nq = a.nq, k = a.k;
+  a.S = g.S;
+  char* ws = (char*)workspace;
+  a.seg_off = (int32_t*)ws;  ws += a256(pairs * 4);
+  a.pairs = (int32_t*)ws;    ws += a256(pairs * 4);
+  a.total = (int32_t*)ws;    ws += a256((size_t)nq * 4);
+  a.prefix = (int64_t*)ws;   ws += a256(((size_t)nq + 1) * 8);
+  a.qbeg = (int32_t*)ws;     ws += a256(((size_t)g.rounds + 1) * 4);
+  a.tstart = (int32_t*)ws;   ws += a256(((size_t)nlist + 1) * 4);
+  a.start = (int32_t*)ws;    ws += a256(((size_t)nlist + 1) * 4);
+  a.blk_list = (int32_t*)ws; ws += a256((size_t)g.max_tasks * 4);
+  a.cnt = (int32_t*)ws;      a.fill = a.cnt + nlist;  ws += a256((size_t)nlist * 8);
+  a.cand = (float*)ws;
+
+  hipLaunchKernelGGL(ivf_rows_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(ivf_tasks_kernel, dim3(1), dim3(1024), 0, stream, a);
+  hipLaunchKernelGGL(ivf_chunks_kernel, dim3(1), dim3(1024), 0, stream, a, g.rounds);
+  if (int e = check_launch(what)) return e;
+
+  const int k2 = pow2_ge_i(k);
+  const size_t lds_sel = (size_t)k2 * 8 + 256 * 4 + 32;
+  const unsigned grid_pairs = (unsigned)((pairs + 255) / 256 < 4096 ? (pairs + 255) / 256 : 4096);
+  for (int r = 0; r < g.rounds; ++r) {
+    if (hipMemsetAsync(a.cnt, 0, (size_t)nlist * 8, stream) != hipSuccess) return set_error(MM_ELAUNCH, "%s: memset failed", what);
+    hipLaunchKernelGGL(ivf_group_kernel<false>, dim3(grid_pairs), dim3(256), 0, stream, a, r);
+    hipLaunchKernelGGL(ivf_lscan_kernel, dim3(1), dim3(1024), 0, stream, a, r);
+    hipLaunchKernelGGL(ivf_group_kernel<true>, dim3(grid_pairs), dim3(256), 0, stream, a, r);
+    if (int e = check_launch(what)) return e;
+    if (int e = score(a, r, g)) return e;
+    hipLaunchKernelGGL(ivf_select_kernel, dim3(nq), dim3(1024), lds_sel, stream, a, r, k2);
+    if (int e = check_launch("ivf_select_kernel")) return e;
+  }
+  return MM_OK;
+}
+
+}  // namespace ivf_dev
+}  // namespace mm

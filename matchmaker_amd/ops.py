@@ -800,6 +800,135 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     return out_s, out_r
 
 
+def _ah_codebook_check(what: str, codebook: torch.Tensor, E: int, dtype):
+    if codebook.dim() != 3 or tuple(codebook.shape) != (E // 2, 16, 2) or codebook.dtype != dtype:
+        raise NativeError(f"{what}: codebook must be {dtype} [{E // 2}, 16, 2], got {codebook.dtype} {tuple(codebook.shape)}")
+    return codebook if codebook.is_contiguous() else codebook.contiguous()
+
+
+def ah_encode(x: torch.Tensor, lists: torch.Tensor, centroids: torch.Tensor, codebook: torch.Tensor, eta: float, passes: int = 2):
+    """Anisotropic 4-bit codes of 2-dimensional blocks (the encoder of a quantized index, faiss_index_type: scann:
+    matchmaker/retrieval/scann_index.py:24-47, `score_ah(2, anisotropic_quantization_threshold)`; native mm_ah_encode).
+
+    x [n, E], centroids [nlist, E], codebook [E / 2, 16, 2] float16 / bfloat16 of one dtype, E in {128,...,768} (pad
+    otherwise); lists [n] int32 = the leaf of every row.  Per row the residual to its leaf centre is coded block by block:
+    the nearest codeword first, then `passes` ascending sweeps of coordinate descent on
+    sum |e_s|^2 + (eta - 1) (sum <e_s, x / |x|>)^2 (include/mm_native.h states every fp32 step); lowest code on equal cost.
+    Returns codes [n, E / 4] uint8, the even block in the low nibble.  A pure function of the inputs (no atomics); one
+    enqueue on the current stream, no workspace, no read-back: graph-capturable."""
+    dev = _dev_check(x, lists, centroids, codebook)
+    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
+        raise NativeError(f"ah_encode: expected [n, E] and [nlist, E], got {tuple(x.shape)} {tuple(centroids.shape)}")
+    if x.dtype != centroids.dtype or x.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"ah_encode: float16 / bfloat16 vectors of one dtype needed, got {x.dtype} / {centroids.dtype}")
+    n, E = x.shape
+    if E not in _KMEANS_DIMS:
+        raise NativeError(f"ah_encode: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    if lists.dim() != 1 or lists.dtype != torch.int32 or lists.shape[0] != n:
+        raise NativeError(f"ah_encode: lists must be int32 [n], got {lists.dtype} {tuple(lists.shape)}")
+    if centroids.shape[0] < 1:
+        raise NativeError("ah_encode: no centroids")
+    codebook = _ah_codebook_check("ah_encode", codebook, E, x.dtype)
+    eta, passes = float(eta), int(passes)
+    if not (0.0 <= eta < 3.0e38) or not 0 <= passes <= 64:
+        raise NativeError(f"ah_encode: eta={eta} must be finite and >= 0, passes={passes} in 0 .. 64", _lib.MM_EUNSUPPORTED)
+    x = x if x.is_contiguous() else x.contiguous()
+    lists = lists if lists.is_contiguous() else lists.contiguous()
+    centroids = centroids if centroids.is_contiguous() else centroids.contiguous()
+    codes = torch.empty((n, E // 4), dtype=torch.uint8, device=dev)
+    if n == 0:
+        return codes
+    L = _lib.lib()
+    with _on(dev):
+        rc = L.mm_ah_encode(x.data_ptr(), lists.data_ptr(), centroids.data_ptr(), codebook.data_ptr(), n, centroids.shape[0], E,
+                            _DT[x.dtype], eta, passes, codes.data_ptr(), _stream(dev))
+    _lib.check(rc, "mm_ah_encode")
+    return codes
+
+
+def ah_scan(queries: torch.Tensor, codes: torch.Tensor, codebook: torch.Tensor, list_begin: torch.Tensor, probes: torch.Tensor,
+            probe_scores: torch.Tensor, k: int):
+    """Exact top-k of the quantized scores over the lists each query probes (the 4-bit scoring stage of a quantized index,
+    faiss_index_type: scann: matchmaker/retrieval/scann_index.py:24-47; native mm_ah_scan_fwd).
+
+    queries [nq, E] float16 / bfloat16, E in {128,...,768}; codes [n, E / 4] uint8 stored list by list, list l = rows
+    list_begin[l] .. list_begin[l + 1] (list_begin [nlist + 1] int64); codebook [E / 2, 16, 2] of the queries' dtype; probes
+    [nq, nprobe] int32 list numbers, -1 = no list (a list named twice in one row: undefined result, memory stays in
+    bounds); probe_scores [nq, nprobe] float32.  score(q, i) = probe_scores[q, j] + <q, decode(codes[i])> for row i of list
+    probes[q, j], fp32-accumulated.  Returns (scores [nq, k] float32 descending, rows [nq, k] int64; -inf / -1 padded;
+    equal scores: lower row first).  One enqueue on the current stream, no read-back: graph-capturable."""
+    dev = _dev_check(queries, codes, codebook, list_begin, probes, probe_scores)
+    if queries.dim() != 2 or codes.dim() != 2 or queries.shape[1] != codes.shape[1] * 4 or codes.dtype != torch.uint8:
+        raise NativeError(f"ah_scan: expected [nq, E] queries and uint8 [n, E / 4] codes, got {tuple(queries.shape)} "
+                          f"{codes.dtype} {tuple(codes.shape)}")
+    if queries.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"ah_scan: float16 / bfloat16 queries needed, got {queries.dtype}")
+    nq, E = queries.shape
+    if E not in _KMEANS_DIMS:
+        raise NativeError(f"ah_scan: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    codebook = _ah_codebook_check("ah_scan", codebook, E, queries.dtype)
+    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
+        raise NativeError(f"ah_scan: list_begin must be int64 [nlist + 1], got {list_begin.dtype} {tuple(list_begin.shape)}")
+    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != nq or probes.shape[1] < 1:
+        raise NativeError(f"ah_scan: probes must be int32 [nq, nprobe], got {probes.dtype} {tuple(probes.shape)}")
+    if probe_scores.dtype != torch.float32 or tuple(probe_scores.shape) != tuple(probes.shape):
+        raise NativeError(f"ah_scan: probe_scores must be float32 {tuple(probes.shape)}, got {probe_scores.dtype} "
+                          f"{tuple(probe_scores.shape)}")
+    if not 1 <= k <= 4096 or probes.shape[1] > 4096:
+        raise NativeError(f"ah_scan: k={k} / nprobe={probes.shape[1]} outside 1 .. 4096")
+    queries = queries if queries.is_contiguous() else queries.contiguous()
+    codes = codes if codes.is_contiguous() else codes.contiguous()
+    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
+    probes = probes if probes.is_contiguous() else probes.contiguous()
+    probe_scores = probe_scores if probe_scores.is_contiguous() else probe_scores.contiguous()
+    n, nlist, nprobe = codes.shape[0], list_begin.shape[0] - 1, probes.shape[1]
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    if nq == 0:
+        return out_s, out_r
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_ah_scan_workspace_bytes, n, nlist, nq, nprobe, k)
+        ws = _workspace(dev, wsb)
+        rc = L.mm_ah_scan_fwd(queries.data_ptr(), codes.data_ptr() if n else None, codebook.data_ptr(), list_begin.data_ptr(),
+                              probes.data_ptr(), probe_scores.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
+                              out_s.data_ptr(), out_r.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
+    _lib.check(rc, "mm_ah_scan_fwd")
+    return out_s, out_r
+
+
+def gather_dot(queries: torch.Tensor, vectors: torch.Tensor, rows: torch.Tensor):
+    """Exact inner products of every query with the rows named for it (the re-score of a quantized index's candidates:
+    matchmaker/retrieval/scann_index.py:35 `reorder`; native mm_gather_dot).
+
+    queries [nq, E], vectors [n, E] float16 / bfloat16 of one dtype, E in {128,...,768} (pad otherwise); rows [nq, R] int64,
+    -1 = none.  Returns out [nq, R] float32 = <queries[q], vectors[rows[q, j]]> accumulated in fp32, -inf for a row of -1.
+    One enqueue on the current stream, no workspace, no read-back: graph-capturable."""
+    dev = _dev_check(queries, vectors, rows)
+    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
+        raise NativeError(f"gather_dot: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
+    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"gather_dot: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
+    nq, E = queries.shape
+    if E not in _KMEANS_DIMS:
+        raise NativeError(f"gather_dot: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    if rows.dim() != 2 or rows.dtype != torch.int64 or rows.shape[0] != nq:
+        raise NativeError(f"gather_dot: rows must be int64 [nq, R], got {rows.dtype} {tuple(rows.shape)}")
+    queries = queries if queries.is_contiguous() else queries.contiguous()
+    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
+    rows = rows if rows.is_contiguous() else rows.contiguous()
+    R = rows.shape[1]
+    out = torch.empty((nq, R), dtype=torch.float32, device=dev)
+    if nq == 0 or R == 0:
+        return out
+    L = _lib.lib()
+    with _on(dev):
+        rc = L.mm_gather_dot(queries.data_ptr(), vectors.data_ptr() if vectors.shape[0] else None, rows.data_ptr(),
+                             vectors.shape[0], nq, R, E, _DT[queries.dtype], out.data_ptr(), _stream(dev))
+    _lib.check(rc, "mm_gather_dot")
+    return out
+
+
 def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.Tensor, entry_rows: torch.Tensor, ef: int, k: int,
                  width: int = 4, max_iters: Optional[int] = None, return_stats: bool = False):
     """Beam search over a fixed-degree neighbour graph (the search of a graph index, faiss_index_type: hnsw; native

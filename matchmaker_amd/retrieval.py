@@ -21,7 +21,13 @@ takes the same path with `native_kmeans=True`.
 GraphIPIndexer (faiss_index_type: hnsw) has the surface of `FaissHNSWIndexer` (a CPU index in the reference): a one-level
 neighbour graph built exactly from the shard's k-NN lists (the top-k kernel over the shard itself), searched by
 mm_graph_search_fwd from entry rows that the top-k kernel picks out of a strided sample.
+
+ScannIPIndexer (faiss_index_type: scann) has the surface of `ScaNNIndexer` (matchmaker/retrieval/scann_index.py:10-53, a CPU
+library in the reference): int(sqrt(n)) spherical k-means leaves, 4-bit anisotropic codes of 2-dimensional blocks of the
+residuals (mm_ah_encode), probe selection with the top-k kernel, the scan of the probed leaves' codes (mm_ah_scan_fwd) and
+the exact re-score of the best candidates from the resident originals (mm_gather_dot).
 """
+import os
 from typing import List, Optional
 
 import numpy as np
@@ -809,3 +815,277 @@ class GraphIPIndexer:
         self.M, self.entry_sample = M, int(sr.size)
         if config_overwrites is not None and "faiss_hnsw_efSearch" in config_overwrites:
             self.ef_search = int(config_overwrites["faiss_hnsw_efSearch"])
+
+
+_SCANN_MAGIC = "matchmaker_amd.ScannIPIndexer"
+_SCANN_FORMAT = 1
+_SCANN_FILE = "scann_ip.npz"
+
+
+def _segment_sum_torch(x: torch.Tensor, order: torch.Tensor, list_begin: torch.Tensor) -> torch.Tensor:
+    """ops.kmeans_segment_sum in torch (host stand-in paths only)."""
+    nlist = list_begin.shape[0] - 1
+    lists = torch.repeat_interleave(torch.arange(nlist, device=x.device), torch.diff(list_begin))
+    return torch.zeros((nlist, x.shape[1]), dtype=torch.float32, device=x.device).index_add_(0, lists, x[order].float())
+
+
+def train_ah_codebook(residuals: torch.Tensor, iters: int = 10, seed: int = 208973249, chunk: int = 1 << 14) -> torch.Tensor:
+    """The codebook of the 4-bit codes: residuals [m, E] float32 -> [E / 2, 16, 2] float32, 16 centres per 2-dimensional
+    block by plain (Euclidean) k-means, `iters` iterations from 16 rows drawn with `seed` (the same rows for every block;
+    repeated when m < 16).  Assignment = nearest centre, lowest number on equal distance; the update sums every centre's
+    members with masked reductions over row chunks in a fixed order (no atomics, no scatter), so two runs from one seed
+    give bit-equal codebooks; a centre without members keeps its place."""
+    m, E = residuals.shape
+    S = E // 2
+    if m < 1:
+        raise ops.NativeError("train_ah_codebook: no training rows")
+    r = residuals.reshape(m, S, 2)
+    gen = torch.Generator().manual_seed(int(seed))
+    rows = torch.randperm(m, generator=gen)[:16]
+    rows = rows[torch.arange(16) % rows.numel()].to(r.device)
+    cb = r[rows].permute(1, 0, 2).contiguous()                     # [S, 16, 2]
+    for _ in range(iters):
+        sums = torch.zeros((S, 16, 2), dtype=torch.float32, device=r.device)
+        counts = torch.zeros((S, 16), dtype=torch.float32, device=r.device)
+        for lo in range(0, m, chunk):
+            rc = r[lo: lo + chunk]                                 # [c, S, 2]
+            d0 = rc[:, :, None, 0] - cb[None, :, :, 0]
+            d1 = rc[:, :, None, 1] - cb[None, :, :, 1]
+            a = torch.argmin(d0 * d0 + d1 * d1, dim=2)             # [c, S]
+            for k in range(16):
+                mk = (a == k).to(torch.float32)
+                sums[:, k] += (rc * mk[:, :, None]).sum(dim=0)
+                counts[:, k] += mk.sum(dim=0)
+        cb = torch.where(counts[:, :, None] > 0, sums / counts[:, :, None].clamp_min(1.0), cb)
+    return cb
+
+
+class ScannIPIndexer:
+    """Drop-in for the reference's ScaNN index (`ScaNNIndexer`, matchmaker/retrieval/scann_index.py:10-53: scann's
+    `.tree(num_leaves=int(sqrt(n)), num_leaves_to_search=100).score_ah(2, anisotropic_quantization_threshold=0.2)
+    .reorder(top_n)`, a CPU library there).  `prepare` is a no-op, `index(ids, data_chunks)` trains the leaves (spherical
+    k-means) and the codebook, stores this rank's shard leaf by leaf — 4-bit codes for the scan, the float16 originals
+    for the re-score —, `search(query_vec, top_n)` probes min(100, leaves) leaves, takes the best max(top_n, reorder)
+    rows by their quantized scores (ops.ah_scan), re-scores them exactly (ops.gather_dot) and returns the top_n, merged
+    over the ranks.  `save(path)` / `load(path)` use a directory, as scann's serialize does, with a file format of their own.
+
+    Config keys that are NOT the reference's (all optional): scann_num_leaves, scann_leaves_to_search, scann_reorder,
+    scann_anisotropic_threshold.
+
+    Differences from ScaNN (which cannot be installed here: parity is unpinned): the tree is our spherical k-means on a
+    seeded sample of at most KMEANS_TRAIN_ROWS rows; the codebook is plain k-means over residual blocks
+    (`train_ah_codebook`), not ScaNN's anisotropic codebook training; the encoder runs a fixed schedule (nearest codeword,
+    then DESCENT_PASSES ascending sweeps of coordinate descent); eta is the closed form (token_dim - 1) T^2 / (1 - T^2);
+    scores come from decoded codewords through MFMA, not from SIMD LUT16 look-up tables with quantized sums; vectors and
+    queries are float16; equal scores come lower row first."""
+
+    KMEANS_ITERS = 20
+    KMEANS_TRAIN_ROWS = 1 << 18   # rows of the seeded sample the leaves are trained on
+    CODEBOOK_ITERS = 10
+    CODEBOOK_TRAIN_ROWS = 1 << 16
+    DESCENT_PASSES = 2
+    ASSIGN_CHUNK = 1 << 14
+
+    def __init__(self, config, device=None, group=None, topk_fn=None, encode_fn=None, scan_fn=None, rescore_fn=None,
+                 merge_fn=None):
+        """topk_fn(queries, vectors, k) / encode_fn(x, lists, centroids, codebook, eta, passes) / scan_fn(queries, codes,
+        codebook, list_begin, probes, probe_scores, k) / rescore_fn(queries, vectors, rows) / merge_fn(scores, ids, k)
+        default to ops.dot_topk / ops.ah_encode / ops.ah_scan / ops.gather_dot / ops.topk_merge; the CPU test-suite injects
+        stand-ins.  With the native top-k the leaves are trained by `spherical_kmeans` on ops.kmeans_assign /
+        ops.kmeans_segment_sum; an injected topk_fn also stands in for the assignment."""
+        self._native = topk_fn is None
+        self._topk = topk_fn if topk_fn is not None else ops.dot_topk
+        self._encode = encode_fn if encode_fn is not None else ops.ah_encode
+        self._scan = scan_fn if scan_fn is not None else ops.ah_scan
+        self._rescore = rescore_fn if rescore_fn is not None else ops.gather_dot
+        self._merge = merge_fn if merge_fn is not None else ops.topk_merge
+        self.token_dim = config["token_dim"]
+        if config.get("token_dtype", "float16") != "float16":
+            raise ops.NativeError("ScannIPIndexer stores float16 originals, float16 centres and a float16 codebook and rounds "
+                                  "queries to float16: set token_dtype: float16, or keep scann for an fp32 index")
+        self.num_leaves = config.get("scann_num_leaves")                       # None: int(sqrt(n)) at index time
+        self.leaves_to_search = int(config.get("scann_leaves_to_search", 100))
+        self.threshold = float(config.get("scann_anisotropic_threshold", 0.2))
+        if "scann_reorder" in config:
+            self.reorder = int(config["scann_reorder"])
+        elif config.get("query_sets"):
+            c = next(iter(config["query_sets"].values()))                      # scann_index.py:21-22
+            self.reorder = int(c.get("index_hit_top_n", c["top_n"]))
+        else:
+            raise ops.NativeError("ScannIPIndexer: the reorder count comes from the first entry of query_sets "
+                                  "(index_hit_top_n, else top_n) or from scann_reorder: neither is configured")
+        if (self.num_leaves is not None and int(self.num_leaves) < 1) or self.leaves_to_search < 1 or self.reorder < 1 \
+                or not 0.0 <= self.threshold < 1.0:
+            raise ops.NativeError("scann_num_leaves, scann_leaves_to_search and scann_reorder must be positive, "
+                                  "scann_anisotropic_threshold in [0, 1)")
+        T2 = self.threshold * self.threshold
+        self.eta = (self.token_dim - 1) * T2 / (1.0 - T2) if self.threshold > 0 else 1.0
+        self.seed = int(config.get("random_seed", 208973249))
+        self.dtype = torch.float16
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
+        self.group = group
+        self.E_pad = _pad_dim(self.token_dim)
+        self.nlist: Optional[int] = None
+        self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
+        self.codebook: Optional[torch.Tensor] = None          # [E_pad / 2, 16, 2] float16
+        self.codes: Optional[torch.Tensor] = None             # [n_local, E_pad / 4] uint8, leaf by leaf
+        self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad] float16, same order
+        self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids, same order
+        self.list_begin: Optional[torch.Tensor] = None        # [nlist + 1] int64
+
+    def _world(self):
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group), dist.get_rank(self.group)
+        return 1, 0
+
+    def prepare(self, data_chunks: List[np.ndarray] = None, subsample=-1):      # scann trains inside index()
+        pass
+
+    def _to_device(self, data_chunks: List[np.ndarray], lo: int, hi: int) -> torch.Tensor:
+        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
+        off = 0
+        for c in data_chunks:
+            a, b = max(lo, off), min(hi, off + c.shape[0])
+            if a < b:
+                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
+                    self.device).to(self.dtype)
+            off += c.shape[0]
+        return vec
+
+    def _assign(self, x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+        """[n] int32: the centre of maximum inner product of every row (lowest number on equal scores)."""
+        if self._native:
+            return ops.kmeans_assign(x, centroids)[0]
+        out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
+        for a in range(0, x.shape[0], self.ASSIGN_CHUNK):
+            out[a: a + self.ASSIGN_CHUNK] = self._topk(x[a: a + self.ASSIGN_CHUNK], centroids, 1)[1][:, 0].to(torch.int32)
+        return out
+
+    def _sample(self, x: torch.Tensor, rows: int, gen) -> torch.Tensor:
+        if x.shape[0] <= rows:
+            return x
+        return x[torch.randperm(x.shape[0], generator=gen)[:rows].sort().values.to(x.device)]
+
+    def _train(self, x: Optional[torch.Tensor], n_all: int):
+        """Leaves and codebook on rank 0 (x: its training vectors; None elsewhere), then the broadcast."""
+        world, rank = self._world()
+        nlist = int(self.num_leaves) if self.num_leaves is not None else max(1, int(np.sqrt(n_all)))
+        S = self.E_pad // 2
+        if rank == 0:
+            if x.shape[0] < nlist:
+                raise ops.NativeError(f"ScannIPIndexer.index: {x.shape[0]} training vectors for {nlist} leaves")
+            gen = torch.Generator().manual_seed(self.seed)
+            xs = self._sample(x, self.KMEANS_TRAIN_ROWS, gen)
+            kw = {} if self._native else dict(assign_fn=lambda a, c: (self._assign(a, c), None), sum_fn=_segment_sum_torch)
+            cent = spherical_kmeans(xs, nlist, iters=self.KMEANS_ITERS, seed=self.seed, **kw)
+            xc = self._sample(xs, self.CODEBOOK_TRAIN_ROWS, gen)
+            res = xc.float() - cent[self._assign(xc, cent).to(torch.int64)].float()
+            cb = train_ah_codebook(res, self.CODEBOOK_ITERS, self.seed).to(self.dtype)
+        else:
+            cent = torch.empty((nlist, self.E_pad), dtype=self.dtype, device=self.device)
+            cb = torch.empty((S, 16, 2), dtype=self.dtype, device=self.device)
+        if world > 1:
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            dist.broadcast(cent, src=src, group=self.group)
+            dist.broadcast(cb, src=src, group=self.group)
+        self.nlist, self.centroids, self.codebook = nlist, cent.contiguous(), cb.contiguous()
+
+    def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
+        """scann_index.py:24-35: trains on the whole collection (rank 0, broadcast), then every rank stores its contiguous
+        shard leaf by leaf (stable: input order inside a leaf) as codes and originals."""
+        i = np.concatenate(ids).astype(np.int64)
+        n_all = i.shape[0]
+        world, rank = self._world()
+        lo, hi = shard_range(n_all, world, rank)
+        x_all = self._to_device(data_chunks, 0, n_all) if rank == 0 else None
+        self._train(x_all, n_all)
+        mine = x_all[lo:hi] if rank == 0 else self._to_device(data_chunks, lo, hi)
+        self._store(torch.from_numpy(i[lo:hi]).to(self.device), mine)
+
+    def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64); rank 0
+        trains on its own shard, the leaf count comes from the size of all shards."""
+        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
+            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        world, rank = self._world()
+        n_all = torch.tensor([vectors.shape[0]], dtype=torch.int64, device=vectors.device)
+        if world > 1:
+            dist.all_reduce(n_all, group=self.group)
+        self._train(vectors if rank == 0 else None, int(n_all))
+        self._store(ids, vectors)
+
+    def _store(self, ids: torch.Tensor, vectors: torch.Tensor):
+        a = self._assign(vectors, self.centroids)
+        order, lb, _ = _lists_of(a, self.nlist)
+        self.vectors = vectors[order].contiguous()
+        self.ids = ids.to(torch.int64)[order].contiguous()
+        self.list_begin = lb
+        self.codes = self._encode(self.vectors, a[order].to(torch.int32).contiguous(), self.centroids, self.codebook,
+                                  self.eta, self.DESCENT_PASSES)
+
+    def search(self, query_vec, top_n: int):
+        """scann_index.py:37-47: (scores [nq, top_n] float32 descending = exact inner products, ids [nq, top_n] int64;
+        -inf / -1 where the probed leaves ran out)."""
+        s, ids = self.search_device(query_vec, top_n)
+        return s.cpu().numpy(), ids.cpu().numpy()
+
+    def search_device(self, query_vec, top_n: int, return_stages: bool = False):
+        """search() on device tensors.  return_stages: also (probes, quantized scores, candidate rows, exact scores)."""
+        if self.codes is None:
+            raise ops.NativeError("ScannIPIndexer.search: index() (or load()) first")
+        top_n = int(top_n)
+        if not 1 <= top_n <= 4096:
+            raise ops.NativeError(f"ScannIPIndexer.search: top_n = {top_n} outside 1 .. 4096")
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
+        ps, probes = self._topk(qd, self.centroids, min(self.leaves_to_search, self.nlist))
+        probes = probes.to(torch.int32)
+        k = min(max(top_n, self.reorder), 4096)
+        qs, rows = self._scan(qd, self.codes, self.codebook, self.list_begin, probes, ps.to(torch.float32), k)
+        exact = self._rescore(qd, self.vectors, rows)
+        s, best = self._merge(exact, rows, top_n)                  # equal exact scores keep the scan's order
+        ids = torch.where(best >= 0, self.ids[best.clamp(min=0)], best) if self.ids.numel() else best
+        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        return (s, ids, (probes, qs, rows, exact)) if return_stages else (s, ids)
+
+    def _file(self, path: str) -> str:
+        world, rank = self._world()
+        return os.path.join(path, _SCANN_FILE if world == 1 else f"{_SCANN_FILE}.rank{rank}")
+
+    def save(self, path: str):
+        """scann_index.py:49-50 / dense_retrieval.py:330-336: `path` is a directory (created when missing); this rank's shard
+        goes into one numpy .npz archive inside it (`scann_ip.npz`, with `.rank<r>` appended under several ranks)."""
+        os.makedirs(path, exist_ok=True)
+        with open(self._file(path), "wb") as f:
+            np.savez(f, magic=np.array(_SCANN_MAGIC), format=np.array(_SCANN_FORMAT), token_dim=np.array(self.token_dim),
+                     eta=np.array(self.eta), centroids=self.centroids.cpu().numpy(), codebook=self.codebook.cpu().numpy(),
+                     list_begin=self.list_begin.cpu().numpy(), codes=self.codes.cpu().numpy(),
+                     vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy())
+
+    def load(self, path: str):
+        """scann_index.py:52-53: reads the archive inside the directory.  The file decides what was built (leaves, codebook,
+        codes); the config decides how it is searched (leaves to search, reorder)."""
+        p = self._file(path)
+        if not os.path.isdir(path) or not os.path.exists(p):
+            raise ops.NativeError(f"{path} holds no ScannIPIndexer archive ({os.path.basename(p)}): an index serialized by scann "
+                                  "cannot be read, build the index again with index()")
+        with open(p, "rb") as f:
+            head = f.read(4)
+        z = np.load(p, allow_pickle=False) if head[:2] == b"PK" else None
+        if z is None or "magic" not in z.files or str(z["magic"]) != _SCANN_MAGIC or int(z["format"]) != _SCANN_FORMAT:
+            raise ops.NativeError(f"{p} is not a ScannIPIndexer file of format {_SCANN_FORMAT}")
+        if int(z["token_dim"]) != self.token_dim or z["centroids"].shape[1] != self.E_pad:
+            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        n, nlist = z["vectors"].shape[0], z["centroids"].shape[0]
+        lb = z["list_begin"]
+        if (z["codes"].shape != (n, self.E_pad // 4) or z["codes"].dtype != np.uint8 or z["vectors"].dtype != np.float16
+                or z["ids"].shape != (n,) or z["codebook"].shape != (self.E_pad // 2, 16, 2) or lb.shape != (nlist + 1,)
+                or lb[0] != 0 or lb[-1] != n or (np.diff(lb) < 0).any()):
+            raise ops.NativeError(f"{p} is damaged: codes {z['codes'].shape} {z['codes'].dtype}, vectors {z['vectors'].shape}, "
+                                  f"ids {z['ids'].shape}, codebook {z['codebook'].shape}, list_begin {lb.shape}")
+        self.centroids = torch.from_numpy(z["centroids"]).to(self.device)
+        self.codebook = torch.from_numpy(z["codebook"]).to(self.device)
+        self.list_begin = torch.from_numpy(lb.astype(np.int64)).to(self.device)
+        self.codes = torch.from_numpy(z["codes"]).to(self.device)
+        self.vectors = torch.from_numpy(z["vectors"]).to(self.device)
+        self.ids = torch.from_numpy(z["ids"].astype(np.int64)).to(self.device)
+        self.nlist, self.eta = nlist, float(z["eta"])
