@@ -175,6 +175,30 @@ int mm_maxsim_bwd(const void* q, const void* d,
                   int64_t n_pairs, int Q, int D, int E, int dtype,
                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Backward of the all-pairs MaxSim (mm_maxsim_inbatch_fwd): autograd through matchmaker/models/colbert.py:154-162, the
+ * [Bq, Bd] score matrix of in-batch-negative training (train.py:434-467 builds it, loss.backward() train.py:503-524).
+ *   j*(i, j, t) = the FIRST arg-max over the document positions of <q[i, t], d[j, .]> with masked positions at -1000 (mask row
+ *   j, or row i with bug_compatible != 0, which needs Bq == Bd: MM_EINVAL otherwise); no gradient for a padded query token
+ *   or when the arg-max is a masked position.  The arg-max is taken on the recomputed fp32-accumulated similarities (the
+ *   rule of mm_maxsim_bwd; the forward's MM_SIM_ROUND plays no part).
+ *     grad_q[i, t, :] = sum_j grad_out[i, j] d[j, j*(i, j, t), :]
+ *     grad_d[j, p, :] = sum_i sum_{t : j*(i, j, t) = p} grad_out[i, j] q[i, t, :]
+ *   grad_out [Bq, Bd] float32; grad_q [Bq, Q, E], grad_d [Bd, D, E] of element type grad_dtype: MM_F32, or the token vectors'
+ *   own 16-bit type (summed in fp32, rounded once).  Every byte of both is written by the call (zeros where nothing flows).
+ *   grad_q or grad_d may be NULL: that gradient is not needed (a frozen encoder) and its pass is not run.
+ *   No floating-point atomics: sums run in a fixed order (ascending j; ascending (i, t)), two calls give the same bits.
+ *   One stream, no host synchronisation, no allocation: the call can be captured into a graph.
+ *   q/d/masks exactly as given to the forward.  The workspace holds the packed masks and the int16 [Bq, Bd, Q] arg-max table.
+ *   MM_EUNSUPPORTED: E rows that are not 16-byte multiples, D > 14336 (the LDS accumulator of grad_d; the table holds 32767). */
+size_t mm_maxsim_inbatch_bwd_workspace_bytes(int64_t Bq, int64_t Bd, int Q, int D, int E, int q_mask_kind, int d_mask_kind);
+
+int mm_maxsim_inbatch_bwd(const void* q, const void* d,
+                          const void* q_mask, int q_mask_kind,
+                          const void* d_mask, int d_mask_kind,
+                          const float* grad_out, void* grad_q, void* grad_d, int grad_dtype,
+                          int64_t Bq, int64_t Bd, int Q, int D, int E, int dtype, int bug_compatible,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * TK kernel pooling (cosine match matrix + K RBF kernels + log-sum pooling + bin weights).
  *

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 from transformers import AutoModel, PretrainedConfig, PreTrainedModel
 
-from . import _fast, ops
+from . import _fast, ops, torch_ops  # noqa: F401  (torch_ops registers torch.ops.mm_native.maxsim_inbatch and its backward)
 
 
 class ColBERTConfig(PretrainedConfig):
@@ -199,8 +199,13 @@ class ColBERT(PreTrainedModel):
         # (the dynamic teacher calls this OUTSIDE autocast on the fp16 vectors its forward returned, dynamic_teacher.py:245-246:
         # `mm`, `max` and `sum` are all fp16 ops there, and so is the result)
         q, d, sim_round, sum_round = _as_reference_would(query_vecs, document_vecs)
-        score = ops.maxsim_inbatch(q, query_mask, d, document_mask, bug_compatible=self.inbatch_bug_compatible,
-                                   sim_round=sim_round, sum_round=sum_round)
+        if torch.is_grad_enabled() and (q.requires_grad or d.requires_grad):
+            # in-batch-negative training (train.py:434-467): the registered op carries the native backward (mm_maxsim_inbatch_bwd)
+            score = torch.ops.mm_native.maxsim_inbatch(q, query_mask, d, document_mask, self.inbatch_bug_compatible,
+                                                       sim_round, sum_round)
+        else:
+            score = ops.maxsim_inbatch(q, query_mask, d, document_mask, bug_compatible=self.inbatch_bug_compatible,
+                                       sim_round=sim_round, sum_round=sum_round)
         return score.to(q.dtype) if sum_round else score
 
     def get_param_stats(self):            # colbert.py:164-165

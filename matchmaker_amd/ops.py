@@ -409,6 +409,57 @@ def maxsim_inbatch(q: torch.Tensor, q_mask: Optional[torch.Tensor], d: torch.Ten
     return out
 
 
+def maxsim_inbatch_bwd(q: torch.Tensor, q_mask: Optional[torch.Tensor], d: torch.Tensor, d_mask: Optional[torch.Tensor],
+                       grad_out: torch.Tensor, bug_compatible: bool = False, grad_dtype: Optional[torch.dtype] = None,
+                       need_q: bool = True, need_d: bool = True):
+    """Backward of the all-pairs MaxSim (colbert.py:154-162; in-batch negatives, train.py:434-467).  grad_out [Bq, Bd];
+    returns (grad_q [Bq,Q,E], grad_d [Bd,D,E]) as float32, or — grad_dtype = q.dtype — in the token vectors' own 16-bit type
+    (summed in fp32, rounded once).  First arg-max on ties, no floating-point atomics: two calls give the same bits; see
+    mm_maxsim_inbatch_bwd in include/mm_native.h.  need_q / need_d = False: that gradient's pass is not run and None stands
+    in its place (a frozen encoder)."""
+    dev = _dev_check(q, d, q_mask, d_mask, grad_out)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != d.dtype:
+        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
+    Bq, Q, E = q.shape
+    Bd, D, E2 = d.shape
+    if E != E2:
+        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    if bug_compatible and Bq != Bd:
+        raise NativeError(f"maxsim_inbatch_bwd: bug_compatible masking (colbert.py:158) requires Bq == Bd (got {Bq}, {Bd})",
+                          _lib.MM_EINVAL)
+    go = grad_out.detach().reshape(-1).to(torch.float32).contiguous()
+    if go.numel() != Bq * Bd:
+        raise NativeError(f"grad_out has {go.numel()} elements for {Bq} x {Bd} pairs")
+    qm, qp, qk = _mask(q_mask, Bq, Q, "q_mask")
+    dm, dp, dk = _mask(d_mask, Bd, D, "d_mask")
+    L = _lib.lib()
+    E0 = E
+    q, d, E = _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
+    gdt = torch.float32 if grad_dtype is None else grad_dtype
+    if gdt not in (torch.float32, q.dtype):
+        raise NativeError(f"maxsim_inbatch_bwd: gradients are float32 or {q.dtype}, not {gdt}")
+    gq = torch.empty((Bq, Q, E), dtype=gdt, device=dev) if need_q else None
+    gd = torch.empty((Bd, D, E), dtype=gdt, device=dev) if need_d else None
+    if Bq == 0 or Bd == 0:
+        return (gq.zero_()[..., :E0] if need_q else None), (gd.zero_()[..., :E0] if need_d else None)
+    if not (need_q or need_d):
+        return None, None
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_maxsim_inbatch_bwd_workspace_bytes, Bq, Bd, Q, D, E, qk, dk)
+        st = _stream(dev)
+        ws = _workspace(dev, wsb, st)
+        rc = L.mm_maxsim_inbatch_bwd(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, go.data_ptr(),
+                                     gq.data_ptr() if need_q else None, gd.data_ptr() if need_d else None,
+                                     _DT[gdt], Bq, Bd, Q, D, E, _DT[q.dtype], 1 if bug_compatible else 0,
+                                     ws.data_ptr() if ws is not None else None, wsb, st)
+    _lib.check(rc, "mm_maxsim_inbatch_bwd")
+    if E != E0:
+        gq = gq[..., :E0].contiguous() if need_q else None
+        gd = gd[..., :E0].contiguous() if need_d else None
+    return gq, gd
+
+
 def kernel_pool(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor], d_mask: Optional[torch.Tensor],
                 mu: torch.Tensor, sigma: torch.Tensor, alpha: torch.Tensor, w: torch.Tensor,
                 pairs_per_query: int = 1, return_per_kernel: bool = False,

@@ -15,7 +15,7 @@ Importing this module defines
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
-(maxsim, kernel_pool) and an autocast rule that mirrors what the reference's eager code does under
+(maxsim, maxsim_inbatch, kernel_pool) and an autocast rule that mirrors what the reference's eager code does under
 `torch.cuda.amp.autocast(enabled=use_fp16)` (colbert.py:60: the bmm runs in fp16 and RETURNS fp16 — the MaxSim ops cast
 their vectors to the autocast dtype and set sim_round, so every per-token maximum is rounded as the reference's fp16 `max`
 is — and the promoted `sum` returns fp32; the TK family stays fp32 — allennlp's cosine has no fp16 path the configs use, tk.yaml `use_fp16: False`).
@@ -88,6 +88,38 @@ def maxsim_inbatch(q: Tensor, q_mask: Optional[Tensor], d: Tensor, d_mask: Optio
 @maxsim_inbatch.register_fake
 def _(q, q_mask, d, d_mask, bug_compatible=False, sim_round=False, sum_round=False):
     return q.new_empty((q.shape[0], d.shape[0]), dtype=torch.float32)
+
+
+@torch.library.custom_op(_NS + "::maxsim_inbatch_backward", mutates_args=(), device_types="cuda")
+def maxsim_inbatch_backward(q: Tensor, q_mask: Optional[Tensor], d: Tensor, d_mask: Optional[Tensor], grad_out: Tensor,
+                            bug_compatible: bool = False, need_q: bool = True, need_d: bool = True) -> Tuple[Tensor, Tensor]:
+    """(grad_q, grad_d) of maxsim_inbatch in the token vectors' dtype (mm_maxsim_inbatch_bwd: first arg-max, fixed summation
+    order, no atomics).  A gradient that is not needed is not computed: an empty tensor stands in its place."""
+    gq, gd = ops.maxsim_inbatch_bwd(q, q_mask, d, d_mask, grad_out, bug_compatible, grad_dtype=q.dtype, need_q=need_q, need_d=need_d)
+    return (gq if need_q else q.new_empty(0)), (gd if need_d else d.new_empty(0))
+
+
+@maxsim_inbatch_backward.register_fake
+def _(q, q_mask, d, d_mask, grad_out, bug_compatible=False, need_q=True, need_d=True):
+    return q.new_empty(q.shape if need_q else 0), d.new_empty(d.shape if need_d else 0)
+
+
+def _maxsim_inbatch_setup(ctx, inputs, output):
+    q, q_mask, d, d_mask, bug_compatible, _sim, _sum = inputs
+    ctx.save_for_backward(q, q_mask, d, d_mask)
+    ctx.bug_compatible = bug_compatible
+
+
+def _maxsim_inbatch_backward(ctx, g):
+    """(the rounding flags are piecewise constant: the gradient is that of the unrounded maxima.  Under autocast the saved
+    vectors are the cast ones, and autograd's own cast node hands fp32 leaves fp32 gradients.)"""
+    q, q_mask, d, d_mask = ctx.saved_tensors
+    need_q, need_d = ctx.needs_input_grad[0], ctx.needs_input_grad[2]          # a frozen encoder's pass is not run
+    gq, gd = torch.ops.mm_native.maxsim_inbatch_backward(q, q_mask, d, d_mask, g.contiguous(), ctx.bug_compatible, need_q, need_d)
+    return (gq if need_q else None), None, (gd if need_d else None), None, None, None, None
+
+
+maxsim_inbatch.register_autograd(_maxsim_inbatch_backward, setup_context=_maxsim_inbatch_setup)
 
 
 def _maxsim_inbatch_autocast(_ks, q, q_mask, d, d_mask, bug_compatible=False, sim_round=False, sum_round=False):
