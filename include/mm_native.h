@@ -776,6 +776,42 @@ int mm_colbert_candidates(const int64_t* hit_rows, const int64_t* doc_begin_sort
                           int32_t* cand_doc, int64_t* cand_begin, int64_t* cand_end, int32_t* cand_count,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * fp8 ColBERT token store: row quantiser and ragged MaxSim over the quantised rows (additive: MM_ABI_VERSION unchanged).
+ *
+ * Format: codes [T, E] uint8 = OCP e4m3fn bytes (not the MI300 fnuz encoding), scales [T] float32 = one power of two per
+ *   token row.  For a row x taken as float32 values with a = max_k |x_k|:
+ *     s      = 2^clamp(floor(log2 a) - 7, -126, 120), or 1.0 when a == 0
+ *     code_k = RNE_e4m3fn(x_k * (1 / s))            (the multiply is exact; the scaled maximum lies in [128, 256), so
+ *                                                    nothing saturates and the NaN patterns 0x7f / 0xff never appear)
+ *   and the row's value is deq(code_k) * s, an exact product.  |deq * s - x| <= 2^-4 |x| + 2^-10 s per element.  Both
+ *   zeros (0x00, 0x80) are one value.  Non-finite input is the caller's error: the codes and scale of such a row are
+ *   unspecified.
+ *
+ * mm_fp8_quantize_rows: x [n_rows, E] of `dtype` (MM_F32 / MM_F16 / MM_BF16) -> codes, scales.  One 16-lane group per row:
+ *   row maximum, then convert and store.  No atomics, every output byte is written, two calls give the same bits.
+ *   E % 16 != 0 returns MM_EUNSUPPORTED; x and codes 16-byte aligned; n_rows = 0 succeeds.
+ *
+ * mm_maxsim_ragged_fp8_fwd: mm_maxsim_ragged_fwd over such a store,
+ *     out[p] = sum_{i, q_mask} max_{t in [doc_begin[p], doc_end[p])} ( scales[t] * sum_k q[i,k] * deq(codes[t,k]) )
+ *   q [n_queries, Q, E] is MM_F16 or MM_BF16 (MM_F32 returns MM_EUNSUPPORTED) and is NOT quantised: the codes are
+ *   converted to q's type in registers (exact) and multiplied on the 16-bit MFMA, so every product is exact, the
+ *   similarities accumulate in fp32 and the scale multiplies the finished dot product in fp32 (exact) before the maximum.
+ *   pair p uses query p / pairs_per_query; q_mask as for mm_maxsim_fwd; an empty range scores -1000 per live query token;
+ *   flags MM_SIM_ROUND / MM_SUM_ROUND round to q's type exactly as in mm_maxsim_ragged_fwd.  out [n_pairs] float32.
+ *   E in {128, 256, 384, 512, 768} with Q <= 64 streams the rows through LDS; other E % 16 == 0 or larger Q take a
+ *   one-wavefront-per-pair kernel; E % 16 != 0 returns MM_EUNSUPPORTED.  The ranges must lie inside [0, T): the kernels do
+ *   not know T.
+ */
+int mm_fp8_quantize_rows(const void* x, int64_t n_rows, int E, int dtype, uint8_t* codes, float* scales, void* stream);
+
+size_t mm_maxsim_ragged_fp8_workspace_bytes(int64_t n_pairs, int64_t pairs_per_query, int Q, int q_mask_kind);
+
+int mm_maxsim_ragged_fp8_fwd(const void* q, const uint8_t* codes, const float* scales, const int64_t* doc_begin,
+                             const int64_t* doc_end, const void* q_mask, int q_mask_kind, float* out,
+                             int64_t n_pairs, int64_t pairs_per_query, int Q, int E, int q_dtype, int flags,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -338,6 +338,88 @@ def maxsim_ragged(q: torch.Tensor, tokens: torch.Tensor, doc_begin: torch.Tensor
     return out
 
 
+def fp8_quantize_rows(x: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
+    """Token rows -> the fp8 store format (mm_fp8_quantize_rows, include/mm_native.h): x [T, E] fp16 / bf16 / fp32 with
+    E % 16 == 0 -> (codes [T, E] uint8 = OCP e4m3fn bytes, scales [T] float32 = one power of two per row); the row's value is
+    deq(code) * scale.  Deterministic (no atomics).  Non-finite input is the caller's error."""
+    dev = _dev_check(x)
+    if x.dim() != 2 or x.dtype not in _DT:
+        raise NativeError(f"fp8_quantize_rows: expected [T, E] float tensor, got {tuple(x.shape)} {x.dtype}")
+    T, E = x.shape
+    if E % 16:
+        raise NativeError(f"fp8_quantize_rows: E={E} is not a multiple of 16", _lib.MM_EUNSUPPORTED)
+    x = x if x.is_contiguous() else x.contiguous()
+    codes = torch.empty((T, E), dtype=torch.uint8, device=dev)
+    scales = torch.empty(T, dtype=torch.float32, device=dev)
+    if T == 0:
+        return codes, scales
+    with _on(dev):
+        rc = _lib.lib().mm_fp8_quantize_rows(x.data_ptr(), T, E, _DT[x.dtype], codes.data_ptr(), scales.data_ptr(), _stream(dev))
+    _lib.check(rc, "mm_fp8_quantize_rows")
+    return codes, scales
+
+
+def fp8_dequantize_rows(codes: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The values an fp8 store holds, deq(codes) * scales[:, None], in `dtype` — plain torch, on the tensors' device (CPU
+    included).  Exact in float32; exact in bfloat16 / float16 too unless the product leaves that type's range (every e4m3
+    value has 4 significant bits and the scale is a power of two)."""
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or scales.shape != (codes.shape[0],):
+        raise NativeError(f"fp8_dequantize_rows: expected codes [T, E] uint8 and scales [T], got {tuple(codes.shape)} "
+                          f"{codes.dtype} / {tuple(scales.shape)}")
+    return (codes.view(torch.float8_e4m3fn).to(torch.float32) * scales.to(torch.float32)[:, None]).to(dtype)
+
+
+def maxsim_ragged_fp8(q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, doc_begin: torch.Tensor,
+                      doc_end: torch.Tensor, q_mask: Optional[torch.Tensor] = None, pairs_per_query: int = 1,
+                      check_ranges: bool = True, sim_round: bool = False, sum_round: bool = False) -> torch.Tensor:
+    """maxsim_ragged over an fp8 token store (mm_maxsim_ragged_fp8_fwd): codes [T, E] uint8 + scales [T] float32 as
+    fp8_quantize_rows writes them, q [n_queries, Q, E] fp16 or bf16 (NOT quantised: the codes are converted to q's type in
+    registers, exactly, and the row scale multiplies the finished fp32 dot product).  Document p is rows
+    [doc_begin[p], doc_end[p]); pair p scores against query p // pairs_per_query.  sim_round / sum_round round to q's
+    dtype as in maxsim_ragged.  Returns float32 [n_pairs]."""
+    dev = _dev_check(q, codes, scales, doc_begin, doc_end, q_mask)
+    q = _emb(q, "q")
+    if q.dtype == torch.float32:
+        raise NativeError("maxsim_ragged_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit "
+                          "MFMA operand)", _lib.MM_EUNSUPPORTED)
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise NativeError(f"maxsim_ragged_fp8: codes: expected [T, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
+    T = codes.shape[0]
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (T,):
+        raise NativeError(f"maxsim_ragged_fp8: scales: expected [{T}] float32 (one per row of codes), got "
+                          f"{tuple(scales.shape)} {scales.dtype}")
+    nq, Q, E = q.shape
+    if codes.shape[1] != E:
+        raise NativeError(f"embedding dims differ: {E} vs {codes.shape[1]}")
+    if E % 16:
+        raise NativeError(f"maxsim_ragged_fp8: E={E} is not a multiple of 16", _lib.MM_EUNSUPPORTED)
+    codes = codes if codes.is_contiguous() else codes.contiguous()
+    scales = scales if scales.is_contiguous() else scales.contiguous()
+    B = doc_begin.numel()
+    if doc_end.numel() != B:
+        raise NativeError("doc_begin / doc_end must have one entry per pair")
+    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
+        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    doc_begin = doc_begin.to(torch.int64).contiguous()
+    doc_end = doc_end.to(torch.int64).contiguous()
+    qm, qp, qk = _mask(q_mask, nq, Q, "q_mask")
+    L = _lib.lib()
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    if check_ranges:
+        _check_ranges(doc_begin, doc_end, T)
+    with torch.cuda.device(dev):
+        wsb = L.mm_maxsim_ragged_fp8_workspace_bytes(B, pairs_per_query, Q, qk)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+        rc = L.mm_maxsim_ragged_fp8_fwd(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), doc_begin.data_ptr(),
+                                        doc_end.data_ptr(), qp, qk, out.data_ptr(), B, pairs_per_query, Q, E, _DT[q.dtype],
+                                        _flags(sim_round, sum_round), ws.data_ptr() if ws is not None else None, wsb,
+                                        _stream(dev))
+    _lib.check(rc, "mm_maxsim_ragged_fp8_fwd")
+    return out
+
+
 def maxsim_bwd(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor], d_mask: Optional[torch.Tensor],
                grad_out: torch.Tensor, grad_dtype: Optional[torch.dtype] = None):
     """Backward of the paired MaxSim (pair-per-row layout).  Returns (grad_q [B,Q,E], grad_d [B,D,E]) as float32, or —

@@ -15,6 +15,12 @@ rows in place (no gather, no padding).
 `search` is the whole ColBERT retrieval of :391-412 on the device: token search over the resident matrix
 (ops.dot_topk, or an IVFFlatIPIndexer over the token rows), the documents that own the hits
 (ops.colbert_candidates), their MaxSim (ops.maxsim_ragged) and the top_n selection (ops.topk_merge).
+
+fp8 mode (opt-in): the store is `codes` [T, E] uint8 (OCP e4m3fn) + `scales` [T] float32 (one power of two per
+row) instead of the 16-bit matrix — half the resident bytes (158 GB -> 81 GB for MS MARCO at dim 128) and half the bytes the
+MaxSim stage streams.  `quantize_fp8()`, `from_reference_parts(..., fp8=True)`, `load(..., fp8=True)` and `load_fp8()` build
+one; aggregate / rank_hits / search_device / search then score through ops.maxsim_ragged_fp8.  The token search still needs
+16-bit rows: pass `index=` (an indexer that holds its own vectors) or keep them with `keep_tokens=True`.
 """
 import glob
 import os
@@ -27,25 +33,44 @@ from . import ops
 
 
 class TokenStore:
-    def __init__(self, tokens: torch.Tensor, seq_ids: Sequence, begin: np.ndarray, end: np.ndarray,
-                 topk_fn=None, candidates_fn=None, maxsim_fn=None, merge_fn=None):
+    def __init__(self, tokens: Optional[torch.Tensor], seq_ids: Sequence, begin: np.ndarray, end: np.ndarray,
+                 topk_fn=None, candidates_fn=None, maxsim_fn=None, merge_fn=None, *, codes: Optional[torch.Tensor] = None,
+                 scales: Optional[torch.Tensor] = None, source_dtype: Optional[torch.dtype] = None, quantize_fn=None):
         """topk_fn(queries, matrix, k) / candidates_fn(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap) /
         maxsim_fn(q, tokens, begin, end, None, pairs_per_query=, check_ranges=, sim_round=) / merge_fn(scores, ids, k) are what
         search() runs; they default to ops.dot_topk / ops.colbert_candidates / ops.maxsim_ragged / ops.topk_merge (the CPU
-        test-suite injects stand-ins, as for the indexers of retrieval.py)."""
+        test-suite injects stand-ins, as for the indexers of retrieval.py).
+        fp8 mode: codes [T, E] uint8 + scales [T] float32 (ops.fp8_quantize_rows' format) make the store an fp8 one; `tokens`
+        may then be None (the 16-bit rows are not resident) or the rows kept for the token search.  maxsim_fn is then called as
+        maxsim_fn(q, codes, scales, begin, end, None, pairs_per_query=, check_ranges=, sim_round=) and defaults to
+        ops.maxsim_ragged_fp8; source_dtype is the dtype the rows were quantised from (it picks the query's 16-bit type);
+        quantize_fn(x) -> (codes, scales) is what quantize_fp8() and the fp8 loaders run (default ops.fp8_quantize_rows)."""
+        self._fp8 = codes is not None
+        if self._fp8:
+            if scales is None or codes.dim() != 2 or codes.dtype != torch.uint8 or tuple(scales.shape) != (codes.shape[0],):
+                raise ops.NativeError("TokenStore: an fp8 store is codes [T, E] uint8 + scales [T] float32")
+            if tokens is not None and (tokens.shape != codes.shape or tokens.device != codes.device):
+                raise ops.NativeError("TokenStore: the kept token rows and the fp8 codes differ in shape or device")
+        elif tokens is None:
+            raise ops.NativeError("TokenStore: needs the token matrix, or codes + scales of an fp8 store")
         self._topk = topk_fn if topk_fn is not None else ops.dot_topk
         self._candidates = candidates_fn if candidates_fn is not None else ops.colbert_candidates
-        self._maxsim = maxsim_fn if maxsim_fn is not None else ops.maxsim_ragged
+        self._maxsim = maxsim_fn if maxsim_fn is not None else (ops.maxsim_ragged_fp8 if self._fp8 else ops.maxsim_ragged)
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
+        self._quantize = quantize_fn if quantize_fn is not None else ops.fp8_quantize_rows
         self._tokens = tokens                         # [T, E] on the scoring device (read-only: the ranges below were validated against it)
         self._tokens_lowp = None                      # fp16 image of an fp32 store, built on the first use_fp16 aggregate()
+        self._codes, self._scales = codes, scales
+        self._device = codes.device if self._fp8 else tokens.device
+        self._n_rows = int(codes.shape[0] if self._fp8 else tokens.shape[0])
+        self._source_dtype = source_dtype if source_dtype is not None else (tokens.dtype if tokens is not None else torch.float16)
         self.seq_ids = list(seq_ids)
         self._index = {s: i for i, s in enumerate(self.seq_ids)}
         self._begin = np.asarray(begin, dtype=np.int64)   # global row ranges per document
         self._end = np.asarray(end, dtype=np.int64)
         # validated once, on the host copy of doc_infos: the scoring calls then skip the per-call device check
-        if self._begin.size and (self._begin.min() < 0 or self._end.max() > tokens.shape[0] or (self._begin > self._end).any()):
-            raise ops.NativeError(f"TokenStore: document ranges leave the {tokens.shape[0]}-row token matrix "
+        if self._begin.size and (self._begin.min() < 0 or self._end.max() > self._n_rows or (self._begin > self._end).any()):
+            raise ops.NativeError(f"TokenStore: document ranges leave the {self._n_rows}-row token matrix "
                                   "(doc_infos of another store?)")
         self._build_sorted_view()
 
@@ -64,7 +89,7 @@ class TokenStore:
                                   "belong to one document")
         if len(self.seq_ids) >= 2 ** 31:
             raise ops.NativeError("TokenStore: more than 2^31-1 documents")
-        dev = self._tokens.device
+        dev = self._device
         self._begin_sorted = torch.from_numpy(np.ascontiguousarray(b)).to(dev)
         self._end_sorted = torch.from_numpy(np.ascontiguousarray(e)).to(dev)
         self._doc_of_sorted = torch.from_numpy(order.astype(np.int32)).to(dev)
@@ -73,13 +98,36 @@ class TokenStore:
     def tokens(self) -> torch.Tensor:
         """The resident token matrix.  Read-only: aggregate() skips the per-call range check because the document ranges
         were validated against THIS matrix in the constructor — build a new TokenStore for another matrix."""
+        if self._tokens is None:
+            raise ops.NativeError("TokenStore.tokens: this is an fp8 store built without keep_tokens=True — the 16-bit rows are "
+                                  "not resident; read .codes / .scales (ops.fp8_dequantize_rows gives their values)")
         return self._tokens
+
+    @property
+    def is_fp8(self) -> bool:
+        return self._fp8
+
+    @property
+    def codes(self) -> torch.Tensor:
+        """[T, E] uint8, OCP e4m3fn bytes of an fp8 store (read-only, like .tokens)."""
+        if not self._fp8:
+            raise ops.NativeError("TokenStore.codes: not an fp8 store (quantize_fp8() makes one)")
+        return self._codes
+
+    @property
+    def scales(self) -> torch.Tensor:
+        """[T] float32, the power-of-two row scales of an fp8 store."""
+        if not self._fp8:
+            raise ops.NativeError("TokenStore.scales: not an fp8 store (quantize_fp8() makes one)")
+        return self._scales
 
     # ------------------------------------------------------------------ construction
     @classmethod
-    def from_reference_parts(cls, storage: List[np.ndarray], doc_infos: Dict, seq_ids: Sequence, device):
+    def from_reference_parts(cls, storage: List[np.ndarray], doc_infos: Dict, seq_ids: Sequence, device, fp8: bool = False,
+                             **fns):
         """storage[n] = filled part of token_reps_<n>.npy; doc_infos / seq_ids as saved by the
-        reference (dense_retrieval.py:265-266, 278-279)."""
+        reference (dense_retrieval.py:265-266, 278-279).  fp8=True: every file is quantised as it arrives and only its codes
+        and scales are kept — the 16-bit matrix is never resident as a whole.  fns: the constructor's *_fn arguments."""
         base = np.concatenate([[0], np.cumsum([s.shape[0] for s in storage])]).astype(np.int64)
         begin = np.empty(len(seq_ids), dtype=np.int64)
         end = np.empty(len(seq_ids), dtype=np.int64)
@@ -88,14 +136,25 @@ class TokenStore:
             begin[i], end[i] = base[f] + a, base[f] + b
         E = storage[0].shape[1]
         T = int(base[-1])
+        if fp8:
+            quantize = fns.get("quantize_fn") or ops.fp8_quantize_rows
+            codes = torch.empty((T, E), dtype=torch.uint8, device=device)
+            scales = torch.empty((T,), dtype=torch.float32, device=device)
+            src = torch.from_numpy(np.empty(0, dtype=storage[0].dtype)).dtype
+            for n, part in enumerate(storage):        # file by file: one file's 16-bit rows at a time
+                c, s = quantize(torch.from_numpy(np.array(part)).to(device))
+                codes[int(base[n]): int(base[n + 1])] = c
+                scales[int(base[n]): int(base[n + 1])] = s
+            return cls(None, seq_ids, begin, end, codes=codes, scales=scales, source_dtype=src, **fns)
         tokens = torch.empty((T, E), dtype=torch.from_numpy(np.empty(0, dtype=storage[0].dtype)).dtype, device=device)
         for n, part in enumerate(storage):            # file by file: no second host copy of the store
             tokens[int(base[n]): int(base[n + 1])] = torch.from_numpy(np.array(part)).to(device)
-        return cls(tokens, seq_ids, begin, end)
+        return cls(tokens, seq_ids, begin, end, **fns)
 
     @classmethod
-    def load(cls, folder: str, token_dim: int, token_dtype: str, token_block_size: int, device):
-        """Reads a folder written by `dense_retrieval.py encode` (same calls as :292-303)."""
+    def load(cls, folder: str, token_dim: int, token_dtype: str, token_block_size: int, device, fp8: bool = False, **fns):
+        """Reads a folder written by `dense_retrieval.py encode` (same calls as :292-303).  fp8=True: quantised file by
+        file into an fp8 store (from_reference_parts)."""
         dfs = np.load(os.path.join(folder, "doc_infos.npz"), allow_pickle=True)
         doc_infos = dfs.get("doc_infos")[()]
         seq_ids = dfs.get("seq_ids")[()]
@@ -105,12 +164,46 @@ class TokenStore:
             mm = np.memmap(os.path.join(folder, "token_reps_" + str(f) + ".npy"), dtype=np.dtype(token_dtype),
                            mode="r", shape=(token_block_size, token_dim))
             storage.append(mm[: int(filled[f])])
-        return cls.from_reference_parts(storage, doc_infos, list(seq_ids), device)
+        return cls.from_reference_parts(storage, doc_infos, list(seq_ids), device, fp8=fp8, **fns)
+
+    def quantize_fp8(self, keep_tokens: bool = False, maxsim_fn=None) -> "TokenStore":
+        """The fp8 store of this one: same documents, rows as e4m3fn codes + one power-of-two scale each
+        (ops.fp8_quantize_rows; per element |value - x| <= 2^-4 |x| + 2^-10 scale).  keep_tokens=True keeps a reference to
+        the 16-bit rows for token_hits() without index= (no memory is saved then, only MaxSim bytes).  maxsim_fn: the fp8
+        store's scoring function (default ops.maxsim_ragged_fp8); the other injected functions carry over."""
+        if self._fp8:
+            raise ops.NativeError("TokenStore.quantize_fp8: already an fp8 store")
+        codes, scales = self._quantize(self._tokens)
+        return TokenStore(self._tokens if keep_tokens else None, self.seq_ids, self._begin, self._end, topk_fn=self._topk,
+                          candidates_fn=self._candidates, maxsim_fn=maxsim_fn, merge_fn=self._merge, codes=codes, scales=scales,
+                          source_dtype=self._tokens.dtype, quantize_fn=self._quantize)
+
+    def save_fp8(self, folder: str) -> None:
+        """Writes an fp8 store with numpy: codes.npy [T, E] uint8, scales.npy [T] float32 and docs.npz (seq_ids, begin, end,
+        source_dtype).  The format is this project's own; the reference has no quantised store."""
+        if not self._fp8:
+            raise ops.NativeError("TokenStore.save_fp8: not an fp8 store (quantize_fp8() makes one)")
+        os.makedirs(folder, exist_ok=True)
+        np.save(os.path.join(folder, "codes.npy"), self._codes.cpu().numpy())
+        np.save(os.path.join(folder, "scales.npy"), self._scales.cpu().numpy())
+        ids = np.empty(len(self.seq_ids), dtype=object)
+        ids[:] = list(self.seq_ids)
+        np.savez(os.path.join(folder, "docs.npz"), seq_ids=ids, begin=self._begin, end=self._end,
+                 source_dtype=np.array(str(self._source_dtype).replace("torch.", "")))
+
+    @classmethod
+    def load_fp8(cls, folder: str, device, **fns) -> "TokenStore":
+        """Reads a folder written by save_fp8 onto `device`.  fns: the constructor's *_fn arguments."""
+        docs = np.load(os.path.join(folder, "docs.npz"), allow_pickle=True)
+        codes = torch.from_numpy(np.load(os.path.join(folder, "codes.npy"))).to(device)
+        scales = torch.from_numpy(np.load(os.path.join(folder, "scales.npy"))).to(device)
+        src = getattr(torch, str(docs["source_dtype"][()]))
+        return cls(None, list(docs["seq_ids"]), docs["begin"], docs["end"], codes=codes, scales=scales, source_dtype=src, **fns)
 
     # ------------------------------------------------------------------ lookup + scoring
     def ranges(self, seq_ids: Iterable) -> Tuple[torch.Tensor, torch.Tensor]:
         idx = np.fromiter((self._index[s] for s in seq_ids), dtype=np.int64)
-        dev = self.tokens.device
+        dev = self._device
         return torch.from_numpy(self._begin[idx]).to(dev), torch.from_numpy(self._end[idx]).to(dev)
 
     def aggregate(self, query_vecs: torch.Tensor, candidates: Sequence[Sequence],
@@ -123,7 +216,10 @@ class TokenStore:
         False = fp32 similarities of the stored values.  An fp32 store (`token_dtype: float32`) under use_fp16 is scored as
         the reference's autocast scores it: `bmm` casts BOTH operands to fp16 first, so the store's fp16 image (built once, on
         the first such call: +50 % of the store's memory) and the fp16 query are what the kernel reads — MM_SIM_ROUND alone
-        would be a no-op on fp32 rows.  Returns, per query, [(seq_id, score)] like `validation_results[query_id]` (:410)."""
+        would be a no-op on fp32 rows.  An fp8 store is scored by ops.maxsim_ragged_fp8: use_fp16=True = an fp16 query and
+        every per-token maximum rounded to fp16; False = the query in the 16-bit type the rows were quantised from (bf16 for
+        an fp32 source) and fp32 through max and sum.  Returns, per query, [(seq_id, score)] like
+        `validation_results[query_id]` (:410)."""
         nq = query_vecs.shape[0]
         if len(candidates) != nq:
             raise ValueError(f"{nq} queries but {len(candidates)} candidate lists")
@@ -143,10 +239,15 @@ class TokenStore:
         for i, n in enumerate(counts):
             bb[i, :n], ee[i, :n] = b[off: off + n], e[off: off + n]
             off += n
-        tokens = self._scoring_tokens(use_fp16)
-        q = query_vecs.to(tokens.dtype)
-        scores = ops.maxsim_ragged(q, tokens, bb.view(-1), ee.view(-1), None, pairs_per_query=C, check_ranges=False,
-                                   sim_round=bool(use_fp16)).view(nq, C)
+        if self._fp8:
+            scores = self._maxsim(query_vecs.to(self._device).to(self._fp8_query_dtype(use_fp16)), self._codes, self._scales,
+                                  bb.view(-1), ee.view(-1), None, pairs_per_query=C, check_ranges=False,
+                                  sim_round=bool(use_fp16)).view(nq, C)
+        else:
+            tokens = self._scoring_tokens(use_fp16)
+            q = query_vecs.to(tokens.dtype)
+            scores = ops.maxsim_ragged(q, tokens, bb.view(-1), ee.view(-1), None, pairs_per_query=C, check_ranges=False,
+                                       sim_round=bool(use_fp16)).view(nq, C)
         scores = scores.cpu()
         return [[(candidates[i][j], float(scores[i, j])) for j in range(counts[i])] for i in range(nq)]
 
@@ -159,6 +260,12 @@ class TokenStore:
             tokens = self._tokens_lowp
         return tokens
 
+    def _fp8_query_dtype(self, use_fp16: bool) -> torch.dtype:
+        """The 16-bit type of the query an fp8 store is scored with (see aggregate())."""
+        if use_fp16:
+            return torch.float16
+        return self._source_dtype if self._source_dtype in (torch.float16, torch.bfloat16) else torch.bfloat16
+
     # ------------------------------------------------------------------ retrieval: query token vectors -> ranked documents
     def token_hits(self, query_vecs: torch.Tensor, token_top_k: int, index=None,
                    query_chunk: Optional[int] = None) -> torch.Tensor:
@@ -166,19 +273,28 @@ class TokenStore:
         non-zero element; `search_type="encode"` multiplies by the mask, so padding is zero rows) the exact token_top_k rows of
         the store by inner product of the 16-bit values (ops.dot_topk: equal scores go to the lower row), -1 for dead tokens.
         index: an IVFFlatIPIndexer built with index_resident(ids=arange(T), vectors=tokens), so that its ids are token rows
-        (its probed lists are then searched instead of the whole matrix).  query_chunk bounds the tokens per search call."""
+        (its probed lists are then searched instead of the whole matrix).  query_chunk bounds the tokens per search call.
+        An fp8 store has no fp8 token search: it needs index=, or the rows kept by keep_tokens=True."""
         nq, Q, E = query_vecs.shape
         k = int(token_top_k)
         if k < 1 or Q * k > ops.COLBERT_MAX_HITS:
             raise ops.NativeError(f"TokenStore.search: Q * token_top_k = {Q} * {k} hits per query outside 1 .. "
                                   f"{ops.COLBERT_MAX_HITS} (the candidate kernel sorts a query's hits in 64 KB of LDS)",
                                   ops._lib.MM_EUNSUPPORTED)
-        dev = self._tokens.device
+        if self._tokens is None and index is None:
+            raise ops.NativeError("TokenStore.token_hits: an fp8 store holds no 16-bit rows to search — pass index= (an "
+                                  "indexer over the token rows) or build the store with keep_tokens=True",
+                                  ops._lib.MM_EUNSUPPORTED)
+        dev = self._device
         q = query_vecs.to(dev).reshape(nq * Q, E)
         live = torch.nonzero((q != 0).any(dim=1)).flatten()
         hits = torch.full((nq * Q, k), -1, dtype=torch.int64, device=dev)
-        matrix = self._scoring_tokens(True)              # the 16-bit matrix: the store, or an fp32 store's fp16 image
-        qs = q.to(matrix.dtype)
+        if self._tokens is None:                         # fp8 store + index: the dtype the 16-bit matrix would have had
+            matrix = None
+            qs = q.to(self._source_dtype if self._source_dtype != torch.float32 else torch.float16)
+        else:
+            matrix = self._scoring_tokens(True)          # the 16-bit matrix: the store, or an fp32 store's fp16 image
+            qs = q.to(matrix.dtype)
         step = int(query_chunk) if query_chunk else max(int(live.numel()), 1)
         for a in range(0, int(live.numel()), step):
             sel = live[a: a + step]
@@ -192,20 +308,25 @@ class TokenStore:
         trim=False keeps min(H, documents) candidate slots per query instead of reading the largest count back: nothing
         then synchronises and the four launches can be captured into a graph (one chain, no parallel branches)."""
         nq = query_vecs.shape[0]
-        dev = self._tokens.device
+        dev = self._device
         n_docs = int(self._begin_sorted.numel())
         if nq == 0 or n_docs == 0:
             return (torch.full((nq, top_n), float("-inf"), dtype=torch.float32, device=dev),
                     torch.full((nq, top_n), -1, dtype=torch.int64, device=dev))
         cand_doc, cb, ce, count = self._candidates(hit_rows, self._begin_sorted, self._end_sorted, self._doc_of_sorted,
-                                                   int(self._tokens.shape[0]), min(hit_rows.shape[1], n_docs))
+                                                   self._n_rows, min(hit_rows.shape[1], n_docs))
         if trim:
             C = max(int(count.max()), 1)                 # the one read-back: the slots behind it are padding in every query
             cand_doc, cb, ce = cand_doc[:, :C].contiguous(), cb[:, :C].contiguous(), ce[:, :C].contiguous()
         C = cand_doc.shape[1]
-        tokens = self._scoring_tokens(use_fp16)
-        scores = self._maxsim(query_vecs.to(dev).to(tokens.dtype), tokens, cb.view(-1), ce.view(-1), None, pairs_per_query=C,
-                              check_ranges=False, sim_round=bool(use_fp16)).view(nq, C)
+        if self._fp8:
+            scores = self._maxsim(query_vecs.to(dev).to(self._fp8_query_dtype(use_fp16)), self._codes, self._scales,
+                                  cb.view(-1), ce.view(-1), None, pairs_per_query=C, check_ranges=False,
+                                  sim_round=bool(use_fp16)).view(nq, C)
+        else:
+            tokens = self._scoring_tokens(use_fp16)
+            scores = self._maxsim(query_vecs.to(dev).to(tokens.dtype), tokens, cb.view(-1), ce.view(-1), None, pairs_per_query=C,
+                                  check_ranges=False, sim_round=bool(use_fp16)).view(nq, C)
         scores = scores.masked_fill(cand_doc < 0, float("-inf"))
         # ascending cand_doc + the merge's input order on ties = equal scores go to the lower document index
         return self._merge(scores, cand_doc.to(torch.int64), int(top_n))

@@ -12,6 +12,9 @@ Importing this module defines
                                         B, C, K, saturation)                        -> (score [B], windows [B, W])
     torch.ops.mm_native.colbert_candidates(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T,
                                            c_cap=None)          -> (cand_doc, cand_begin, cand_end, count)
+    torch.ops.mm_native.fp8_quantize_rows(x)                                        -> (codes [T, E] uint8, scales [T])
+    torch.ops.mm_native.maxsim_ragged_fp8(q, codes, scales, doc_begin, doc_end, q_mask=None, pairs_per_query=1,
+                                          check_ranges=True, sim_round=False, sum_round=False) -> [n_pairs]
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
@@ -400,6 +403,36 @@ def _(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap=None):
     C = min(H, begin_sorted.shape[0]) if c_cap is None else c_cap
     return (hit_rows.new_empty((nq, C), dtype=torch.int32), hit_rows.new_empty((nq, C), dtype=torch.int64),
             hit_rows.new_empty((nq, C), dtype=torch.int64), hit_rows.new_empty((nq,), dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- fp8 token store
+@torch.library.custom_op(_NS + "::fp8_quantize_rows", mutates_args=(), device_types="cuda")
+def fp8_quantize_rows(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """(codes [T, E] uint8 = OCP e4m3fn bytes, scales [T] float32 powers of two) of token rows x [T, E] (ops.fp8_quantize_rows).
+    A rounding, not a differentiable function: no autograd formula."""
+    return ops.fp8_quantize_rows(x)
+
+
+@fp8_quantize_rows.register_fake
+def _(x):
+    T, E = x.shape
+    return x.new_empty((T, E), dtype=torch.uint8), x.new_empty((T,), dtype=torch.float32)
+
+
+@torch.library.custom_op(_NS + "::maxsim_ragged_fp8", mutates_args=(), device_types="cuda")
+def maxsim_ragged_fp8(q: Tensor, codes: Tensor, scales: Tensor, doc_begin: Tensor, doc_end: Tensor,
+                      q_mask: Optional[Tensor] = None, pairs_per_query: int = 1, check_ranges: bool = True,
+                      sim_round: bool = False, sum_round: bool = False) -> Tensor:
+    """[n_pairs] float32: the ragged MaxSim over an fp8 token store (ops.maxsim_ragged_fp8).  Forward only, like
+    colbert_candidates: a retrieval-time operator over a frozen store."""
+    return ops.maxsim_ragged_fp8(q, codes, scales, doc_begin, doc_end, q_mask, pairs_per_query=pairs_per_query,
+                                 check_ranges=check_ranges, sim_round=sim_round, sum_round=sum_round)
+
+
+@maxsim_ragged_fp8.register_fake
+def _(q, codes, scales, doc_begin, doc_end, q_mask=None, pairs_per_query=1, check_ranges=True, sim_round=False,
+      sum_round=False):
+    return q.new_empty((doc_begin.numel(),), dtype=torch.float32)
 
 
 # ---------------------------------------------------------------------------------------------- graph index
