@@ -38,7 +38,38 @@ def _emb(t: torch.Tensor, name: str) -> torch.Tensor:
         raise NativeError(f"{name}: unsupported dtype {t.dtype}")
     if t.dim() != 3:
         raise NativeError(f"{name}: expected [rows, tokens, dim], got {tuple(t.shape)}")
-    return t if t.is_contiguous() else t.contiguous()
+    return t.contiguous()
+
+
+_NATIVE_DIMS = (128, 256, 384, 512, 768)      # the row widths the retrieval kernels are instantiated for
+
+
+def _pair16(op: str, a: torch.Tensor, b: torch.Tensor, la: str, lb: str):
+    """Two 2-D float16 / bfloat16 matrices of one dtype and one width; la / lb name their shapes in the message."""
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise NativeError(f"{op}: expected {la} and {lb}, got {tuple(a.shape)} {tuple(b.shape)}")
+    if a.dtype != b.dtype or b.dtype not in (torch.float16, torch.bfloat16):
+        raise NativeError(f"{op}: float16 / bfloat16 vectors of one dtype needed, got {a.dtype} / {b.dtype}")
+
+
+def _native_width(op: str, E: int):
+    if E not in _NATIVE_DIMS:
+        raise NativeError(f"{op}: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+
+
+def _list_begin_check(op: str, list_begin: torch.Tensor):
+    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
+        raise NativeError(f"{op}: list_begin must be int64 [nlist + 1], got {list_begin.dtype} {tuple(list_begin.shape)}")
+
+
+def _probes_check(op: str, probes: torch.Tensor, nq: int):
+    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != nq or probes.shape[1] < 1:
+        raise NativeError(f"{op}: probes must be int32 [nq, nprobe], got {probes.dtype} {tuple(probes.shape)}")
+
+
+def _k_range(op: str, k: int, nprobe: int):
+    if not 1 <= k <= 4096 or nprobe > 4096:
+        raise NativeError(f"{op}: k={k} / nprobe={nprobe} outside 1 .. 4096")
 
 
 def _pad_rows(q: torch.Tensor, d: torch.Tensor, mult: int):
@@ -273,7 +304,7 @@ def hbm_stream_probe(t: torch.Tensor, nt: bool = True) -> None:
     """Calibration launch (mm_hbm_stream_probe): streams tensor `t` through the MaxSim kernel's LDS-DMA ring with the
     arithmetic removed.  Returns nothing: it exists to be timed (bench.py extra.hbm_calibration)."""
     dev = _dev_check(t)
-    t = t if t.is_contiguous() else t.contiguous()
+    t = t.contiguous()
     nbytes = (t.numel() * t.element_size()) // 8192 * 8192
     with _on(dev):
         rc = _lib.lib().mm_hbm_stream_probe(t.data_ptr(), nbytes, 1 if nt else 0, _stream(dev))
@@ -310,7 +341,7 @@ def maxsim_ragged(q: torch.Tensor, tokens: torch.Tensor, doc_begin: torch.Tensor
         raise NativeError(f"tokens: expected [T, E] float tensor, got {tuple(tokens.shape)} {tokens.dtype}")
     if q.dtype != tokens.dtype:
         raise NativeError(f"q/tokens dtype mismatch: {q.dtype} vs {tokens.dtype} (convert the query to the store's dtype)")
-    tokens = tokens if tokens.is_contiguous() else tokens.contiguous()
+    tokens = tokens.contiguous()
     nq, Q, E = q.shape
     if tokens.shape[1] != E:
         raise NativeError(f"embedding dims differ: {E} vs {tokens.shape[1]}")
@@ -348,7 +379,7 @@ def fp8_quantize_rows(x: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
     T, E = x.shape
     if E % 16:
         raise NativeError(f"fp8_quantize_rows: E={E} is not a multiple of 16", _lib.MM_EUNSUPPORTED)
-    x = x if x.is_contiguous() else x.contiguous()
+    x = x.contiguous()
     codes = torch.empty((T, E), dtype=torch.uint8, device=dev)
     scales = torch.empty(T, dtype=torch.float32, device=dev)
     if T == 0:
@@ -393,8 +424,8 @@ def maxsim_ragged_fp8(q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
         raise NativeError(f"embedding dims differ: {E} vs {codes.shape[1]}")
     if E % 16:
         raise NativeError(f"maxsim_ragged_fp8: E={E} is not a multiple of 16", _lib.MM_EUNSUPPORTED)
-    codes = codes if codes.is_contiguous() else codes.contiguous()
-    scales = scales if scales.is_contiguous() else scales.contiguous()
+    codes = codes.contiguous()
+    scales = scales.contiguous()
     B = doc_begin.numel()
     if doc_end.numel() != B:
         raise NativeError("doc_begin / doc_end must have one entry per pair")
@@ -821,12 +852,8 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
     shard; queries whose threshold let too few / too many candidates through (status != 0, rare)
     are re-run with a moved threshold until every row is exact."""
     dev = _dev_check(queries, corpus)
-    if queries.dim() != 2 or corpus.dim() != 2 or queries.shape[1] != corpus.shape[1]:
-        raise NativeError(f"dot_topk: expected [nq, E] and [N, E], got {tuple(queries.shape)} {tuple(corpus.shape)}")
-    if queries.dtype != corpus.dtype or corpus.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"dot_topk: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {corpus.dtype}")
-    queries = queries if queries.is_contiguous() else queries.contiguous()
-    corpus = corpus if corpus.is_contiguous() else corpus.contiguous()
+    _pair16("dot_topk", queries, corpus, "[nq, E]", "[N, E]")
+    queries, corpus = queries.contiguous(), corpus.contiguous()
     nq, E = queries.shape
     N = corpus.shape[0]
     L = _lib.lib()
@@ -902,20 +929,12 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     rows [nq, k] int64 rows of `vectors`; -inf / -1 padded when the probed lists hold fewer than k vectors; equal scores:
     lower row first).  One enqueue on the current stream, no read-back: graph-capturable."""
     dev = _dev_check(queries, vectors, list_begin, probes)
-    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
-        raise NativeError(f"ivf_scan: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
-    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"ivf_scan: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
-    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
-        raise NativeError(f"ivf_scan: list_begin must be int64 [nlist + 1], got {list_begin.dtype} {tuple(list_begin.shape)}")
-    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != queries.shape[0] or probes.shape[1] < 1:
-        raise NativeError(f"ivf_scan: probes must be int32 [nq, nprobe], got {probes.dtype} {tuple(probes.shape)}")
-    if not 1 <= k <= 4096 or probes.shape[1] > 4096:
-        raise NativeError(f"ivf_scan: k={k} / nprobe={probes.shape[1]} outside 1 .. 4096")
-    queries = queries if queries.is_contiguous() else queries.contiguous()
-    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
-    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
-    probes = probes if probes.is_contiguous() else probes.contiguous()
+    _pair16("ivf_scan", queries, vectors, "[nq, E]", "[n, E]")
+    _list_begin_check("ivf_scan", list_begin)
+    _probes_check("ivf_scan", probes, queries.shape[0])
+    _k_range("ivf_scan", k, probes.shape[1])
+    queries, vectors = queries.contiguous(), vectors.contiguous()
+    list_begin, probes = list_begin.contiguous(), probes.contiguous()
     nq, E = queries.shape
     n, nlist, nprobe = vectors.shape[0], list_begin.shape[0] - 1, probes.shape[1]
     out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
@@ -936,7 +955,7 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
 def _ah_codebook_check(what: str, codebook: torch.Tensor, E: int, dtype):
     if codebook.dim() != 3 or tuple(codebook.shape) != (E // 2, 16, 2) or codebook.dtype != dtype:
         raise NativeError(f"{what}: codebook must be {dtype} [{E // 2}, 16, 2], got {codebook.dtype} {tuple(codebook.shape)}")
-    return codebook if codebook.is_contiguous() else codebook.contiguous()
+    return codebook.contiguous()
 
 
 def ah_encode(x: torch.Tensor, lists: torch.Tensor, centroids: torch.Tensor, codebook: torch.Tensor, eta: float, passes: int = 2):
@@ -950,13 +969,9 @@ def ah_encode(x: torch.Tensor, lists: torch.Tensor, centroids: torch.Tensor, cod
     Returns codes [n, E / 4] uint8, the even block in the low nibble.  A pure function of the inputs (no atomics); one
     enqueue on the current stream, no workspace, no read-back: graph-capturable."""
     dev = _dev_check(x, lists, centroids, codebook)
-    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
-        raise NativeError(f"ah_encode: expected [n, E] and [nlist, E], got {tuple(x.shape)} {tuple(centroids.shape)}")
-    if x.dtype != centroids.dtype or x.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"ah_encode: float16 / bfloat16 vectors of one dtype needed, got {x.dtype} / {centroids.dtype}")
+    _pair16("ah_encode", x, centroids, "[n, E]", "[nlist, E]")
     n, E = x.shape
-    if E not in _KMEANS_DIMS:
-        raise NativeError(f"ah_encode: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    _native_width("ah_encode", E)
     if lists.dim() != 1 or lists.dtype != torch.int32 or lists.shape[0] != n:
         raise NativeError(f"ah_encode: lists must be int32 [n], got {lists.dtype} {tuple(lists.shape)}")
     if centroids.shape[0] < 1:
@@ -965,9 +980,7 @@ def ah_encode(x: torch.Tensor, lists: torch.Tensor, centroids: torch.Tensor, cod
     eta, passes = float(eta), int(passes)
     if not (0.0 <= eta < 3.0e38) or not 0 <= passes <= 64:
         raise NativeError(f"ah_encode: eta={eta} must be finite and >= 0, passes={passes} in 0 .. 64", _lib.MM_EUNSUPPORTED)
-    x = x if x.is_contiguous() else x.contiguous()
-    lists = lists if lists.is_contiguous() else lists.contiguous()
-    centroids = centroids if centroids.is_contiguous() else centroids.contiguous()
+    x, lists, centroids = x.contiguous(), lists.contiguous(), centroids.contiguous()
     codes = torch.empty((n, E // 4), dtype=torch.uint8, device=dev)
     if n == 0:
         return codes
@@ -997,23 +1010,16 @@ def ah_scan(queries: torch.Tensor, codes: torch.Tensor, codebook: torch.Tensor, 
     if queries.dtype not in (torch.float16, torch.bfloat16):
         raise NativeError(f"ah_scan: float16 / bfloat16 queries needed, got {queries.dtype}")
     nq, E = queries.shape
-    if E not in _KMEANS_DIMS:
-        raise NativeError(f"ah_scan: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    _native_width("ah_scan", E)
     codebook = _ah_codebook_check("ah_scan", codebook, E, queries.dtype)
-    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
-        raise NativeError(f"ah_scan: list_begin must be int64 [nlist + 1], got {list_begin.dtype} {tuple(list_begin.shape)}")
-    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != nq or probes.shape[1] < 1:
-        raise NativeError(f"ah_scan: probes must be int32 [nq, nprobe], got {probes.dtype} {tuple(probes.shape)}")
+    _list_begin_check("ah_scan", list_begin)
+    _probes_check("ah_scan", probes, nq)
     if probe_scores.dtype != torch.float32 or tuple(probe_scores.shape) != tuple(probes.shape):
         raise NativeError(f"ah_scan: probe_scores must be float32 {tuple(probes.shape)}, got {probe_scores.dtype} "
                           f"{tuple(probe_scores.shape)}")
-    if not 1 <= k <= 4096 or probes.shape[1] > 4096:
-        raise NativeError(f"ah_scan: k={k} / nprobe={probes.shape[1]} outside 1 .. 4096")
-    queries = queries if queries.is_contiguous() else queries.contiguous()
-    codes = codes if codes.is_contiguous() else codes.contiguous()
-    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
-    probes = probes if probes.is_contiguous() else probes.contiguous()
-    probe_scores = probe_scores if probe_scores.is_contiguous() else probe_scores.contiguous()
+    _k_range("ah_scan", k, probes.shape[1])
+    queries, codes, list_begin = queries.contiguous(), codes.contiguous(), list_begin.contiguous()
+    probes, probe_scores = probes.contiguous(), probe_scores.contiguous()
     n, nlist, nprobe = codes.shape[0], list_begin.shape[0] - 1, probes.shape[1]
     out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
     out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
@@ -1038,18 +1044,12 @@ def gather_dot(queries: torch.Tensor, vectors: torch.Tensor, rows: torch.Tensor)
     -1 = none.  Returns out [nq, R] float32 = <queries[q], vectors[rows[q, j]]> accumulated in fp32, -inf for a row of -1.
     One enqueue on the current stream, no workspace, no read-back: graph-capturable."""
     dev = _dev_check(queries, vectors, rows)
-    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
-        raise NativeError(f"gather_dot: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
-    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"gather_dot: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
+    _pair16("gather_dot", queries, vectors, "[nq, E]", "[n, E]")
     nq, E = queries.shape
-    if E not in _KMEANS_DIMS:
-        raise NativeError(f"gather_dot: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    _native_width("gather_dot", E)
     if rows.dim() != 2 or rows.dtype != torch.int64 or rows.shape[0] != nq:
         raise NativeError(f"gather_dot: rows must be int64 [nq, R], got {rows.dtype} {tuple(rows.shape)}")
-    queries = queries if queries.is_contiguous() else queries.contiguous()
-    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
-    rows = rows if rows.is_contiguous() else rows.contiguous()
+    queries, vectors, rows = queries.contiguous(), vectors.contiguous(), rows.contiguous()
     R = rows.shape[1]
     out = torch.empty((nq, R), dtype=torch.float32, device=dev)
     if nq == 0 or R == 0:
@@ -1076,10 +1076,7 @@ def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.
     rows were reached), and with return_stats also stats [nq, 2] int32 = (iterations run, rows scored).  One enqueue on
     the current stream, no read-back: graph-capturable."""
     dev = _dev_check(queries, vectors, neighbors, entry_rows)
-    if queries.dim() != 2 or vectors.dim() != 2 or queries.shape[1] != vectors.shape[1]:
-        raise NativeError(f"graph_search: expected [nq, E] and [n, E], got {tuple(queries.shape)} {tuple(vectors.shape)}")
-    if queries.dtype != vectors.dtype or vectors.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"graph_search: float16 / bfloat16 vectors of one dtype needed, got {queries.dtype} / {vectors.dtype}")
+    _pair16("graph_search", queries, vectors, "[nq, E]", "[n, E]")
     if neighbors.dim() != 2 or neighbors.dtype != torch.int32 or neighbors.shape[0] != vectors.shape[0]:
         raise NativeError(f"graph_search: neighbors must be int32 [n, M], got {neighbors.dtype} {tuple(neighbors.shape)}")
     if entry_rows.dim() != 2 or entry_rows.dtype != torch.int32 or entry_rows.shape[0] != queries.shape[0]:
@@ -1090,10 +1087,8 @@ def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.
         max_iters = -(-int(ef) // max(1, int(width))) + 8
     if E % 128:
         queries, vectors, E = _pad_rows(queries, vectors, 128)
-    queries = queries if queries.is_contiguous() else queries.contiguous()
-    vectors = vectors if vectors.is_contiguous() else vectors.contiguous()
-    neighbors = neighbors if neighbors.is_contiguous() else neighbors.contiguous()
-    entry_rows = entry_rows if entry_rows.is_contiguous() else entry_rows.contiguous()
+    queries, vectors = queries.contiguous(), vectors.contiguous()
+    neighbors, entry_rows = neighbors.contiguous(), entry_rows.contiguous()
     out_s = torch.empty((nq, max(int(k), 0)), dtype=torch.float32, device=dev)
     out_r = torch.empty((nq, max(int(k), 0)), dtype=torch.int64, device=dev)
     stats = torch.empty((nq, 2), dtype=torch.int32, device=dev) if return_stats else None
@@ -1111,9 +1106,6 @@ def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.
     return (out_s, out_r, stats) if return_stats else (out_s, out_r)
 
 
-_KMEANS_DIMS = (128, 256, 384, 512, 768)
-
-
 def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
     """Maximum-inner-product assignment against a centroid table (the coarse quantiser of an IVF index with nprobe = 1:
     matchmaker/retrieval/faiss_indices.py:401-428, the loop of matchmaker/distillation/query_clusterer.py:218-221; native
@@ -1123,18 +1115,13 @@ def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
     Returns (list [n] int32, score [n] float32 = the fp32-accumulated inner product with that centroid); equal scores: the
     lowest centroid number.  One enqueue on the current stream, no workspace, no read-back: graph-capturable."""
     dev = _dev_check(x, centroids)
-    if x.dim() != 2 or centroids.dim() != 2 or x.shape[1] != centroids.shape[1]:
-        raise NativeError(f"kmeans_assign: expected [n, E] and [nlist, E], got {tuple(x.shape)} {tuple(centroids.shape)}")
-    if x.dtype != centroids.dtype or x.dtype not in (torch.float16, torch.bfloat16):
-        raise NativeError(f"kmeans_assign: float16 / bfloat16 vectors of one dtype needed, got {x.dtype} / {centroids.dtype}")
+    _pair16("kmeans_assign", x, centroids, "[n, E]", "[nlist, E]")
     n, E = x.shape
     nlist = centroids.shape[0]
-    if E not in _KMEANS_DIMS:
-        raise NativeError(f"kmeans_assign: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)", _lib.MM_EUNSUPPORTED)
+    _native_width("kmeans_assign", E)
     if not 1 <= nlist <= 65536 or n >= 1 << 31:
         raise NativeError(f"kmeans_assign: nlist={nlist} outside 1 .. 65536, or n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
-    x = x if x.is_contiguous() else x.contiguous()
-    centroids = centroids if centroids.is_contiguous() else centroids.contiguous()
+    x, centroids = x.contiguous(), centroids.contiguous()
     out_l = torch.empty(n, dtype=torch.int32, device=dev)
     out_s = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
@@ -1160,19 +1147,13 @@ def kmeans_segment_sum(x: torch.Tensor, order: torch.Tensor, list_begin: torch.T
         raise NativeError(f"kmeans_segment_sum: expected float16 / bfloat16 [n, E], got {x.dtype} {tuple(x.shape)}")
     if order.dim() != 1 or order.dtype != torch.int64 or order.shape[0] != x.shape[0]:
         raise NativeError(f"kmeans_segment_sum: order must be int64 [n], got {order.dtype} {tuple(order.shape)}")
-    if list_begin.dim() != 1 or list_begin.dtype != torch.int64 or list_begin.shape[0] < 2:
-        raise NativeError(f"kmeans_segment_sum: list_begin must be int64 [nlist + 1], got {list_begin.dtype} "
-                          f"{tuple(list_begin.shape)}")
+    _list_begin_check("kmeans_segment_sum", list_begin)
     n, E = x.shape
     nlist = list_begin.shape[0] - 1
-    if E not in _KMEANS_DIMS:
-        raise NativeError(f"kmeans_segment_sum: E={E} is not one of 128, 256, 384, 512, 768 (pad the vectors)",
-                          _lib.MM_EUNSUPPORTED)
+    _native_width("kmeans_segment_sum", E)
     if nlist > 65536 or n >= 1 << 31:
         raise NativeError(f"kmeans_segment_sum: nlist={nlist} outside 1 .. 65536, or n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
-    x = x if x.is_contiguous() else x.contiguous()
-    order = order if order.is_contiguous() else order.contiguous()
-    list_begin = list_begin if list_begin.is_contiguous() else list_begin.contiguous()
+    x, order, list_begin = x.contiguous(), order.contiguous(), list_begin.contiguous()
     sums = torch.empty((nlist, E), dtype=torch.float32, device=dev)
     L = _lib.lib()
     with _on(dev):
@@ -1232,10 +1213,10 @@ def colbert_candidates(hit_rows: torch.Tensor, begin_sorted: torch.Tensor, end_s
     c_cap = need if c_cap is None else int(c_cap)
     if c_cap < need:
         raise NativeError(f"colbert_candidates: c_cap={c_cap} is below min(H, n_docs)={need}", _lib.MM_EUNSUPPORTED)
-    hit_rows = hit_rows if hit_rows.is_contiguous() else hit_rows.contiguous()
-    begin_sorted = begin_sorted if begin_sorted.is_contiguous() else begin_sorted.contiguous()
-    end_sorted = end_sorted if end_sorted.is_contiguous() else end_sorted.contiguous()
-    doc_of_sorted = doc_of_sorted if doc_of_sorted.is_contiguous() else doc_of_sorted.contiguous()
+    hit_rows = hit_rows.contiguous()
+    begin_sorted = begin_sorted.contiguous()
+    end_sorted = end_sorted.contiguous()
+    doc_of_sorted = doc_of_sorted.contiguous()
     cand_doc = torch.empty((nq, c_cap), dtype=torch.int32, device=dev)
     cand_begin = torch.empty((nq, c_cap), dtype=torch.int64, device=dev)
     cand_end = torch.empty((nq, c_cap), dtype=torch.int64, device=dev)

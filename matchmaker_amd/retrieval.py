@@ -26,6 +26,11 @@ ScannIPIndexer (faiss_index_type: scann) has the surface of `ScaNNIndexer` (matc
 library in the reference): int(sqrt(n)) spherical k-means leaves, 4-bit anisotropic codes of 2-dimensional blocks of the
 residuals (mm_ah_encode), probe selection with the top-k kernel, the scan of the probed leaves' codes (mm_ah_scan_fwd) and
 the exact re-score of the best candidates from the resident originals (mm_gather_dot).
+
+What the indexers have in common lives once, in two private bases: `_DeviceIndex` (the config and device set-up with the
+float16 refusal, the chunk-by-chunk copy to the device, rows -> ids) and, for the four that shard over a process group,
+`_ShardedIndex` (this rank's shard, the resident-shard check, `search()`, the all-gather + merge, the archive writer and
+reader).  A class keeps what is its own: training, layout, `search_device`, the fields of its archive.
 """
 import os
 from typing import List, Optional
@@ -56,23 +61,6 @@ def _device_queries(query_vec, dtype, E_pad: int, token_dim: int, device) -> tor
     qd = torch.zeros((q.shape[0], E_pad), dtype=dtype, device=device)
     qd[:, : token_dim] = q.to(device).to(dtype)
     return qd
-
-
-def _merge_shards(s: torch.Tensor, ids: torch.Tensor, top_n: int, group, merge_fn, merge_single_rank: bool = False):
-    """co.shard's final step: all-gather every rank's [nq, top_n] (score, id) lists and merge them; one rank (and no
-    rehearsal asked for) returns its own lists."""
-    if not (dist.is_available() and dist.is_initialized()):
-        return s, ids
-    world = dist.get_world_size(group)
-    if world > 1 or merge_single_rank:
-        nq = s.shape[0]
-        gs = torch.empty((world * nq, top_n), dtype=s.dtype, device=s.device)        # rank-major concatenation
-        gi = torch.empty((world * nq, top_n), dtype=ids.dtype, device=ids.device)
-        dist.all_gather_into_tensor(gs, s.contiguous(), group=group)                  # RCCL over xGMI
-        dist.all_gather_into_tensor(gi, ids.contiguous(), group=group)
-        s, ids = merge_fn(gs.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1),
-                          gi.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1), top_n)
-    return s, ids
 
 
 def _unit_rows(c: torch.Tensor) -> torch.Tensor:
@@ -131,7 +119,135 @@ def spherical_kmeans(x: torch.Tensor, nlist: int, iters: int = 20, seed: int = 2
     return cent
 
 
-class FlatIPIndexer:
+def _assign_by_topk(topk_fn, x: torch.Tensor, centroids: torch.Tensor, chunk: int, out_dtype) -> torch.Tensor:
+    """[n] out_dtype: the centroid of maximum inner product of every row of x, by top-1 calls of `chunk` rows (the chunk
+    bounds the top-k workspace)."""
+    out = torch.empty(x.shape[0], dtype=out_dtype, device=x.device)
+    for a in range(0, x.shape[0], chunk):
+        out[a: a + chunk] = topk_fn(x[a: a + chunk], centroids, 1)[1][:, 0]
+    return out
+
+
+class _DeviceIndex:
+    """What every indexer of this module is: float16 vectors of `token_dim` columns, zero-padded to the native width
+    `E_pad`, resident on one device, with external int64 `ids` beside them."""
+
+    def _configure(self, config, device, refusal: str, fp16_override: bool = True):
+        """base_index.py:14 derives fp16 storage from config["token_dtype"] == "float16"; `faiss_use_fp16` (not a reference
+        key) is an explicit override where fp16_override is set.  faiss keeps fp32 vectors AND fp32 queries when
+        useFloat16 is off (faiss_indices.py:58-61); these indices store fp16 vectors and round the queries to fp16 as well,
+        so near-tie rankings could differ from an fp32 index: `refusal` is raised instead of silently changing the
+        arithmetic."""
+        self.token_dim = config["token_dim"]
+        self.use_fp16 = config.get("token_dtype", "float16") == "float16"
+        if fp16_override:
+            self.use_fp16 = config.get("faiss_use_fp16", self.use_fp16)
+        if not self.use_fp16:
+            raise ops.NativeError(refusal)
+        self.dtype = torch.float16
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
+        self.E_pad = _pad_dim(self.token_dim)
+
+    def _to_device(self, data_chunks: List[np.ndarray], lo: int, hi: int) -> torch.Tensor:
+        """Rows lo .. hi of the concatenated chunks as [hi - lo, E_pad] on the device, chunk by chunk: no second host copy."""
+        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
+        off = 0
+        for c in data_chunks:
+            a, b = max(lo, off), min(hi, off + c.shape[0])
+            if a < b:
+                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
+                    self.device).to(self.dtype)
+            off += c.shape[0]
+        return vec
+
+    def _ids_of(self, rows: torch.Tensor) -> torch.Tensor:
+        """Rows of `vectors` -> external ids (IndexIDMap); -1 stays -1, and an empty shard has only those."""
+        return torch.where(rows >= 0, self.ids[rows.clamp(min=0)], rows) if self.ids.numel() else rows
+
+
+class _ShardedIndex(_DeviceIndex):
+    """The reference's `co.shard = True` (faiss_indices.py:62-66): every rank of `group` holds a contiguous shard of the
+    vectors, searches it and the ranks' lists are merged.  A subclass provides `search_device` and `_merge`."""
+
+    merge_single_rank = False     # run the all-gathers + the merge even in a group of ONE rank (FlatIPIndexer's rehearsal)
+
+    def _configure(self, config, device, group, refusal: str, fp16_override: bool = True):
+        super()._configure(config, device, refusal, fp16_override)
+        self.group = group
+
+    def _world(self):
+        if dist.is_available() and dist.is_initialized():
+            return dist.get_world_size(self.group), dist.get_rank(self.group)
+        return 1, 0
+
+    def _broadcast(self, *tensors):
+        """What rank 0 of the group trained goes to the buffers the other ranks allocated."""
+        if self._world()[0] > 1:
+            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+            for t in tensors:
+                dist.broadcast(t, src=src, group=self.group)
+
+    def _shard(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
+        """(ids [n_local] int64, vectors [n_local, E_pad]) of this rank's contiguous shard, on the device (every rank is
+        given the same full lists, as the reference's single process is)."""
+        i = np.concatenate(ids).astype(np.int64)
+        lo, hi = shard_range(i.shape[0], *self._world())
+        return torch.from_numpy(i[lo:hi]).to(self.device), self._to_device(data_chunks, lo, hi)
+
+    def _check_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
+            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+
+    def search(self, query_vec, top_n: int):
+        """faiss_indices.py:29-36: (scores [nq, top_n] float32 descending, ids [nq, top_n] int64; -inf / -1 where the index
+        reached fewer than top_n vectors) as numpy arrays."""
+        s, ids = self.search_device(query_vec, top_n)
+        return s.cpu().numpy(), ids.cpu().numpy()
+
+    def _finish(self, s: torch.Tensor, ids: torch.Tensor, top_n: int):
+        """co.shard's final step: all-gather every rank's [nq, top_n] (score, id) lists and merge them; one rank (and no
+        rehearsal asked for) returns its own lists."""
+        if not (dist.is_available() and dist.is_initialized()):
+            return s, ids
+        world = dist.get_world_size(self.group)
+        if world > 1 or self.merge_single_rank:
+            nq = s.shape[0]
+            gs = torch.empty((world * nq, top_n), dtype=s.dtype, device=s.device)        # rank-major concatenation
+            gi = torch.empty((world * nq, top_n), dtype=ids.dtype, device=ids.device)
+            dist.all_gather_into_tensor(gs, s.contiguous(), group=self.group)             # RCCL over xGMI
+            dist.all_gather_into_tensor(gi, ids.contiguous(), group=self.group)
+            s, ids = self._merge(gs.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1),
+                                 gi.view(world, nq, top_n).permute(1, 0, 2).reshape(nq, -1), top_n)
+        return s, ids
+
+    def _rank_path(self, path: str) -> str:
+        world, rank = self._world()
+        return path if world == 1 else f"{path}.rank{rank}"
+
+    def _write_archive(self, p: str, magic: str, fmt: int, **fields):
+        """One numpy .npz archive: magic, format, token_dim and the class's own fields (tensors or numbers)."""
+        with open(p, "wb") as f:
+            np.savez(f, magic=np.array(magic), format=np.array(fmt), token_dim=np.array(self.token_dim),
+                     **{k: v.cpu().numpy() if torch.is_tensor(v) else np.array(v) for k, v in fields.items()})
+
+    def _read_archive(self, p: str, what: str, magic: str, fmt: int, width_of: str, rebuild_with: Optional[str] = None):
+        """The archive at p after the checks every class makes: a zip at all (rebuild_with: the class tells a faiss file
+        apart with a message of its own), this class's magic and format, the config's token_dim and the padded width of
+        field `width_of`.  `what` = the class name with its article."""
+        with open(p, "rb") as f:
+            is_zip = f.read(4)[:2] == b"PK"
+        if not is_zip and rebuild_with is not None:
+            raise ops.NativeError(f"{p} is not {what} file (an index written by faiss cannot be read: build the index again "
+                                  f"with {rebuild_with})")
+        z = np.load(p, allow_pickle=False) if is_zip else None
+        if z is None or "magic" not in z.files or str(z["magic"]) != magic or int(z["format"]) != fmt:
+            raise ops.NativeError(f"{p} is not {what} file of format {fmt}")
+        if int(z["token_dim"]) != self.token_dim or z[width_of].shape[1] != self.E_pad:
+            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        return z
+
+
+class FlatIPIndexer(_ShardedIndex):
     def __init__(self, config, device=None, group=None, topk_fn=None, merge_fn=None, merge_single_rank: bool = False):
         """topk_fn(queries, vectors, k) / merge_fn(scores, ids, k) default to the native operators
         (ops.dot_topk / ops.topk_merge); the CPU test-suite injects oracle stand-ins to exercise the
@@ -140,77 +256,40 @@ class FlatIPIndexer:
         self.merge_single_rank = bool(merge_single_rank)
         self._topk = topk_fn if topk_fn is not None else ops.dot_topk
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
-        self.token_dim = config["token_dim"]
-        # base_index.py:14 derives fp16 storage from config["token_dtype"] == "float16"; `faiss_use_fp16` (not a reference
-        # key) is kept as an explicit override only
-        self.use_fp16 = config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16")
-        if not self.use_fp16:
-            # faiss keeps fp32 vectors AND fp32 queries when useFloat16 is off (faiss_indices.py:58-61); this index
-            # stores fp16 vectors and rounds the queries to fp16 as well, so near-tie rankings could differ from
-            # an fp32 IndexFlatIP.  Refuse instead of silently changing the arithmetic.
-            raise ops.NativeError("FlatIPIndexer stores float16 vectors and rounds queries to float16 (faiss useFloat16 "
-                                  "semantics): set token_dtype: float16 (base_index.py:14), or keep faiss for an fp32 index")
-        self.dtype = torch.float16
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
-        self.group = group
+        self._configure(config, device, group,
+                        "FlatIPIndexer stores float16 vectors and rounds queries to float16 (faiss useFloat16 "
+                        "semantics): set token_dtype: float16 (base_index.py:14), or keep faiss for an fp32 index")
         self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad]
         self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids (IndexIDMap)
-        self.E_pad = _pad_dim(self.token_dim)
-
-    def _world(self):
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group), dist.get_rank(self.group)
-        return 1, 0
 
     def prepare(self, data_chunks: List[np.ndarray]):          # base_index.py: nothing to train for a flat index
         pass
 
     def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
         """faiss_indices.py:22-27: one add of all vectors with their ids.  With several ranks each
-        keeps its contiguous shard (every rank is given the same full lists, as the reference's single
-        process is)."""
-        i = np.concatenate(ids).astype(np.int64)
-        n = i.shape[0]
-        world, rank = self._world()
-        lo, hi = shard_range(n, world, rank)
-        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
-        off = 0
-        for c in data_chunks:                                  # chunk by chunk: no second host copy
-            a, b = max(lo, off), min(hi, off + c.shape[0])
-            if a < b:
-                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
-                    self.device).to(self.dtype)
-            off += c.shape[0]
-        self.vectors = vec
-        self.ids = torch.from_numpy(i[lo:hi]).to(self.device)
+        keeps its contiguous shard."""
+        self.ids, self.vectors = self._shard(ids, data_chunks)
 
     def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
         """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64) — for
         collections that are produced on the device (bench.py generates each rank's shard of the 8.8 M synthetic passages in
         place instead of materialising 13.6 GB of host arrays per rank)."""
-        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
-            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        self._check_resident(ids, vectors)
         self.vectors, self.ids = vectors.contiguous(), ids.to(torch.int64).contiguous()
-
-    def search(self, query_vec, top_n: int):
-        """faiss_indices.py:29-36: (scores [nq, top_n] float32 descending, ids [nq, top_n] int64)."""
-        s, ids = self.search_device(query_vec, top_n)
-        return s.cpu().numpy(), ids.cpu().numpy()
 
     def search_device(self, query_vec, top_n: int):
         """search() without the final copy to the host: device tensors (what a caller that keeps working on the GPU wants,
         and what bench.py times)."""
         qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
         s, idx = self._topk(qd, self.vectors, top_n)
-        ids = torch.where(idx >= 0, self.ids[idx.clamp(min=0)], idx)
-        return _merge_shards(s, ids, top_n, self.group, self._merge, self.merge_single_rank)
+        return self._finish(s, self._ids_of(idx), top_n)
 
 
 _IVF_MAGIC = "matchmaker_amd.IVFFlatIPIndexer"
 _IVF_FORMAT = 1
 
 
-class IVFFlatIPIndexer:
+class IVFFlatIPIndexer(_ShardedIndex):
     """Drop-in for the reference's GPU IVF index (`FaissIVFIndexer`, faiss_indices.py:106-145: inner-product inverted
     lists, fp16 scalar quantiser for centroids and lists, `co.shard` over the GPUs): `prepare(data_chunks, subsample)`
     trains `faiss_ivf_list_count` centroids by spherical k-means, `index(ids, data_chunks)` stores this rank's shard list
@@ -234,54 +313,25 @@ class IVFFlatIPIndexer:
         self._topk = topk_fn if topk_fn is not None else ops.dot_topk
         self._scan = scan_fn if scan_fn is not None else ops.ivf_scan
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
-        self.token_dim = config["token_dim"]
-        self.use_fp16 = config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16")
-        if not self.use_fp16:
-            raise ops.NativeError("IVFFlatIPIndexer stores float16 centroids and lists and rounds queries to float16 (the "
-                                  "reference's fp16 IVF: an fp16 scalar quantiser): set token_dtype: float16, or keep faiss "
-                                  "for an fp32 index")
+        self._configure(config, device, group,
+                        "IVFFlatIPIndexer stores float16 centroids and lists and rounds queries to float16 (the "
+                        "reference's fp16 IVF: an fp16 scalar quantiser): set token_dtype: float16, or keep faiss "
+                        "for an fp32 index")
         self.nlist = int(config["faiss_ivf_list_count"])
         self.nprobe = int(config["faiss_ivf_search_probe_count"])
         if self.nlist < 1 or self.nprobe < 1:
             raise ops.NativeError("faiss_ivf_list_count and faiss_ivf_search_probe_count must be positive")
         self.seed = int(config.get("random_seed", 208973249))
-        self.dtype = torch.float16
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
-        self.group = group
-        self.E_pad = _pad_dim(self.token_dim)
         self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
         self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad] list by list
         self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids, same order
         self.list_begin: Optional[torch.Tensor] = None        # [nlist + 1] int64
 
-    def _world(self):
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group), dist.get_rank(self.group)
-        return 1, 0
-
-    def _to_device(self, data_chunks: List[np.ndarray], lo: int, hi: int) -> torch.Tensor:
-        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
-        off = 0
-        for c in data_chunks:
-            a, b = max(lo, off), min(hi, off + c.shape[0])
-            if a < b:
-                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
-                    self.device).to(self.dtype)
-            off += c.shape[0]
-        return vec
-
     def _assign(self, x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
         """[n] int64: the centroid of maximum inner product for every row of x."""
         if self.native_kmeans:
             return self._kassign(x, centroids)[0].to(torch.int64)
-        out = torch.empty(x.shape[0], dtype=torch.int64, device=x.device)
-        for a in range(0, x.shape[0], self.ASSIGN_CHUNK):
-            out[a: a + self.ASSIGN_CHUNK] = self._topk(x[a: a + self.ASSIGN_CHUNK], centroids, 1)[1][:, 0]
-        return out
-
-    @staticmethod
-    def _unit(c: torch.Tensor) -> torch.Tensor:
-        return c / c.norm(dim=1, keepdim=True).clamp_min(1e-20)
+        return _assign_by_topk(self._topk, x, centroids, self.ASSIGN_CHUNK, torch.int64)
 
     def _train_rows(self, n: int, subsample, gen) -> Optional[torch.Tensor]:
         """The seeded, sorted rows a subsample in (0, 1) trains on (host int64), or None for all of them."""
@@ -324,10 +374,9 @@ class IVFFlatIPIndexer:
 
     def _train(self, x: Optional[torch.Tensor], gen):
         """k-means on rank 0 (x is None elsewhere), then the broadcast."""
-        world, rank = self._world()
-        if rank == 0:
+        if self._world()[1] == 0:
             n = x.shape[0]
-            cent = self._unit(x[torch.randperm(n, generator=gen)[: self.nlist].to(x.device)].float()).to(self.dtype)
+            cent = _unit_rows(x[torch.randperm(n, generator=gen)[: self.nlist].to(x.device)].float()).to(self.dtype)
             if self.native_kmeans:
                 cent = spherical_kmeans(x, self.nlist, iters=self.KMEANS_ITERS, init=cent, assign_fn=self._kassign,
                                         sum_fn=self._ksum)
@@ -341,11 +390,10 @@ class IVFFlatIPIndexer:
                 if empty.numel():
                     members = torch.nonzero(a == counts.argmax()).flatten()
                     sums[empty] = x[members[torch.arange(empty.numel(), device=x.device) % members.numel()]].float()
-                cent = self._unit(sums).to(self.dtype)
+                cent = _unit_rows(sums).to(self.dtype)
         else:
             cent = torch.empty((self.nlist, self.E_pad), dtype=self.dtype, device=self.device)
-        if world > 1:
-            dist.broadcast(cent, src=dist.get_global_rank(self.group, 0) if self.group is not None else 0, group=self.group)
+        self._broadcast(cent)
         self.centroids = cent.contiguous()
 
     def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
@@ -353,60 +401,32 @@ class IVFFlatIPIndexer:
         is then stored list by list (stable: input order inside a list)."""
         if self.centroids is None:
             raise ops.NativeError("IVFFlatIPIndexer.index: prepare() (or load()) first")
-        i = np.concatenate(ids).astype(np.int64)
-        world, rank = self._world()
-        lo, hi = shard_range(i.shape[0], world, rank)
-        self.index_resident(torch.from_numpy(i[lo:hi]).to(self.device), self._to_device(data_chunks, lo, hi))
+        self.index_resident(*self._shard(ids, data_chunks))
 
     def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
         """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64)."""
-        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
-            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
-        a = self._assign(vectors, self.centroids)
-        order = torch.sort(a, stable=True).indices
+        self._check_resident(ids, vectors)
+        order, self.list_begin, _ = _lists_of(self._assign(vectors, self.centroids), self.nlist)
         self.vectors = vectors[order].contiguous()
         self.ids = ids.to(torch.int64)[order].contiguous()
-        lb = torch.zeros(self.nlist + 1, dtype=torch.int64, device=vectors.device)
-        lb[1:] = torch.cumsum(torch.bincount(a, minlength=self.nlist), 0)
-        self.list_begin = lb
-
-    def search(self, query_vec, top_n: int):
-        """(scores [nq, top_n] float32 descending, ids [nq, top_n] int64; -inf / -1 where the probed lists ran out)."""
-        s, ids = self.search_device(query_vec, top_n)
-        return s.cpu().numpy(), ids.cpu().numpy()
 
     def search_device(self, query_vec, top_n: int, return_probes: bool = False):
+        """search() on device tensors; -inf / -1 where the probed lists ran out."""
         qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
         probes = self._topk(qd, self.centroids, min(self.nprobe, self.nlist))[1].to(torch.int32)
         s, rows = self._scan(qd, self.vectors, self.list_begin, probes, top_n)
-        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0)], rows) if self.ids.numel() else rows
-        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        s, ids = self._finish(s, self._ids_of(rows), top_n)
         return (s, ids, probes) if return_probes else (s, ids)
-
-    def _rank_path(self, path: str) -> str:
-        world, rank = self._world()
-        return path if world == 1 else f"{path}.rank{rank}"
 
     def save(self, path: str):
         """One numpy .npz archive (this rank's shard; `path + ".rank<r>"` with several ranks)."""
-        with open(self._rank_path(path), "wb") as f:
-            np.savez(f, magic=np.array(_IVF_MAGIC), format=np.array(_IVF_FORMAT), token_dim=np.array(self.token_dim),
-                     nprobe=np.array(self.nprobe), centroids=self.centroids.cpu().numpy(),
-                     list_begin=self.list_begin.cpu().numpy(), vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy())
+        self._write_archive(self._rank_path(path), _IVF_MAGIC, _IVF_FORMAT, nprobe=self.nprobe, centroids=self.centroids,
+                            list_begin=self.list_begin, vectors=self.vectors, ids=self.ids)
 
     def load(self, path: str, config_overwrites=None):
         """faiss_indices.py:143-145: the probe count comes from config_overwrites["faiss_ivf_search_probe_count"]."""
-        p = self._rank_path(path)
-        with open(p, "rb") as f:
-            head = f.read(4)
-        if head[:2] != b"PK":
-            raise ops.NativeError(f"{p} is not an IVFFlatIPIndexer file (an index written by faiss cannot be read: build the "
-                                  "index again with prepare() / index())")
-        z = np.load(p, allow_pickle=False)
-        if "magic" not in z.files or str(z["magic"]) != _IVF_MAGIC or int(z["format"]) != _IVF_FORMAT:
-            raise ops.NativeError(f"{p} is not an IVFFlatIPIndexer file of format {_IVF_FORMAT}")
-        if int(z["token_dim"]) != self.token_dim or z["centroids"].shape[1] != self.E_pad:
-            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        z = self._read_archive(self._rank_path(path), "an IVFFlatIPIndexer", _IVF_MAGIC, _IVF_FORMAT, "centroids",
+                               rebuild_with="prepare() / index()")
         self.centroids = torch.from_numpy(z["centroids"]).to(self.device)
         self.list_begin = torch.from_numpy(z["list_begin"]).to(self.device)
         self.vectors = torch.from_numpy(z["vectors"]).to(self.device)
@@ -417,7 +437,7 @@ class IVFFlatIPIndexer:
             self.nprobe = int(config_overwrites["faiss_ivf_search_probe_count"])
 
 
-class DynamicIVFIndexer:
+class DynamicIVFIndexer(_DeviceIndex):
     """Drop-in for the reference's dynamic IVF index (`FaissDynamicIndexer`, faiss_indices.py:307-428), the index behind
     TAS-Balanced query clustering (matchmaker/distillation/query_clusterer.py:187-221): `prepare` trains
     `faiss_ivf_list_count` centroids by spherical k-means (mm_kmeans_assign / mm_kmeans_segment_sum), `index_all` and
@@ -444,18 +464,13 @@ class DynamicIVFIndexer:
         self._ksum = sum_fn if sum_fn is not None else ops.kmeans_segment_sum
         self._scan = scan_fn if scan_fn is not None else ops.ivf_scan
         self.list_n_probe = 1
-        self.token_dim = config["token_dim"]
         self.faiss_ivf_list_count = int(config["faiss_ivf_list_count"])
         self.nlist = self.faiss_ivf_list_count
         if not 1 <= self.nlist <= 65536:
             raise ops.NativeError("faiss_ivf_list_count must be in 1 .. 65536")
-        if not config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16"):
-            raise ops.NativeError("DynamicIVFIndexer stores float16 centroids and lists and rounds queries to float16: set "
-                                  "token_dtype: float16, or keep faiss for an fp32 index")
+        self._configure(config, device, "DynamicIVFIndexer stores float16 centroids and lists and rounds queries to float16: "
+                        "set token_dtype: float16, or keep faiss for an fp32 index")
         self.seed = int(config.get("random_seed", 208973249))
-        self.dtype = torch.float16
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
-        self.E_pad = _pad_dim(self.token_dim)
         self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
         self._vec = torch.zeros((0, self.E_pad), dtype=self.dtype, device=self.device)      # arrival order
         self._ids = torch.zeros(0, dtype=torch.int64, device=self.device)
@@ -463,11 +478,6 @@ class DynamicIVFIndexer:
         self._view = None                                      # (vectors, ids, list_begin, ids on the host, list_begin on the host)
 
     # ---- training -----------------------------------------------------------------------------------------------------
-    def _to_device(self, a: np.ndarray) -> torch.Tensor:
-        vec = torch.zeros((a.shape[0], self.E_pad), dtype=self.dtype, device=self.device)
-        vec[:, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(a)).to(self.device).to(self.dtype)
-        return vec
-
     @staticmethod
     def train_rows(chunk_sizes: List[int], subsample) -> List[np.ndarray]:
         """The rows of every chunk but the last that `prepare(subsample > -1)` trains on: faiss_indices.py:335-345 —
@@ -490,7 +500,7 @@ class DynamicIVFIndexer:
         n = sum(p.shape[0] for p in parts)
         if n < self.nlist:
             raise ops.NativeError(f"DynamicIVFIndexer.prepare: {n} training vectors for faiss_ivf_list_count = {self.nlist}")
-        x = torch.cat([self._to_device(p) for p in parts])
+        x = self._to_device(parts, 0, n)
         self.centroids = spherical_kmeans(x, self.nlist, iters=self.KMEANS_ITERS, seed=self.seed, assign_fn=self._kassign,
                                           sum_fn=self._ksum)
 
@@ -502,7 +512,7 @@ class DynamicIVFIndexer:
             raise ops.NativeError(f"DynamicIVFIndexer: {ids.shape[0]} ids for {data.shape[0]} vectors")
         if ids.shape[0] == 0:
             return
-        vec = self._to_device(data)
+        vec = self._to_device([data], 0, data.shape[0])
         self._vec = torch.cat([self._vec, vec])
         self._ids = torch.cat([self._ids, torch.from_numpy(ids).to(self.device)])
         self._lists = torch.cat([self._lists, self._kassign(vec, self.centroids)[0].to(torch.int64)])
@@ -582,10 +592,8 @@ class DynamicIVFIndexer:
             raise ops.NativeError("DynamicIVFIndexer: prepare() first")
         qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
         cids = self._kassign(qd, self.centroids)[0]
-        vectors, ids, lb = self._lists_view()[:3]
-        s, rows = self._scan(qd, vectors, lb, cids.to(torch.int32)[:, None].contiguous(), top_n)
-        out = torch.where(rows >= 0, ids[rows.clamp(min=0)], rows) if ids.numel() else rows
-        return s.cpu().numpy(), out.cpu().numpy(), cids.to(torch.int64)[:, None].cpu().numpy()
+        s, rows = self._scan(qd, self.vectors, self.list_begin, cids.to(torch.int32)[:, None].contiguous(), top_n)
+        return s.cpu().numpy(), self._ids_of(rows).cpu().numpy(), cids.to(torch.int64)[:, None].cpu().numpy()
 
 
 _GRAPH_MAGIC = "matchmaker_amd.GraphIPIndexer"
@@ -666,7 +674,7 @@ def build_graph(vectors: torch.Tensor, M: int, topk_fn=None, block: int = 1 << 1
     return out
 
 
-class GraphIPIndexer:
+class GraphIPIndexer(_ShardedIndex):
     """Drop-in for the reference's HNSW index (`FaissHNSWIndexer`, faiss_indices.py: IndexHNSWFlat with
     `faiss_hnsw_graph_neighbors` links, `efSearch`, inner product; a CPU index there — "HNSW does not support GPUs"):
     `prepare` has nothing to train, `index(ids, data_chunks)` stores this rank's shard and builds its neighbour graph
@@ -685,11 +693,8 @@ class GraphIPIndexer:
         self._topk = topk_fn if topk_fn is not None else ops.dot_topk
         self._search = search_fn if search_fn is not None else ops.graph_search
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
-        self.token_dim = config["token_dim"]
-        self.use_fp16 = config.get("faiss_use_fp16", config.get("token_dtype", "float16") == "float16")
-        if not self.use_fp16:
-            raise ops.NativeError("GraphIPIndexer stores float16 vectors and rounds queries to float16: set token_dtype: "
-                                  "float16, or keep faiss for an fp32 index")
+        self._configure(config, device, group, "GraphIPIndexer stores float16 vectors and rounds queries to float16: set "
+                        "token_dtype: float16, or keep faiss for an fp32 index")
         self.M = int(config["faiss_hnsw_graph_neighbors"])
         self.ef_search = int(config["faiss_hnsw_efSearch"])
         self.ef_construction = config.get("faiss_hnsw_efConstruction")       # accepted, ignored: the construction is exact
@@ -701,38 +706,18 @@ class GraphIPIndexer:
         if self.ef_search < 1 or self.entry_sample < 1 or self.entry_count < 1 or not 1 <= self.width <= 8:
             raise ops.NativeError("faiss_hnsw_efSearch, graph_entry_sample and graph_entry_count must be positive, "
                                   "graph_search_width in 1 .. 8")
-        self.dtype = torch.float16
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
-        self.group = group
-        self.E_pad = _pad_dim(self.token_dim)
         self.vectors: Optional[torch.Tensor] = None           # [n_local, E_pad]
         self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids
         self.neighbors: Optional[torch.Tensor] = None         # [n_local, M] int32, -1 padded
         self.sample_rows: Optional[torch.Tensor] = None       # [S] int64 rows of the entry sample
         self.sample_vectors: Optional[torch.Tensor] = None    # [S, E_pad] their vectors, contiguous
 
-    def _world(self):
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group), dist.get_rank(self.group)
-        return 1, 0
-
     def prepare(self, data_chunks: List[np.ndarray] = None, subsample=-1):      # nothing to train
         pass
 
     def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
         """This rank's contiguous shard of the vectors (every rank is given the same full lists) and its graph."""
-        i = np.concatenate(ids).astype(np.int64)
-        world, rank = self._world()
-        lo, hi = shard_range(i.shape[0], world, rank)
-        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
-        off = 0
-        for c in data_chunks:
-            a, b = max(lo, off), min(hi, off + c.shape[0])
-            if a < b:
-                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
-                    self.device).to(self.dtype)
-            off += c.shape[0]
-        self.index_resident(torch.from_numpy(i[lo:hi]).to(self.device), vec)
+        self.index_resident(*self._shard(ids, data_chunks))
 
     def _set_sample(self):
         n = self.vectors.shape[0]
@@ -742,16 +727,10 @@ class GraphIPIndexer:
 
     def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
         """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64)."""
-        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
-            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        self._check_resident(ids, vectors)
         self.vectors, self.ids = vectors.contiguous(), ids.to(torch.int64).contiguous()
         self.neighbors = build_graph(self.vectors, self.M, self._topk)
         self._set_sample()
-
-    def search(self, query_vec, top_n: int):
-        """(scores [nq, top_n] float32 descending, ids [nq, top_n] int64; -inf / -1 where the search reached fewer rows)."""
-        s, ids = self.search_device(query_vec, top_n)
-        return s.cpu().numpy(), ids.cpu().numpy()
 
     def entry_rows(self, qd: torch.Tensor, ef: int) -> torch.Tensor:
         """[nq, min(graph_entry_count, ef, S)] int32: the rows of the sample with the highest inner product."""
@@ -760,6 +739,7 @@ class GraphIPIndexer:
         return torch.where(i >= 0, self.sample_rows[i.clamp(min=0)], i).to(torch.int32)
 
     def search_device(self, query_vec, top_n: int, return_rows: bool = False):
+        """search() on device tensors; -inf / -1 where the search reached fewer rows."""
         if self.neighbors is None:
             raise ops.NativeError("GraphIPIndexer.search: index() (or load()) first")
         qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
@@ -769,35 +749,19 @@ class GraphIPIndexer:
             rows = torch.full((qd.shape[0], top_n), -1, dtype=torch.int64, device=qd.device)
         else:
             s, rows = self._search(qd, self.vectors, self.neighbors, self.entry_rows(qd, ef), ef, top_n, self.width)
-        ids = torch.where(rows >= 0, self.ids[rows.clamp(min=0)], rows) if self.ids.numel() else rows
-        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        s, ids = self._finish(s, self._ids_of(rows), top_n)
         return (s, ids, rows) if return_rows else (s, ids)
-
-    def _rank_path(self, path: str) -> str:
-        world, rank = self._world()
-        return path if world == 1 else f"{path}.rank{rank}"
 
     def save(self, path: str):
         """One numpy .npz archive (this rank's shard; `path + ".rank<r>"` with several ranks)."""
-        with open(self._rank_path(path), "wb") as f:
-            np.savez(f, magic=np.array(_GRAPH_MAGIC), format=np.array(_GRAPH_FORMAT), token_dim=np.array(self.token_dim),
-                     M=np.array(self.M), vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy(),
-                     neighbors=self.neighbors.cpu().numpy(), sample_rows=self.sample_rows.cpu().numpy())
+        self._write_archive(self._rank_path(path), _GRAPH_MAGIC, _GRAPH_FORMAT, M=self.M, vectors=self.vectors, ids=self.ids,
+                            neighbors=self.neighbors, sample_rows=self.sample_rows)
 
     def load(self, path: str, config_overwrites=None):
         """The file decides what was built (vectors, ids, graph, M, entry sample); the config decides how it is searched
         (efSearch, graph_entry_count, graph_search_width), and config_overwrites["faiss_hnsw_efSearch"] overrides efSearch."""
         p = self._rank_path(path)
-        with open(p, "rb") as f:
-            head = f.read(4)
-        if head[:2] != b"PK":
-            raise ops.NativeError(f"{p} is not a GraphIPIndexer file (an index written by faiss cannot be read: build the "
-                                  "index again with index())")
-        z = np.load(p, allow_pickle=False)
-        if "magic" not in z.files or str(z["magic"]) != _GRAPH_MAGIC or int(z["format"]) != _GRAPH_FORMAT:
-            raise ops.NativeError(f"{p} is not a GraphIPIndexer file of format {_GRAPH_FORMAT}")
-        if int(z["token_dim"]) != self.token_dim or z["vectors"].shape[1] != self.E_pad:
-            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        z = self._read_archive(p, "a GraphIPIndexer", _GRAPH_MAGIC, _GRAPH_FORMAT, "vectors", rebuild_with="index()")
         n, M = z["vectors"].shape[0], int(z["M"])
         nb, sr = z["neighbors"], z["sample_rows"]
         if (z["ids"].shape != (n,) or nb.shape != (n, M) or nb.dtype != np.int32 or z["vectors"].dtype != np.float16 or M % 2
@@ -860,7 +824,7 @@ def train_ah_codebook(residuals: torch.Tensor, iters: int = 10, seed: int = 2089
     return cb
 
 
-class ScannIPIndexer:
+class ScannIPIndexer(_ShardedIndex):
     """Drop-in for the reference's ScaNN index (`ScaNNIndexer`, matchmaker/retrieval/scann_index.py:10-53: scann's
     `.tree(num_leaves=int(sqrt(n)), num_leaves_to_search=100).score_ah(2, anisotropic_quantization_threshold=0.2)
     .reorder(top_n)`, a CPU library there).  `prepare` is a no-op, `index(ids, data_chunks)` trains the leaves (spherical
@@ -899,10 +863,10 @@ class ScannIPIndexer:
         self._scan = scan_fn if scan_fn is not None else ops.ah_scan
         self._rescore = rescore_fn if rescore_fn is not None else ops.gather_dot
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
-        self.token_dim = config["token_dim"]
-        if config.get("token_dtype", "float16") != "float16":
-            raise ops.NativeError("ScannIPIndexer stores float16 originals, float16 centres and a float16 codebook and rounds "
-                                  "queries to float16: set token_dtype: float16, or keep scann for an fp32 index")
+        # token_dtype alone decides here: `faiss_use_fp16`, the override the faiss-shaped indices honour, is not read
+        self._configure(config, device, group,
+                        "ScannIPIndexer stores float16 originals, float16 centres and a float16 codebook and rounds "
+                        "queries to float16: set token_dtype: float16, or keep scann for an fp32 index", fp16_override=False)
         self.num_leaves = config.get("scann_num_leaves")                       # None: int(sqrt(n)) at index time
         self.leaves_to_search = int(config.get("scann_leaves_to_search", 100))
         self.threshold = float(config.get("scann_anisotropic_threshold", 0.2))
@@ -921,10 +885,6 @@ class ScannIPIndexer:
         T2 = self.threshold * self.threshold
         self.eta = (self.token_dim - 1) * T2 / (1.0 - T2) if self.threshold > 0 else 1.0
         self.seed = int(config.get("random_seed", 208973249))
-        self.dtype = torch.float16
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())  # noqa: E501
-        self.group = group
-        self.E_pad = _pad_dim(self.token_dim)
         self.nlist: Optional[int] = None
         self.centroids: Optional[torch.Tensor] = None         # [nlist, E_pad] unit length, float16
         self.codebook: Optional[torch.Tensor] = None          # [E_pad / 2, 16, 2] float16
@@ -933,33 +893,14 @@ class ScannIPIndexer:
         self.ids: Optional[torch.Tensor] = None               # [n_local] int64 external ids, same order
         self.list_begin: Optional[torch.Tensor] = None        # [nlist + 1] int64
 
-    def _world(self):
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_world_size(self.group), dist.get_rank(self.group)
-        return 1, 0
-
     def prepare(self, data_chunks: List[np.ndarray] = None, subsample=-1):      # scann trains inside index()
         pass
-
-    def _to_device(self, data_chunks: List[np.ndarray], lo: int, hi: int) -> torch.Tensor:
-        vec = torch.zeros((hi - lo, self.E_pad), dtype=self.dtype, device=self.device)
-        off = 0
-        for c in data_chunks:
-            a, b = max(lo, off), min(hi, off + c.shape[0])
-            if a < b:
-                vec[a - lo: b - lo, : self.token_dim] = torch.from_numpy(np.ascontiguousarray(c[a - off: b - off])).to(
-                    self.device).to(self.dtype)
-            off += c.shape[0]
-        return vec
 
     def _assign(self, x: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
         """[n] int32: the centre of maximum inner product of every row (lowest number on equal scores)."""
         if self._native:
             return ops.kmeans_assign(x, centroids)[0]
-        out = torch.empty(x.shape[0], dtype=torch.int32, device=x.device)
-        for a in range(0, x.shape[0], self.ASSIGN_CHUNK):
-            out[a: a + self.ASSIGN_CHUNK] = self._topk(x[a: a + self.ASSIGN_CHUNK], centroids, 1)[1][:, 0].to(torch.int32)
-        return out
+        return _assign_by_topk(self._topk, x, centroids, self.ASSIGN_CHUNK, torch.int32)
 
     def _sample(self, x: torch.Tensor, rows: int, gen) -> torch.Tensor:
         if x.shape[0] <= rows:
@@ -968,10 +909,8 @@ class ScannIPIndexer:
 
     def _train(self, x: Optional[torch.Tensor], n_all: int):
         """Leaves and codebook on rank 0 (x: its training vectors; None elsewhere), then the broadcast."""
-        world, rank = self._world()
         nlist = int(self.num_leaves) if self.num_leaves is not None else max(1, int(np.sqrt(n_all)))
-        S = self.E_pad // 2
-        if rank == 0:
+        if self._world()[1] == 0:
             if x.shape[0] < nlist:
                 raise ops.NativeError(f"ScannIPIndexer.index: {x.shape[0]} training vectors for {nlist} leaves")
             gen = torch.Generator().manual_seed(self.seed)
@@ -983,11 +922,8 @@ class ScannIPIndexer:
             cb = train_ah_codebook(res, self.CODEBOOK_ITERS, self.seed).to(self.dtype)
         else:
             cent = torch.empty((nlist, self.E_pad), dtype=self.dtype, device=self.device)
-            cb = torch.empty((S, 16, 2), dtype=self.dtype, device=self.device)
-        if world > 1:
-            src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
-            dist.broadcast(cent, src=src, group=self.group)
-            dist.broadcast(cb, src=src, group=self.group)
+            cb = torch.empty((self.E_pad // 2, 16, 2), dtype=self.dtype, device=self.device)
+        self._broadcast(cent, cb)
         self.nlist, self.centroids, self.codebook = nlist, cent.contiguous(), cb.contiguous()
 
     def index(self, ids: List[np.ndarray], data_chunks: List[np.ndarray]):
@@ -1005,8 +941,7 @@ class ScannIPIndexer:
     def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
         """This rank's shard handed over as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64); rank 0
         trains on its own shard, the leaf count comes from the size of all shards."""
-        if vectors.dtype != self.dtype or vectors.dim() != 2 or vectors.shape[1] != self.E_pad or ids.shape[0] != vectors.shape[0]:
-            raise ops.NativeError(f"index_resident: need float16 [n, {self.E_pad}] vectors and [n] ids")
+        self._check_resident(ids, vectors)
         world, rank = self._world()
         n_all = torch.tensor([vectors.shape[0]], dtype=torch.int64, device=vectors.device)
         if world > 1:
@@ -1023,14 +958,9 @@ class ScannIPIndexer:
         self.codes = self._encode(self.vectors, a[order].to(torch.int32).contiguous(), self.centroids, self.codebook,
                                   self.eta, self.DESCENT_PASSES)
 
-    def search(self, query_vec, top_n: int):
-        """scann_index.py:37-47: (scores [nq, top_n] float32 descending = exact inner products, ids [nq, top_n] int64;
-        -inf / -1 where the probed leaves ran out)."""
-        s, ids = self.search_device(query_vec, top_n)
-        return s.cpu().numpy(), ids.cpu().numpy()
-
     def search_device(self, query_vec, top_n: int, return_stages: bool = False):
-        """search() on device tensors.  return_stages: also (probes, quantized scores, candidate rows, exact scores)."""
+        """scann_index.py:37-47 on device tensors: the scores are exact inner products; -inf / -1 where the probed leaves ran
+        out.  return_stages: also (probes, quantized scores, candidate rows, exact scores)."""
         if self.codes is None:
             raise ops.NativeError("ScannIPIndexer.search: index() (or load()) first")
         top_n = int(top_n)
@@ -1043,23 +973,19 @@ class ScannIPIndexer:
         qs, rows = self._scan(qd, self.codes, self.codebook, self.list_begin, probes, ps.to(torch.float32), k)
         exact = self._rescore(qd, self.vectors, rows)
         s, best = self._merge(exact, rows, top_n)                  # equal exact scores keep the scan's order
-        ids = torch.where(best >= 0, self.ids[best.clamp(min=0)], best) if self.ids.numel() else best
-        s, ids = _merge_shards(s, ids, top_n, self.group, self._merge)
+        s, ids = self._finish(s, self._ids_of(best), top_n)
         return (s, ids, (probes, qs, rows, exact)) if return_stages else (s, ids)
 
     def _file(self, path: str) -> str:
-        world, rank = self._world()
-        return os.path.join(path, _SCANN_FILE if world == 1 else f"{_SCANN_FILE}.rank{rank}")
+        return self._rank_path(os.path.join(path, _SCANN_FILE))
 
     def save(self, path: str):
         """scann_index.py:49-50 / dense_retrieval.py:330-336: `path` is a directory (created when missing); this rank's shard
         goes into one numpy .npz archive inside it (`scann_ip.npz`, with `.rank<r>` appended under several ranks)."""
         os.makedirs(path, exist_ok=True)
-        with open(self._file(path), "wb") as f:
-            np.savez(f, magic=np.array(_SCANN_MAGIC), format=np.array(_SCANN_FORMAT), token_dim=np.array(self.token_dim),
-                     eta=np.array(self.eta), centroids=self.centroids.cpu().numpy(), codebook=self.codebook.cpu().numpy(),
-                     list_begin=self.list_begin.cpu().numpy(), codes=self.codes.cpu().numpy(),
-                     vectors=self.vectors.cpu().numpy(), ids=self.ids.cpu().numpy())
+        self._write_archive(self._file(path), _SCANN_MAGIC, _SCANN_FORMAT, eta=self.eta, centroids=self.centroids,
+                            codebook=self.codebook, list_begin=self.list_begin, codes=self.codes, vectors=self.vectors,
+                            ids=self.ids)
 
     def load(self, path: str):
         """scann_index.py:52-53: reads the archive inside the directory.  The file decides what was built (leaves, codebook,
@@ -1068,13 +994,7 @@ class ScannIPIndexer:
         if not os.path.isdir(path) or not os.path.exists(p):
             raise ops.NativeError(f"{path} holds no ScannIPIndexer archive ({os.path.basename(p)}): an index serialized by scann "
                                   "cannot be read, build the index again with index()")
-        with open(p, "rb") as f:
-            head = f.read(4)
-        z = np.load(p, allow_pickle=False) if head[:2] == b"PK" else None
-        if z is None or "magic" not in z.files or str(z["magic"]) != _SCANN_MAGIC or int(z["format"]) != _SCANN_FORMAT:
-            raise ops.NativeError(f"{p} is not a ScannIPIndexer file of format {_SCANN_FORMAT}")
-        if int(z["token_dim"]) != self.token_dim or z["centroids"].shape[1] != self.E_pad:
-            raise ops.NativeError(f"{p} holds {int(z['token_dim'])}-dim vectors, the config says {self.token_dim}")
+        z = self._read_archive(p, "a ScannIPIndexer", _SCANN_MAGIC, _SCANN_FORMAT, "centroids")
         n, nlist = z["vectors"].shape[0], z["centroids"].shape[0]
         lb = z["list_begin"]
         if (z["codes"].shape != (n, self.E_pad // 4) or z["codes"].dtype != np.uint8 or z["vectors"].dtype != np.float16
