@@ -398,11 +398,8 @@ __global__ void __launch_bounds__(64) drmm_generic_kernel(const DrmmArgs a) {
 
 template <typename Kern>
 int launch(Kern kern, DrmmArgs a, int lds, hipStream_t stream, const char* what) {
-  int64_t waves = (int64_t)kCUs * 4;   // one wavefront per SIMD: the fp32 MFMA pipe is the co-limiter (as kernel pooling)
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
-  hipLaunchKernelGGL(kern, dim3((unsigned)waves), dim3(64), (size_t)lds, stream, a);
+  const unsigned waves = split_pairs(a, (int64_t)kCUs * 4);   // one wavefront per SIMD: the fp32 MFMA pipe is the co-limiter (as kernel pooling)
+  hipLaunchKernelGGL(kern, dim3(waves), dim3(64), (size_t)lds, stream, a);
   return check_launch(what);
 }
 

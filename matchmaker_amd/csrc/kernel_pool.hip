@@ -1236,21 +1236,15 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
 #endif
   constexpr int NBUF = TKL ? MM_TKL_NBUF : 3;
   const int lds = NBUF * kSliceBytes + 128 + (W ? 128 * ((a.D + 31) >> 5) : 0);
-  int64_t waves = (int64_t)kCUs * (TKL ? MM_TKL_WPC : MM_KP_WPC);  // one wavefront per SIMD: the fp32 MFMA pipe is the co-limiter
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
-  const dim3 grid((unsigned)waves, (unsigned)(a.n_md > 0 ? a.n_mblk : 1)), block(64);
+  const unsigned waves = split_pairs(a, (int64_t)kCUs * (TKL ? MM_TKL_WPC : MM_KP_WPC));  // one wavefront per SIMD: the fp32 MFMA pipe is the co-limiter
+  const dim3 grid(waves, (unsigned)(a.n_md > 0 ? a.n_mblk : 1)), block(64);
   // MM_KP_F32MFMA=1 selects the exact-f32 MFMA kernel (A/B runs, tools/bench_kernel_pool.py);
   // the default is the split-bf16 kernel (same numerics class, 4x less matrix-pipe time)
   if (env().kp_f32mfma && !W && !a.pair_q && a.n_md == 0) {
-    if (a.E == 100)
-      hipLaunchKernelGGL((kernel_pool_stream_kernel<1, K, NBUF, true, TKL>), grid, block, lds, stream, a);
-    else if (a.E == 200)
-      hipLaunchKernelGGL((kernel_pool_stream_kernel<2, K, NBUF, true, TKL>), grid, block, lds, stream, a);
-    else
-      hipLaunchKernelGGL((kernel_pool_stream_kernel<3, K, NBUF, true, TKL>), grid, block, lds, stream, a);
-    return check_launch("kernel_pool_stream_kernel");
+    return with_ns(a.E, [&](auto ns) {
+      hipLaunchKernelGGL((kernel_pool_stream_kernel<MM_V(ns), K, NBUF, true, TKL>), grid, block, lds, stream, a);
+      return check_launch("kernel_pool_stream_kernel");
+    });
   }
   // No non-temporal hint on these K-sliced streams: the 400-B row pieces of neighbouring slices share cache
   // lines, and with `nt` the shared lines came from HBM twice (FETCH_SIZE 1.22 x the padded bytes, 1.08 x without).
@@ -1260,21 +1254,15 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
     if (a.cos_out && env().tkl_stage1_ksplit && tkl_stage1_ksplit_supported(a.Q, a.E)) return tkl_stage1_ksplit_launch(a, stream);
     if (a.cos_out && !env().tkl_stage1_slices && tkl_stage1_rows_supported(a.Q, a.E)) return tkl_stage1_rows_launch(a, stream);
     if (a.cos_out) {
-      if (a.E == 100)
-        hipLaunchKernelGGL((tkl_stage1_run_kernel<1, K, NBUF, false, true>), grid, block, lds, stream, a);
-      else if (a.E == 200)
-        hipLaunchKernelGGL((tkl_stage1_run_kernel<2, K, NBUF, false, true>), grid, block, lds, stream, a);
-      else
-        hipLaunchKernelGGL((tkl_stage1_run_kernel<3, K, NBUF, false, true>), grid, block, lds, stream, a);
-      return check_launch("tkl_stage1_run_kernel<cos>");
+      return with_ns(a.E, [&](auto ns) {
+        hipLaunchKernelGGL((tkl_stage1_run_kernel<MM_V(ns), K, NBUF, false, true>), grid, block, lds, stream, a);
+        return check_launch("tkl_stage1_run_kernel<cos>");
+      });
     }
-    if (a.E == 100)
-      hipLaunchKernelGGL((tkl_stage1_run_kernel<1, K, NBUF, false, false>), grid, block, lds, stream, a);
-    else if (a.E == 200)
-      hipLaunchKernelGGL((tkl_stage1_run_kernel<2, K, NBUF, false, false>), grid, block, lds, stream, a);
-    else
-      hipLaunchKernelGGL((tkl_stage1_run_kernel<3, K, NBUF, false, false>), grid, block, lds, stream, a);
-    return check_launch("tkl_stage1_run_kernel");
+    return with_ns(a.E, [&](auto ns) {
+      hipLaunchKernelGGL((tkl_stage1_run_kernel<MM_V(ns), K, NBUF, false, false>), grid, block, lds, stream, a);
+      return check_launch("tkl_stage1_run_kernel");
+    });
   } else {
     if constexpr (!W) {
       // fewer pairs than half the wavefront slots (eval.py-sized calls): two wavefronts per pair
@@ -1283,31 +1271,22 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
         b.pairs_per_wave = 1;
         const int lds2 = 2 * (NBUF * kSliceBytes + 128);
         const dim3 grid2((unsigned)a.n_pairs), block2(128);
-        if (a.E == 100) {
-          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<1, K, NBUF, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-          hipLaunchKernelGGL((kernel_pool_split_kernel<1, K, NBUF, false, false, false, 2>), grid2, block2, lds2, stream, b);
-        } else if (a.E == 200) {
-          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<2, K, NBUF, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-          hipLaunchKernelGGL((kernel_pool_split_kernel<2, K, NBUF, false, false, false, 2>), grid2, block2, lds2, stream, b);
-        } else {
-          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<3, K, NBUF, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-          hipLaunchKernelGGL((kernel_pool_split_kernel<3, K, NBUF, false, false, false, 2>), grid2, block2, lds2, stream, b);
-        }
-        return check_launch("kernel_pool_split_kernel<2 wavefronts per pair>");
+        return with_ns(a.E, [&](auto ns) {
+          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
+          hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, false, 2>), grid2, block2, lds2, stream, b);
+          return check_launch("kernel_pool_split_kernel<2 wavefronts per pair>");
+        });
       }
     }
     if (a.fdm) return set_error(MM_ELAUNCH, "kernel_pool: float masks were left to a kernel that does not read them (internal)");
-    if (a.E == 100)
-      hipLaunchKernelGGL((kernel_pool_split_kernel<1, K, NBUF, false, false, W>), grid, block, lds, stream, a);
-    else if (a.E == 200)
-      hipLaunchKernelGGL((kernel_pool_split_kernel<2, K, NBUF, false, false, W>), grid, block, lds, stream, a);
-    else
-      hipLaunchKernelGGL((kernel_pool_split_kernel<3, K, NBUF, false, false, W>), grid, block, lds, stream, a);
-    return check_launch("kernel_pool_split_kernel");
+    return with_ns(a.E, [&](auto ns) {
+      hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, W>), grid, block, lds, stream, a);
+      return check_launch("kernel_pool_split_kernel");
+    });
   }
 }
 
-bool kp_stream_supported(int Q, int E) { return Q <= 32 && (E == 100 || E == 200 || E == 300); }
+bool kp_stream_supported(int Q, int E) { return Q <= 32 && kp_stream_width(E); }
 
 // the cosine hand-off exists on the grouped-run kernel only (the exact-f32 A/B kernel and the generic kernel emit pair sums)
 bool tkl_cos_supported(int Q, int E) { return !env().kp_generic && !env().kp_f32mfma && !env().tkl_pairsums && kp_stream_supported(Q, E); }
@@ -1333,7 +1312,7 @@ template <int K>
 static int launch_k(const KpArgs& a0, hipStream_t stream) {
   KpArgs a = a0;
   const bool force_generic = env().kp_generic != 0;
-  const bool stream_ok = !force_generic && a.Q <= 32 && (a.E == 100 || a.E == 200 || a.E == 300);
+  const bool stream_ok = !force_generic && kp_stream_supported(a.Q, a.E);
   if (!force_generic && !stream_ok && kp128_supported(a.Q, a.D, a.E, a.dw != nullptr)) return kp128_launch(a, stream);
   if (a.dw) {  // gated (TK-Sparse); the gate vector of a document sits in LDS: D <= 4096 on the streaming path (LDS stays under 64 KB)
     if (stream_ok && a.D <= 4096) return launch_stream<K, false, true>(a, stream);
@@ -1394,17 +1373,16 @@ extern "C" int mm_kernel_pool_ex_fwd2(const void* q, const void* d, const void* 
   a.Q = Q; a.D = D; a.E = E; a.K = K;
   a.d_doc_rows = D; a.d_row0 = 0;
   a.dw = d_gate; a.clamp_min = clamp_min; a.pair_q = pair_query;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
+  WsCursor ws(workspace, workspace_bytes);
   // eval.py-sized calls of TK at E = 100n with float masks: the two-wavefronts-per-pair kernel reads the masks itself
   // (one launch instead of two: the call is bound by the host, ~4 us per launch)
   const bool inline_masks = K == 11 && !d_gate && q_mask_kind == MM_MASK_F32 && d_mask_kind == MM_MASK_F32 && q_mask && d_mask &&
-                            Q <= 32 && D > 32 && D <= 256 && (E == 100 || E == 200 || E == 300) && n_pairs * 2 <= (int64_t)kCUs * 4 &&
+                            Q <= 32 && D > 32 && D <= 256 && kp_stream_width(E) && n_pairs * 2 <= (int64_t)kCUs * 4 &&
                             !env().kp_generic && !env().kp_f32mfma;
   if (inline_masks) {
     a.fqm = (const float*)q_mask;
     a.fdm = (const float*)d_mask;
-  } else if (int e = resolve_mask_pair(q_mask, q_mask_kind, q_rows, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) {
+  } else if (int e = resolve_mask_pair(q_mask, q_mask_kind, q_rows, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) {
     return e;
   }
   if (K == 11) return launch_k<11>(a, stream);
@@ -1463,13 +1441,12 @@ extern "C" int mm_kernel_pool_multi_fwd(const void* const* q_list, int n_q, cons
   a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w;
   a.n_pairs = n_pairs; a.ppq = pairs_per_query; a.Q = Q; a.D = D; a.E = E; a.K = K;
   a.d_doc_rows = D; a.d_row0 = 0; a.clamp_min = clamp_min;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
+  WsCursor ws(workspace, workspace_bytes);
   const int64_t q_rows = (n_pairs + pairs_per_query - 1) / pairs_per_query;
-  if (int e = resolve_mask_pair(q_mask, q_mask_kind, q_rows, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+  if (int e = resolve_mask_pair(q_mask, q_mask_kind, q_rows, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   const size_t need = (size_t)a.n_mblk * (size_t)n_pairs * 4;
-  if (!ws || left < need) return set_error(MM_EWORKSPACE, "kernel_pool_multi: workspace needs %zu more bytes", need);
-  float* partial = (float*)ws;
+  if (!ws.p || ws.left < need) return set_error(MM_EWORKSPACE, "kernel_pool_multi: workspace needs %zu more bytes", need);
+  float* partial = (float*)ws.p;
   a.out = partial;
   if (int e = launch_k<11>(a, stream)) return e;
   hipLaunchKernelGGL(kp_sum_blocks_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, stream, partial, n_pairs, a.n_mblk, out);

@@ -21,6 +21,7 @@
 // kernel pairs (wave 0: kernels 0-5, wave 1: 6-10) so that both matrix pipes and both VALUs stay busy.
 #include "mm_internal.h"
 #include "kp_device.h"
+#include "maxsim_device.h"
 
 namespace mm {
 
@@ -68,25 +69,10 @@ __host__ __device__ constexpr int kp128_lds_fixed(int KS, int nbuf = kS128Nbuf) 
   return KS * (nbuf * kS128Bytes + 128) + (KS == 2 ? kXchgBytes : 0);
 }
 
-// MaxSim epilogue (MX): running maximum per accumulator register with ColBERT's -1000 sentinel for masked rows
-// (colbert.py:68-75), as maxsim.hip's block_max / finish_pair
-__device__ __forceinline__ void mx_block(float (&m)[16], const f32x16& acc, uint32_t ex, uint32_t va, float fill, int h) {
-  if (va == 0xffffffffu) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) m[i] = fmaxf(m[i], acc[i]);
-  } else {
-    const uint32_t exs = ex >> (4 * h), vas = va >> (4 * h);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int bit = rowof(i);
-      const float v = ((vas >> bit) & 1u) ? acc[i] : (((exs >> bit) & 1u) ? -1000.0f : fill);
-      m[i] = fmaxf(m[i], v);
-    }
-  }
-}
-
 // MX: 0 = kernel pooling; 1 = fp32 MaxSim with the two-term split (4 MFMAs per K step); 2 = fp32 MaxSim with the
 // three-term split x = hi + lo + c (6 MFMAs: + c.hi and hi.c; operand error 2^-25, i.e. fp32-class scores)
+// The MaxSim epilogue is the running maximum with ColBERT's -1000 sentinel for masked rows (colbert.py:68-75): block_max of
+// maxsim_device.h.
 // OCC = 2 (round 5): TWO wavefronts per SIMD, each with a ring of two slices (16.5 KiB of LDS: eight single-wave workgroups per
 // CU) and at most 256 registers.  For SHORT documents — IDCM's ck-small sampler: 64-token passages, at most two blocks per
 // pair — a lone wavefront per SIMD spends more cycles between the blocks (scalar length / mask lookups with their waits, the
@@ -319,7 +305,7 @@ __global__ void __launch_bounds__(64 * KS * MW, OCC) kernel_pool_split128_kernel
         const int rem = len - 32 * t;
         const uint32_t ex = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
         const uint32_t va = a.dm.bits ? (sload_u32(a.dm.bits, pair * nblk_tot + t) & ex) : ex;
-        mx_block(mrun, acc, ex, va, fill, h);
+        block_max(mrun, acc, ex, va, fill, h);
         continue;
       }
       ss += __shfl_xor(ss, 32, 64);
@@ -343,7 +329,7 @@ __global__ void __launch_bounds__(64 * KS * MW, OCC) kernel_pool_split128_kernel
           const int rem = len - 32 * t;
           const uint32_t ex = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
           const uint32_t va = a.dm.bits ? (sload_u32(a.dm.bits, pair * nblk_tot + t) & ex) : ex;
-          mx_block(mrun, acc, ex, va, fill, h);
+          block_max(mrun, acc, ex, va, fill, h);
         }
         continue;
       }
@@ -836,11 +822,7 @@ int kp128_maxsim_f32(const float* q, const float* d, PackedMask qm, PackedMask d
   // profiles/r05_experiments/maxsim_fp32_occ.txt).  MM_KP128_OCC=1 forces the old form.
   const bool occ2 = nsl <= 2 && env().kp128_occ != 1 && n_pairs >= (int64_t)kCUs * 8 * 4;
   const int lds = occ2 ? kp128_lds_fixed(1, 2) : kp128_lds_fixed(ks);
-  int64_t groups = occ2 ? (int64_t)kCUs * 8 : (int64_t)kCUs * 4 / ks;
-  if (groups > a.n_pairs) groups = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + groups - 1) / groups;
-  groups = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
-  const dim3 grid((unsigned)groups);
+  const dim3 grid(split_pairs(a, occ2 ? (int64_t)kCUs * 8 : (int64_t)kCUs * 4 / ks));
   const bool x3 = env().maxsim_f32_terms == 3;  // MM_MAXSIM_F32_TERMS=2: two-term split (operand error 2^-17) for A/B runs
 #define MM_MX(NSL, KS) (x3 ? launch_mx<NSL, KS, 2>(a, grid, lds, stream) : launch_mx<NSL, KS, 1>(a, grid, lds, stream))
   if (occ2) {
@@ -895,10 +877,7 @@ int kp128_launch(const KpArgs& a0, hipStream_t stream) {
     int64_t groups = (int64_t)kCUs * 4 / a.n_md;
     const bool xcd = !env().kp_multi_2d && groups >= 8;   // XCD-grouped ids (see the kernel); MM_KP_MULTI_2D=1: consecutive ids (A/B runs)
     if (xcd) groups = groups / 8 * 8;                     // whole groups of 8 ranges, all resident at once (one wavefront per SIMD)
-    if (groups < 1) groups = 1;
-    if (groups > a.n_pairs) groups = a.n_pairs;
-    a.pairs_per_wave = (a.n_pairs + groups - 1) / groups;
-    groups = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+    groups = split_pairs(a, groups);
     a.m_flat = xcd ? 3 : 0;
     a.m_ranges = (int)groups;
     const dim3 grid((unsigned)((xcd ? (groups + 7) / 8 * 8 : groups) * a.n_md));
@@ -911,11 +890,7 @@ int kp128_launch(const KpArgs& a0, hipStream_t stream) {
     // CU: 8 (two per SIMD) in workgroups of n_mq -> 2 x 3 for Conv-KNRM's three n-gram widths
     const int n_mq = a.n_mblk / a.n_md;
     const int lds2 = n_mq * kp128_lds_fixed(1, 2);
-    int64_t groups = (int64_t)kCUs * (8 / n_mq) / a.n_md;
-    if (groups < 1) groups = 1;
-    if (groups > a.n_pairs) groups = a.n_pairs;
-    a.pairs_per_wave = (a.n_pairs + groups - 1) / groups;
-    groups = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+    const int64_t groups = split_pairs(a, (int64_t)kCUs * (8 / n_mq) / a.n_md);
     a.m_flat = 2;
     a.m_ranges = (int)groups;
     const dim3 grid((unsigned)(groups * a.n_md));
@@ -929,21 +904,13 @@ int kp128_launch(const KpArgs& a0, hipStream_t stream) {
   }
   if (occ2) {
     const int lds2 = kp128_lds_fixed(1, 2);
-    int64_t groups = (int64_t)kCUs * per_cu;
-    if (groups > a.n_pairs) groups = a.n_pairs;
-    a.pairs_per_wave = (a.n_pairs + groups - 1) / groups;
-    groups = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
-    const dim3 grid = flat_grid(groups);
+    const dim3 grid = flat_grid(split_pairs(a, (int64_t)kCUs * per_cu));
     if (nsl == 1) hipLaunchKernelGGL((kernel_pool_split128_kernel<1, 11, false, 1, 0, 2>), grid, dim3(64), lds2, stream, a);
     else hipLaunchKernelGGL((kernel_pool_split128_kernel<2, 11, false, 1, 0, 2>), grid, dim3(64), lds2, stream, a);
     return check_launch("kernel_pool_split128_kernel<two wavefronts per SIMD>");
   }
   const int lds = kp128_lds_fixed(ks) + (gated ? ks * 128 * ((a.D + 31) >> 5) : 0);
-  int64_t groups = (int64_t)kCUs * 4 / ks;  // one wave per SIMD either way
-  if (groups > a.n_pairs) groups = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + groups - 1) / groups;
-  groups = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
-  const dim3 grid = flat_grid(groups);
+  const dim3 grid = flat_grid(split_pairs(a, (int64_t)kCUs * 4 / ks));  // one wave per SIMD either way
 #define MM_KP128(NSL, KS) \
   return gated ? launch128<NSL, true, KS>(a, grid, lds, stream) : launch128<NSL, false, KS>(a, grid, lds, stream)
   switch (nsl) {

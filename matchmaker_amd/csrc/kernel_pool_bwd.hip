@@ -718,22 +718,21 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
     a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
     a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
     a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-    char* ws = (char*)workspace;
-    size_t left = workspace ? workspace_bytes : 0;
-    if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+    WsCursor ws(workspace, workspace_bytes);
+    if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
     float* pkq_ws = nullptr;
     if (!pooled) {
-      const size_t skip = (size_t)(-(intptr_t)ws) & 255, need = kp_bwd_split_ws_bytes(n_pairs, Q, K);
-      if (left < skip + need)
+      const size_t skip = (size_t)(-(intptr_t)ws.p) & 255, need = kp_bwd_split_ws_bytes(n_pairs, Q, K);
+      if (ws.left < skip + need)
         return set_error(MM_EINVAL, "kernel_pool_bwd: workspace too small for the pooled sums (%zu bytes left, %zu needed; "
-                                    "mm_kernel_pool_bwd_workspace_bytes)", left, skip + need);
-      pkq_ws = (float*)(ws + skip);
-      ws += skip + need;
-      left -= skip + need;
+                                    "mm_kernel_pool_bwd_workspace_bytes)", ws.left, skip + need);
+      pkq_ws = (float*)(ws.p + skip);
+      ws.p += skip + need;
+      ws.left -= skip + need;
     }
-    const size_t pskip = (size_t)(-(intptr_t)ws) & 255;
-    float* part = left > pskip ? (float*)(ws + pskip) : nullptr;
-    return kp_bwd_split_launch(a, pooled, pkq_ws, part, part ? left - pskip : 0, stream);
+    const size_t pskip = (size_t)(-(intptr_t)ws.p) & 255;
+    float* part = ws.left > pskip ? (float*)(ws.p + pskip) : nullptr;
+    return kp_bwd_split_launch(a, pooled, pkq_ws, part, part ? ws.left - pskip : 0, stream);
   }
   // the exact-f32 tiled kernel whenever its tiles fit; the per-element kernel otherwise
   {
@@ -746,9 +745,8 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
       a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
       a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
       a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-      char* ws = (char*)workspace;
-      size_t left = workspace ? workspace_bytes : 0;
-      if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+      WsCursor ws(workspace, workspace_bytes);
+      if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
       auto go = [&](auto kern) {
         if (tl > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl);
         hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3((unsigned)nthr), tl, stream, a, Dpad);
@@ -779,9 +777,8 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
   a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
   a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
   a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kernel_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kernel_pool_bwd_kernel, dim3((unsigned)n_pairs), dim3(256), lds, stream, a, DT);

@@ -113,15 +113,6 @@ __device__ __forceinline__ KpArgs kp_block_args(const KpArgs& a, int wq = 0) {
   return b;
 }
 
-__device__ __forceinline__ constexpr int rowof(int i) { return (i & 3) + 8 * (i >> 2); }
-
-__device__ __forceinline__ uint32_t sload_u32(const void* base, int64_t idx) {
-  uint32_t v;
-  const uint32_t* p = (const uint32_t*)base + idx;
-  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p));
-  return v;
-}
-
 // RBF constants in exp2 form: exp(-(c-mu)^2/(2 s^2)) = exp2((c-mu)^2 * c2), c2 = -log2(e)/(2 s^2)
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 

@@ -874,51 +874,47 @@ static int validate_flags(int flags) {
 // Measured on MI355X (profiles/r01_sweep_nbuf_wpc.log): one wavefront per SIMD (4 / CU) with a
 // 2-slot ring is the fastest point (6.9 TB/s); more wavefronts or deeper rings only add contention.
 // (defaults and their environment overrides: EnvCfg in mm_internal.h)
+static int64_t stream_max_waves(int lds) {      // launch_stream's wavefronts with `lds` bytes of ring each
+  int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : (160 * 1024) / lds;
+  if (wpc > 16) wpc = 16;
+  return (int64_t)kCUs * wpc;
+}
+
 template <int DT, int NBUF, bool NT, int NSL, bool RAG, int NQT = 1>
 static int launch_stream(const MaxsimArgs& a0, hipStream_t stream) {
   MaxsimArgs a = a0;
   const int lds = NBUF * kBlkBytes;
-  int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : (160 * 1024) / lds;
-  if (wpc > 16) wpc = 16;
-  int64_t waves = (int64_t)kCUs * wpc;
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const unsigned waves = split_pairs(a, stream_max_waves(lds));
   if constexpr (NQT == 2 && !RAG) {      // (a query of <= 32 tokens in this layout is the pair kernel's, maxsim_pair.hip)
     if (a.dm64) {
       if (a.pairs_per_wave != 1) return set_error(MM_EINVAL, "maxsim: in-kernel masks need one pair per wavefront");
       if (a.n_pairs * 2 <= (int64_t)kCUs * 4 && a.D > 32 && !env().maxsim_no_wpp2) {
-        hipLaunchKernelGGL((maxsim_stream_wpp2_kernel<DT, NBUF, NT, NSL, NQT>), dim3((unsigned)waves), dim3(128), 2 * lds + NQT * 256, stream, a);
+        hipLaunchKernelGGL((maxsim_stream_wpp2_kernel<DT, NBUF, NT, NSL, NQT>), dim3(waves), dim3(128), 2 * lds + NQT * 256, stream, a);
         return check_launch("maxsim_stream_wpp2_kernel");
       }
-      hipLaunchKernelGGL((maxsim_stream_kernel<DT, NBUF, NT, NSL, RAG, NQT, 0, true>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+      hipLaunchKernelGGL((maxsim_stream_kernel<DT, NBUF, NT, NSL, RAG, NQT, 0, true>), dim3(waves), dim3(64), lds, stream, a);
       return check_launch("maxsim_stream_kernel<in-kernel masks>");
     }
   }
-  hipLaunchKernelGGL((maxsim_stream_kernel<DT, NBUF, NT, NSL, RAG, NQT>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+  hipLaunchKernelGGL((maxsim_stream_kernel<DT, NBUF, NT, NSL, RAG, NQT>), dim3(waves), dim3(64), lds, stream, a);
   return check_launch("maxsim_stream_kernel");
 }
 
 // every wavefront of launch_stream<.., NBUF = 2, ..> gets at most one pair
 static bool stream_one_pair_per_wave(int64_t n_pairs) {
-  int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : (160 * 1024) / (2 * kBlkBytes);
-  if (wpc > 16) wpc = 16;
-  return n_pairs <= (int64_t)kCUs * wpc;
+  return wave_split(n_pairs, stream_max_waves(2 * kBlkBytes)).pairs_per_wave == 1;
 }
 
 template <int DT, int NSL>
 static int launch_stream_inb(const MaxsimArgs& a0, hipStream_t stream) {
   MaxsimArgs a = a0;
   const int lds = 2 * kBlkBytes;
-  int64_t waves = (int64_t)kCUs * 4;
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const unsigned waves = split_pairs(a, (int64_t)kCUs * 4);
   if (a.Q > 32) {
-    hipLaunchKernelGGL((maxsim_stream_kernel<DT, 2, false, NSL, false, 2, true>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL((maxsim_stream_kernel<DT, 2, false, NSL, false, 2, true>), dim3(waves), dim3(64), lds, stream, a);
     return check_launch("maxsim_stream_kernel<all pairs>");
   }
-  hipLaunchKernelGGL((maxsim_stream_kernel<DT, 2, false, NSL, false, 1, true>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+  hipLaunchKernelGGL((maxsim_stream_kernel<DT, 2, false, NSL, false, 1, true>), dim3(waves), dim3(64), lds, stream, a);
   return check_launch("maxsim_stream_kernel<all pairs>");
 }
 
@@ -928,18 +924,11 @@ template <int DT, int NSL, int NQT>
 static int launch_stream_inb_tiled(const MaxsimArgs& a0, hipStream_t stream) {
   MaxsimArgs a = a0;
   const int lds = 2 * kBlkBytes;
-  const int64_t G = (a.inb_bq + NQT - 1) / NQT;
-  const int64_t target = (int64_t)kCUs * 4 / 8;                 // wavefronts per XCD
-  a.inb_gw = (int)(G < target ? G : target);                    // query-group lanes per (XCD, slice)
-  int64_t T = target / a.inb_gw;                                 // document slices per XCD
-  const int64_t max_t = (a.inb_bd + 7) / 8;                      // >= 1 document per slice
-  if (T > max_t) T = max_t;
-  if (T < 1) T = 1;
-  a.inb_t = (int)T;
-  // the kernel indexes a wavefront's (query group, document) items with 32 bits
-  if (((G + a.inb_gw - 1) / a.inb_gw) * ((a.inb_bd + 8 * T - 1) / (8 * T) + 1) >= (1LL << 31)) return kNotLaunched;
-  const int64_t waves = 8 * T * a.inb_gw;
-  hipLaunchKernelGGL((maxsim_allpairs_tiled_kernel<DT, NSL, NQT>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+  const AllPairsMap m = all_pairs_tiled(a.inb_bq, a.inb_bd, NQT);
+  if (!m.grid) return kNotLaunched;
+  a.inb_gw = m.gw;
+  a.inb_t = m.t;
+  hipLaunchKernelGGL((maxsim_allpairs_tiled_kernel<DT, NSL, NQT>), dim3((unsigned)m.grid), dim3(64), lds, stream, a);
   return check_launch("maxsim_allpairs_tiled_kernel");
 }
 
@@ -948,16 +937,11 @@ template <int DT, int NSL, int NQT>
 static int launch_inb_wg(const MaxsimArgs& a0, hipStream_t stream) {
   MaxsimArgs a = a0;
   const int lds = (NSL == 1 ? 3 : 4) * kBlkBytes;
-  const int64_t G = (a.inb_bq + 4 * NQT - 1) / (4 * NQT);
-  const int64_t target = (int64_t)kCUs * 2 / 8;                  // workgroups per XCD
-  a.inb_gw = (int)(G < target ? G : target);
-  int64_t T = target / a.inb_gw;
-  const int64_t max_t = (a.inb_bd + 7) / 8;
-  if (T > max_t) T = max_t;
-  if (T < 1) T = 1;
-  a.inb_t = (int)T;
-  if (a.inb_bd >= (1LL << 31)) return kNotLaunched;
-  hipLaunchKernelGGL((maxsim_allpairs_wg_kernel<DT, NSL, NQT>), dim3((unsigned)(8 * T * a.inb_gw)), dim3(256), lds, stream, a);
+  const AllPairsMap m = all_pairs_ring(a.inb_bq, a.inb_bd, NQT);
+  if (!m.grid) return kNotLaunched;
+  a.inb_gw = m.gw;
+  a.inb_t = m.t;
+  hipLaunchKernelGGL((maxsim_allpairs_wg_kernel<DT, NSL, NQT>), dim3((unsigned)m.grid), dim3(256), lds, stream, a);
   return check_launch("maxsim_allpairs_wg_kernel");
 }
 
@@ -977,13 +961,7 @@ static int launch_stream_inb_cfg(const MaxsimArgs& a, hipStream_t stream) {
     if (a.E == 256) e = launch_stream_inb_tiled<DT, 2, 2>(a, stream);
     if (e != kNotLaunched) return e;      // index range too large for the tiled map: one query per wavefront below
   }
-  switch (a.E / 128) {
-    case 1: return launch_stream_inb<DT, 1>(a, stream);
-    case 2: return launch_stream_inb<DT, 2>(a, stream);
-    case 3: return launch_stream_inb<DT, 3>(a, stream);
-    case 4: return launch_stream_inb<DT, 4>(a, stream);
-    default: return launch_stream_inb<DT, 6>(a, stream);
-  }
+  return with_nsl(a.E, [&](auto nsl) { return launch_stream_inb<DT, MM_V(nsl)>(a, stream); });
 }
 
 template <int DT, int NSL, bool RAG>
@@ -1000,27 +978,22 @@ static int launch_stream_nsl(const MaxsimArgs& a, hipStream_t stream) {
   return launch_stream<DT, 2, true, NSL, RAG>(a, stream);
 }
 
-template <int DT, bool RAG>
-static int launch_stream_cfg(const MaxsimArgs& a, hipStream_t stream) {
-  switch (a.E / 128) {
-    case 1: return launch_stream_nsl<DT, 1, RAG>(a, stream);
-    case 2: return launch_stream_nsl<DT, 2, RAG>(a, stream);
-    case 3: return launch_stream_nsl<DT, 3, RAG>(a, stream);
-    case 4: return launch_stream_nsl<DT, 4, RAG>(a, stream);
-    default: return launch_stream_nsl<DT, 6, RAG>(a, stream);
-  }
+template <bool RAG>
+static int launch_stream_cfg(const MaxsimArgs& a, int dtype, hipStream_t stream) {
+  return with_dtype16(dtype, [&](auto dt) {
+    return with_nsl(a.E, [&](auto nsl) { return launch_stream_nsl<MM_V(dt), MM_V(nsl), RAG>(a, stream); });
+  });
 }
+
+// the streaming kernels take 16-bit vectors, up to two query tiles and the widths of stream_width
+static bool stream_ok(int dtype, int Q, int E) { return !env().maxsim_generic && dtype != MM_F32 && Q <= 64 && stream_width(E); }
 
 static int launch_generic(const MaxsimArgs& a, int dtype, hipStream_t stream) {
   if (a.n_pairs > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "maxsim: more than 2^31-1 pairs in one generic launch");
-  const dim3 grid((unsigned)a.n_pairs), block(64);
-  if (dtype == MM_F32)
-    hipLaunchKernelGGL(maxsim_generic_kernel<MM_F32>, grid, block, 0, stream, a);
-  else if (dtype == MM_F16)
-    hipLaunchKernelGGL(maxsim_generic_kernel<MM_F16>, grid, block, 0, stream, a);
-  else
-    hipLaunchKernelGGL(maxsim_generic_kernel<MM_BF16>, grid, block, 0, stream, a);
-  return check_launch("maxsim_generic_kernel");
+  return with_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(maxsim_generic_kernel<MM_V(dt)>, dim3((unsigned)a.n_pairs), dim3(64), 0, stream, a);
+    return check_launch("maxsim_generic_kernel");
+  });
 }
 
 }  // namespace mm
@@ -1047,8 +1020,7 @@ extern "C" int mm_maxsim_fwd(const void* q, const void* d, const void* q_mask, i
   MaxsimArgs a{};
   a.q = q; a.d = d; a.out = out; a.n_pairs = n_pairs; a.ppq = pairs_per_query; a.inb_bd = 0; a.inb_bug = 0;
   a.Q = Q; a.D = D; a.E = E; a.rnd = flags;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
+  WsCursor ws(workspace, workspace_bytes);
   // the reference's batch layout (one query tile per pair, eval.py:108): the pair kernel; HF int64 masks are read by
   // the kernel itself (no pack pass) when their rows are 16-byte multiples
   const bool pair_kernel = pairs_per_query == 1 && !env().maxsim_generic && maxsim_pair_supported(Q, E, dtype);
@@ -1058,19 +1030,18 @@ extern "C" int mm_maxsim_fwd(const void* q, const void* d, const void* q_mask, i
     a.dm64 = (const int64_t*)d_mask;
     return maxsim_pair_launch(a, dtype, true, stream);
   }
-  const bool stream_ok = !env().maxsim_generic && dtype != MM_F32 && Q <= 64 &&
-                         (E == 128 || E == 256 || E == 384 || E == 512 || E == 768);
+  const bool streams = stream_ok(dtype, Q, E);
   // a long query (ColBERT's [MASK] augmentation: 30 + 8 tokens) in a call small enough that every wavefront scores one
   // pair: the two-tile streaming kernel reads the int64 masks itself, one launch per call
-  if (stream_ok && !pair_kernel && Q > 32 && D <= 256 && q_mask_kind == MM_MASK_I64 && d_mask_kind == MM_MASK_I64 && q_mask &&
+  if (streams && !pair_kernel && Q > 32 && D <= 256 && q_mask_kind == MM_MASK_I64 && d_mask_kind == MM_MASK_I64 && q_mask &&
       d_mask && !env().maxsim_no_inline_masks && stream_one_pair_per_wave(n_pairs)) {
     a.qm64 = (const int64_t*)q_mask;
     a.dm64 = (const int64_t*)d_mask;
-    return dtype == MM_BF16 ? launch_stream_cfg<MM_BF16, false>(a, stream) : launch_stream_cfg<MM_F16, false>(a, stream);
+    return launch_stream_cfg<false>(a, dtype, stream);
   }
-  if (int e = resolve_mask_pair(q_mask, q_mask_kind, nq, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+  if (int e = resolve_mask_pair(q_mask, q_mask_kind, nq, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   if (pair_kernel) return maxsim_pair_launch(a, dtype, false, stream);
-  if (stream_ok) return dtype == MM_BF16 ? launch_stream_cfg<MM_BF16, false>(a, stream) : launch_stream_cfg<MM_F16, false>(a, stream);
+  if (streams) return launch_stream_cfg<false>(a, dtype, stream);
   // fp32 token vectors (ColBERT run with use_fp16 = False): the split-bf16 streaming kernel of kernel_pool128.hip
   // with the MaxSim epilogue
   if (!env().maxsim_generic && dtype == MM_F32 && kp128_maxsim_supported(Q, E)) {
@@ -1099,17 +1070,14 @@ extern "C" int mm_maxsim_inbatch_fwd(const void* q, const void* d, const void* q
   MaxsimArgs a{};
   a.q = q; a.d = d; a.out = out; a.n_pairs = Bq * Bd; a.ppq = 1; a.inb_bd = Bd; a.inb_bq = Bq; a.inb_bug = bug_compatible ? 1 : 0;
   a.Q = Q; a.D = D; a.E = E; a.rnd = flags;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask(q_mask, q_mask_kind, Bq, Q, &ws, &left, stream, &a.qm)) return e;
-  if (int e = resolve_mask(d_mask, d_mask_kind, Bd, D, &ws, &left, stream, &a.dm)) return e;
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask(q_mask, q_mask_kind, Bq, Q, ws, stream, &a.qm)) return e;
+  if (int e = resolve_mask(d_mask, d_mask_kind, Bd, D, ws, stream, &a.dm)) return e;
   // the streaming kernel in all-pairs mode (query tile resident, documents of one query consecutive: no non-temporal
   // hint, every document is read once per query); Q > 64 and fp32 stay on the one-wavefront-per-pair kernel
-  const bool stream_ok = !env().maxsim_generic && dtype != MM_F32 && Q <= 64 &&
-                         (E == 128 || E == 256 || E == 384 || E == 512 || E == 768);
-  if (stream_ok) {
+  if (stream_ok(dtype, Q, E)) {
     a.ppq = Bd;
-    return dtype == MM_BF16 ? launch_stream_inb_cfg<MM_BF16>(a, stream) : launch_stream_inb_cfg<MM_F16>(a, stream);
+    return with_dtype16(dtype, [&](auto dt) { return launch_stream_inb_cfg<MM_V(dt)>(a, stream); });
   }
   return launch_generic(a, dtype, stream);
 }
@@ -1133,12 +1101,9 @@ extern "C" int mm_maxsim_ragged_fwd(const void* q, const void* tokens, const int
   MaxsimArgs a{};
   a.q = q; a.d = tokens; a.out = out; a.n_pairs = n_pairs; a.ppq = pairs_per_query;
   a.Q = Q; a.D = 32; a.E = E; a.rag_begin = doc_begin; a.rag_end = doc_end; a.rnd = flags;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask(q_mask, q_mask_kind, nq, Q, &ws, &left, stream, &a.qm)) return e;
-  const bool stream_ok = !env().maxsim_generic && dtype != MM_F32 && Q <= 64 &&
-                         (E == 128 || E == 256 || E == 384 || E == 512 || E == 768);
-  if (stream_ok) return dtype == MM_BF16 ? launch_stream_cfg<MM_BF16, true>(a, stream) : launch_stream_cfg<MM_F16, true>(a, stream);
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask(q_mask, q_mask_kind, nq, Q, ws, stream, &a.qm)) return e;
+  if (stream_ok(dtype, Q, E)) return launch_stream_cfg<true>(a, dtype, stream);
   return launch_generic(a, dtype, stream);
 }
 
@@ -1147,14 +1112,12 @@ extern "C" int mm_hbm_stream_probe(const void* src, int64_t bytes, int nt, void*
   if (!src || bytes <= 0 || (bytes % kBlkBytes) || ((uintptr_t)src & 15))
     return set_error(MM_EINVAL, "hbm_stream_probe: need a 16-byte aligned buffer of a multiple of %d bytes", kBlkBytes);
   const int64_t n_blocks = bytes / kBlkBytes;
-  int64_t waves = (int64_t)kCUs * 4;
-  if (waves > n_blocks) waves = n_blocks;
-  const int64_t per = (n_blocks + waves - 1) / waves;
-  waves = (n_blocks + per - 1) / per;
+  const WaveSplit s = wave_split(n_blocks, (int64_t)kCUs * 4);
+  const int64_t per = s.pairs_per_wave;
   if (nt)
-    hipLaunchKernelGGL(hbm_stream_probe_kernel<true>, dim3((unsigned)waves), dim3(64), 2 * kBlkBytes, stream, (const char*)src, n_blocks, per, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(hbm_stream_probe_kernel<true>, dim3((unsigned)s.grid), dim3(64), 2 * kBlkBytes, stream, (const char*)src, n_blocks, per, (uint32_t*)nullptr);
   else
-    hipLaunchKernelGGL(hbm_stream_probe_kernel<false>, dim3((unsigned)waves), dim3(64), 2 * kBlkBytes, stream, (const char*)src, n_blocks, per, (uint32_t*)nullptr);
+    hipLaunchKernelGGL(hbm_stream_probe_kernel<false>, dim3((unsigned)s.grid), dim3(64), 2 * kBlkBytes, stream, (const char*)src, n_blocks, per, (uint32_t*)nullptr);
   return check_launch("hbm_stream_probe_kernel");
 }
 
@@ -1175,24 +1138,19 @@ extern "C" int mm_maxsim_bwd(const void* q, const void* d, const void* q_mask, i
   if ((size_t)Q * 4 > 48 * 1024) return set_error(MM_EUNSUPPORTED, "maxsim_bwd: Q = %d query tokens exceed the arg-max table", Q);
   MaxsimBwdArgs a{};
   a.q = q; a.d = d; a.go = grad_out; a.gq = grad_q; a.gd = grad_d; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, &ws, &left, stream)) return e;
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   if (((uintptr_t)grad_q | (uintptr_t)grad_d) & 15) return set_error(MM_EINVAL, "maxsim_bwd: gradients must be 16-byte aligned");
   const dim3 grid((unsigned)n_pairs), block(256);
   size_t lds = (size_t)Q * 4 + 2 * 128 * 4;
   const size_t mask_bytes = (size_t)D * ((Q + 31) / 32) * 4;
   a.row_masks = lds + mask_bytes <= 60 * 1024;
   if (a.row_masks) lds += mask_bytes;
-  if (dtype == MM_F32)
-    hipLaunchKernelGGL((maxsim_bwd_kernel<MM_F32, MM_F32>), grid, block, lds, stream, a);
-  else if (dtype == MM_F16 && grad_dtype == MM_F32)
-    hipLaunchKernelGGL((maxsim_bwd_kernel<MM_F16, MM_F32>), grid, block, lds, stream, a);
-  else if (dtype == MM_F16)
-    hipLaunchKernelGGL((maxsim_bwd_kernel<MM_F16, MM_F16>), grid, block, lds, stream, a);
-  else if (grad_dtype == MM_F32)
-    hipLaunchKernelGGL((maxsim_bwd_kernel<MM_BF16, MM_F32>), grid, block, lds, stream, a);
-  else
-    hipLaunchKernelGGL((maxsim_bwd_kernel<MM_BF16, MM_BF16>), grid, block, lds, stream, a);
-  return check_launch("maxsim_bwd_kernel");
+  return with_dtype(dtype, [&](auto dt) {      // gradients in fp32 or in the vectors' own type
+    if (grad_dtype == MM_F32)
+      hipLaunchKernelGGL((maxsim_bwd_kernel<MM_V(dt), MM_F32>), grid, block, lds, stream, a);
+    else
+      hipLaunchKernelGGL((maxsim_bwd_kernel<MM_V(dt), MM_V(dt)>), grid, block, lds, stream, a);
+    return check_launch("maxsim_bwd_kernel");
+  });
 }

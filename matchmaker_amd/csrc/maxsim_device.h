@@ -1,4 +1,5 @@
-// Device helpers shared by the MaxSim translation units (maxsim.hip, maxsim_pair.hip).  gfx950 only.
+// Device helpers shared by the MaxSim translation units (maxsim.hip, maxsim_pair.hip, maxsim_fp8.hip) and the fp32 MaxSim
+// epilogue of kernel_pool128.hip.  gfx950 only.
 #pragma once
 #include "mm_internal.h"
 
@@ -48,9 +49,6 @@ struct Mfma32x16<MM_F16> {
   }
 };
 
-// C/D layout of the 32x32 MFMA: lane l holds column (l & 31), rows rowof(i) + 4*(l >> 5).
-__device__ __forceinline__ constexpr int rowof(int i) { return (i & 3) + 8 * (i >> 2); }
-
 // Running max of one 32-row document block into m[16].
 //   ex: bit r set <=> row r of the block is below the document's effective length
 //   va: bit r set <=> row r is a real token (va is a subset of ex)
@@ -69,17 +67,6 @@ __device__ __forceinline__ void block_max(float (&m)[16], const f32x16& acc, uin
       m[i] = fmaxf(m[i], v);
     }
   }
-}
-
-// Wave-uniform 32-bit load through the scalar cache.  The compiler cannot use s_load here on its
-// own (the asm "memory" clobbers of the LDS-DMA pipeline make every global look written), and a
-// vector load would make it wait vmcnt(0) and drain the D stream once per pair.  Lengths / mask
-// words are never written by these kernels, so the (non-coherent) scalar cache is safe.
-__device__ __forceinline__ uint32_t sload_u32(const void* base, int64_t idx) {
-  uint32_t v;
-  const uint32_t* p = (const uint32_t*)base + idx;
-  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p));
-  return v;
 }
 
 __device__ __forceinline__ int64_t sload_i64(const int64_t* base, int64_t idx) {
@@ -204,73 +191,25 @@ constexpr int kBlkBytes = 32 * 256;  // 32 document tokens x 128 dims x 2 B
 template <bool NT>
 __device__ __forceinline__ void issue_block(const char* gbase, const uint32_t (&voff)[8], uint32_t lds_dst) {
   uint32_t keep;
+#define MM_BLK_LD(N, NTS) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #N ", %9" NTS "\n\t"
+#define MM_BLK_NEXT "s_add_u32 m0, m0, 0x400\n\t"
+#define MM_ISSUE_BLOCK(NTS)                                                                                               \
+  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %10\n\t" MM_BLK_LD(1, NTS) MM_BLK_NEXT             \
+                   MM_BLK_LD(2, NTS) MM_BLK_NEXT MM_BLK_LD(3, NTS) MM_BLK_NEXT MM_BLK_LD(4, NTS) MM_BLK_NEXT             \
+                       MM_BLK_LD(5, NTS) MM_BLK_NEXT MM_BLK_LD(6, NTS) MM_BLK_NEXT MM_BLK_LD(7, NTS) MM_BLK_NEXT         \
+                           MM_BLK_LD(8, NTS) "s_mov_b32 m0, %0"                                                          \
+               : "=&s"(keep)                                                                                             \
+               : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]),       \
+                 "v"(voff[7]), "s"(gbase), "s"(lds_dst)                                                                  \
+               : "memory", "scc")
   if (NT) {
-    asm volatile(
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %10\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %5, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %6, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %7, %9 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %8, %9 nt\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]),
-          "v"(voff[7]), "s"(gbase), "s"(lds_dst)
-        : "memory", "scc");
+    MM_ISSUE_BLOCK(" nt");
   } else {
-    asm volatile(
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %10\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %5, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %6, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %7, %9\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %8, %9\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]),
-          "v"(voff[7]), "s"(gbase), "s"(lds_dst)
-        : "memory", "scc");
+    MM_ISSUE_BLOCK("");
   }
+#undef MM_ISSUE_BLOCK
+#undef MM_BLK_NEXT
+#undef MM_BLK_LD
 }
 
 // Wait until at most `younger` blocks (8 LDS-DMA each) issued after the one we need are pending.

@@ -474,31 +474,20 @@ static int launch_fp8_stream(const Fp8Args& a0, hipStream_t stream) {
   static_assert(Fp8Slot<32>::kNbuf * Fp8Slot<32>::kBytes <= lds + 512, "ring sizes");
   int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : 4;
   if (wpc > 8) wpc = 8;
-  int64_t waves = (int64_t)kCUs * wpc;
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const unsigned waves = split_pairs(a, (int64_t)kCUs * wpc);
   if (a.Q > 32) {
     constexpr int ROWS = NSL >= 6 ? 32 : 64;
-    hipLaunchKernelGGL((maxsim_fp8_stream_kernel<DT, NSL, 2, ROWS>), dim3((unsigned)waves), dim3(64),
+    hipLaunchKernelGGL((maxsim_fp8_stream_kernel<DT, NSL, 2, ROWS>), dim3(waves), dim3(64),
                        Fp8Slot<ROWS>::kNbuf * Fp8Slot<ROWS>::kBytes, stream, a);
   } else {
-    hipLaunchKernelGGL((maxsim_fp8_stream_kernel<DT, NSL, 1, 64>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL((maxsim_fp8_stream_kernel<DT, NSL, 1, 64>), dim3(waves), dim3(64), lds, stream, a);
   }
   return check_launch("maxsim_fp8_stream_kernel");
 }
 
 template <int DT>
 static int launch_fp8(const Fp8Args& a, bool stream_ok, hipStream_t stream) {
-  if (stream_ok) {
-    switch (a.E / 128) {
-      case 1: return launch_fp8_stream<DT, 1>(a, stream);
-      case 2: return launch_fp8_stream<DT, 2>(a, stream);
-      case 3: return launch_fp8_stream<DT, 3>(a, stream);
-      case 4: return launch_fp8_stream<DT, 4>(a, stream);
-      default: return launch_fp8_stream<DT, 6>(a, stream);
-    }
-  }
+  if (stream_ok) return with_nsl(a.E, [&](auto nsl) { return launch_fp8_stream<DT, MM_V(nsl)>(a, stream); });
   if (a.n_pairs > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "maxsim_ragged_fp8: more than 2^31-1 pairs in one plain launch");
   hipLaunchKernelGGL(maxsim_fp8_plain_kernel<DT>, dim3((unsigned)a.n_pairs), dim3(64), 0, stream, a);
   return check_launch("maxsim_fp8_plain_kernel");
@@ -553,9 +542,8 @@ extern "C" int mm_maxsim_ragged_fp8_fwd(const void* q, const uint8_t* codes, con
   Fp8Args a{};
   a.q = q; a.codes = codes; a.scales = scales; a.out = out; a.n_pairs = n_pairs; a.ppq = pairs_per_query;
   a.begin = doc_begin; a.end = doc_end; a.Q = Q; a.E = E; a.rnd = flags;
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask(q_mask, q_mask_kind, nq, Q, &ws, &left, stream, &a.qm)) return e;
-  const bool stream_ok = !env().maxsim_generic && Q <= 64 && (E == 128 || E == 256 || E == 384 || E == 512 || E == 768);
-  return q_dtype == MM_BF16 ? launch_fp8<MM_BF16>(a, stream_ok, stream) : launch_fp8<MM_F16>(a, stream_ok, stream);
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask(q_mask, q_mask_kind, nq, Q, ws, stream, &a.qm)) return e;
+  const bool stream_ok = !env().maxsim_generic && Q <= 64 && stream_width(E);
+  return with_dtype16(q_dtype, [&](auto dt) { return launch_fp8<MM_V(dt)>(a, stream_ok, stream); });
 }

@@ -363,14 +363,13 @@ extern "C" int mm_maxsim_inbatch_bwd(const void* q, const void* d, const void* q
   const int64_t lim = 0x7fffffffLL;
   if ((Bq * Bd + 3) / 4 > lim || (Bq * Q * (E / per16) + 255) / 256 > lim || Bd * a.ntile > lim)
     return set_error(MM_EUNSUPPORTED, "maxsim_inbatch_bwd: %lld x %lld pairs exceed one launch", (long long)Bq, (long long)Bd);
-  char* ws = (char*)workspace;
-  size_t left = workspace ? workspace_bytes : 0;
-  if (int e = resolve_mask(q_mask, q_mask_kind, Bq, Q, &ws, &left, stream, &a.qm)) return e;
-  if (int e = resolve_mask(d_mask, d_mask_kind, Bd, D, &ws, &left, stream, &a.dm)) return e;
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask(q_mask, q_mask_kind, Bq, Q, ws, stream, &a.qm)) return e;
+  if (int e = resolve_mask(d_mask, d_mask_kind, Bd, D, ws, stream, &a.dm)) return e;
   const size_t tb = table_bytes(Bq, Bd, Q);
-  if (!ws || left < tb)
-    return set_error(MM_EWORKSPACE, "maxsim_inbatch_bwd: workspace too small for the arg-max table: need %zu more bytes, have %zu", tb, left);
-  a.tab = (int16_t*)ws;
+  if (!ws.p || ws.left < tb)
+    return set_error(MM_EWORKSPACE, "maxsim_inbatch_bwd: workspace too small for the arg-max table: need %zu more bytes, have %zu", tb, ws.left);
+  a.tab = (int16_t*)ws.p;
   if (dtype == MM_F32) return launch<MM_F32, MM_F32>(a, stream);
   if (dtype == MM_F16) return grad_dtype == MM_F32 ? launch<MM_F16, MM_F32>(a, stream) : launch<MM_F16, MM_F16>(a, stream);
   return grad_dtype == MM_F32 ? launch<MM_BF16, MM_F32>(a, stream) : launch<MM_BF16, MM_BF16>(a, stream);

@@ -311,9 +311,7 @@ static int launch_pair_batched(const MaxsimArgs& a0, const MaxsimBatches& bt, in
   const int lds = nbuf * kBlkBytes + (I64 ? kMaskRaw + kMaskEntries * kMaskEntry * 4 : 0);
   int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : 4;
   if (wpc > 8) wpc = 8;
-  int64_t waves = (int64_t)kCUs * wpc;                   // over ALL batches
-  if (waves > total) waves = total;
-  a.pairs_per_wave = (total + waves - 1) / waves;
+  a.pairs_per_wave = wave_split(total, (int64_t)kCUs * wpc).pairs_per_wave;      // over ALL batches
   const int64_t gx = (max_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
   const dim3 grid((unsigned)gx, (unsigned)nb);
   if (nbuf == 3)
@@ -325,13 +323,7 @@ static int launch_pair_batched(const MaxsimArgs& a0, const MaxsimBatches& bt, in
 
 template <int DT, bool I64>
 static int launch_pair_batched_e(const MaxsimArgs& a, const MaxsimBatches& bt, int nb, int64_t total, int64_t max_pairs, hipStream_t stream) {
-  switch (a.E / 128) {
-    case 1: return launch_pair_batched<DT, 1, I64>(a, bt, nb, total, max_pairs, stream);
-    case 2: return launch_pair_batched<DT, 2, I64>(a, bt, nb, total, max_pairs, stream);
-    case 3: return launch_pair_batched<DT, 3, I64>(a, bt, nb, total, max_pairs, stream);
-    case 4: return launch_pair_batched<DT, 4, I64>(a, bt, nb, total, max_pairs, stream);
-    default: return launch_pair_batched<DT, 6, I64>(a, bt, nb, total, max_pairs, stream);
-  }
+  return with_nsl(a.E, [&](auto nsl) { return launch_pair_batched<DT, MM_V(nsl), I64>(a, bt, nb, total, max_pairs, stream); });
 }
 
 template <int DT, int NSL, bool I64>
@@ -341,30 +333,21 @@ static int launch_pair(const MaxsimArgs& a0, hipStream_t stream) {
   const int lds = nbuf * kBlkBytes + (I64 ? kMaskRaw + kMaskEntries * kMaskEntry * 4 : 0);
   int wpc = env().maxsim_wpc > 0 ? env().maxsim_wpc : 4;
   if (wpc > 8) wpc = 8;
-  int64_t waves = (int64_t)kCUs * wpc;
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const unsigned waves = split_pairs(a, (int64_t)kCUs * wpc);
   if (nbuf == 3)
-    hipLaunchKernelGGL((maxsim_pair_kernel<DT, 3, NSL, I64>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL((maxsim_pair_kernel<DT, 3, NSL, I64>), dim3(waves), dim3(64), lds, stream, a);
   else
-    hipLaunchKernelGGL((maxsim_pair_kernel<DT, 2, NSL, I64>), dim3((unsigned)waves), dim3(64), lds, stream, a);
+    hipLaunchKernelGGL((maxsim_pair_kernel<DT, 2, NSL, I64>), dim3(waves), dim3(64), lds, stream, a);
   return check_launch("maxsim_pair_kernel");
 }
 
 template <int DT, bool I64>
 static int launch_pair_e(const MaxsimArgs& a, hipStream_t stream) {
-  switch (a.E / 128) {
-    case 1: return launch_pair<DT, 1, I64>(a, stream);
-    case 2: return launch_pair<DT, 2, I64>(a, stream);
-    case 3: return launch_pair<DT, 3, I64>(a, stream);
-    case 4: return launch_pair<DT, 4, I64>(a, stream);
-    default: return launch_pair<DT, 6, I64>(a, stream);
-  }
+  return with_nsl(a.E, [&](auto nsl) { return launch_pair<DT, MM_V(nsl), I64>(a, stream); });
 }
 
 bool maxsim_pair_supported(int Q, int E, int dtype) {
-  return dtype != MM_F32 && Q <= 32 && (E == 128 || E == 256 || E == 384 || E == 512 || E == 768);
+  return dtype != MM_F32 && Q <= 32 && stream_width(E);
 }
 
 // int64 masks straight from the tokenizer: rows must be 16-byte multiples (even Q / D) for the LDS-DMA fetch

@@ -4,8 +4,10 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <type_traits>
 
 #include "../../include/mm_native.h"
+#include "launch_geometry.h"
 
 namespace mm {
 
@@ -15,8 +17,7 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-constexpr int kWave = 64;
-constexpr int kCUs = 256;  // MI355X
+constexpr int kWave = 64;   // (kCUs: launch_geometry.h)
 
 int set_error(int code, const char* fmt, ...);
 
@@ -83,6 +84,50 @@ int resolve_mask(const void* mask, int kind, int64_t rows, int L, char** ws, siz
 // Both masks of a call: two dense masks of one element type are packed by ONE launch (else one resolve_mask each).
 int resolve_mask_pair(const void* m0, int kind0, int64_t rows0, int L0, PackedMask* out0, const void* m1, int kind1,
                       int64_t rows1, int L1, PackedMask* out1, char** ws, size_t* ws_left, hipStream_t stream);
+// ... the same two on an entry point's workspace cursor
+inline int resolve_mask(const void* mask, int kind, int64_t rows, int L, WsCursor& ws, hipStream_t stream, PackedMask* out) {
+  return resolve_mask(mask, kind, rows, L, &ws.p, &ws.left, stream, out);
+}
+inline int resolve_mask_pair(const void* m0, int kind0, int64_t rows0, int L0, PackedMask* out0, const void* m1, int kind1,
+                             int64_t rows1, int L1, PackedMask* out1, WsCursor& ws, hipStream_t stream) {
+  return resolve_mask_pair(m0, kind0, rows0, L0, out0, m1, kind1, rows1, L1, out1, &ws.p, &ws.left, stream);
+}
+
+// Run-time value -> template argument: f is a generic lambda, called with std::integral_constant<int, V> (`decltype(v)::value`
+// is the template argument inside it).  One instantiation per value named here, as the ladders these replace had.
+template <int V>
+using Int = std::integral_constant<int, V>;
+#define MM_V(v) decltype(v)::value
+template <class F>
+inline int with_nsl(int E, F&& f) {          // NSL = E / 128 of a stream_width(E): 1, 2, 3, 4, 6
+  switch (E / 128) {
+    case 1: return f(Int<1>{});
+    case 2: return f(Int<2>{});
+    case 3: return f(Int<3>{});
+    case 4: return f(Int<4>{});
+    default: return f(Int<6>{});
+  }
+}
+template <class F>
+inline int with_ns(int E, F&& f) {           // NS = E / 100 of a kp_stream_width(E): 1, 2, 3
+  return E == 100 ? f(Int<1>{}) : E == 200 ? f(Int<2>{}) : f(Int<3>{});
+}
+template <class F>
+inline int with_dtype16(int dtype, F&& f) {   // MM_BF16, else MM_F16
+  return dtype == MM_BF16 ? f(Int<MM_BF16>{}) : f(Int<MM_F16>{});
+}
+template <class F>
+inline int with_dtype(int dtype, F&& f) {     // ... and MM_F32
+  return dtype == MM_F32 ? f(Int<MM_F32>{}) : with_dtype16(dtype, f);
+}
+
+// a.pairs_per_wave and the grid of a launch whose wavefronts (or workgroups) each take a range of the a.n_pairs pairs
+template <class Args>
+inline unsigned split_pairs(Args& a, int64_t max_waves) {
+  const WaveSplit s = wave_split(a.n_pairs, max_waves);
+  a.pairs_per_wave = s.pairs_per_wave;
+  return (unsigned)s.grid;
+}
 
 constexpr int kK = 11;   // RBF kernels of TK / TKL (tk.yaml:18-19, tkl.yaml)
 constexpr int kKC = 12;  // K + the non-zero-count channel of TKL's pair sums
@@ -193,6 +238,20 @@ __device__ __forceinline__ void wait_vm(int n) {
     case 62: asm volatile("s_waitcnt vmcnt(62)" ::: "memory"); break;
     default: break;
   }
+}
+
+// C/D layout of the 32x32 MFMA: lane l holds column (l & 31), rows rowof(i) + 4*(l >> 5).
+__device__ __forceinline__ constexpr int rowof(int i) { return (i & 3) + 8 * (i >> 2); }
+
+// Wave-uniform 32-bit load through the scalar cache.  The compiler cannot use s_load here on its
+// own (the asm "memory" clobbers of the LDS-DMA pipeline make every global look written), and a
+// vector load would make it wait vmcnt(0) and drain the D stream once per pair.  Lengths / mask
+// words are never written by these kernels, so the (non-coherent) scalar cache is safe.
+__device__ __forceinline__ uint32_t sload_u32(const void* base, int64_t idx) {
+  uint32_t v;
+  const uint32_t* p = (const uint32_t*)base + idx;
+  asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(p));
+  return v;
 }
 
 __device__ __forceinline__ float neg_inf() { return -__builtin_huge_valf(); }

@@ -391,24 +391,17 @@ __global__ void __launch_bounds__(128, 2) tkl_stage1_ksplit_kernel(const KpArgs 
 #endif
 }
 
-bool tkl_stage1_ksplit_supported(int Q, int E) { return Q <= 32 && (E == 100 || E == 200 || E == 300); }
+bool tkl_stage1_ksplit_supported(int Q, int E) { return Q <= 32 && kp_stream_width(E); }
 
 int tkl_stage1_ksplit_launch(const KpArgs& a0, hipStream_t stream) {
   KpArgs a = a0;
-  int64_t wgs = (int64_t)kCUs * 4;
-  if (wgs > a.n_pairs) wgs = a.n_pairs;
-  if (wgs <= 0) return MM_OK;
-  a.pairs_per_wave = (a.n_pairs + wgs - 1) / wgs;
-  wgs = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const dim3 grid(split_pairs(a, (int64_t)kCUs * 4)), block(128);
+  if (grid.x == 0) return MM_OK;
   const int lds = kRing * 8 * a.E * 4 + 2 * 2 * 2 * 16 * 16 + 2 * 16 * 4;
-  const dim3 grid((unsigned)wgs), block(128);
-  if (a.E == 100)
-    hipLaunchKernelGGL((tkl_stage1_ksplit_kernel<100>), grid, block, lds, stream, a);
-  else if (a.E == 200)
-    hipLaunchKernelGGL((tkl_stage1_ksplit_kernel<200>), grid, block, lds, stream, a);
-  else
-    hipLaunchKernelGGL((tkl_stage1_ksplit_kernel<300>), grid, block, lds, stream, a);
-  return check_launch("tkl_stage1_ksplit_kernel");
+  return with_ns(a.E, [&](auto ns) {
+    hipLaunchKernelGGL((tkl_stage1_ksplit_kernel<100 * MM_V(ns)>), grid, block, lds, stream, a);
+    return check_launch("tkl_stage1_ksplit_kernel");
+  });
 }
 
 }  // namespace mm

@@ -455,27 +455,20 @@ __global__ void __launch_bounds__(64) tkl_stage1_rows_kernel(const KpArgs a) {
 #endif
 }
 
-bool tkl_stage1_rows_supported(int Q, int E) { return Q <= 32 && (E == 100 || E == 200 || E == 300); }
+bool tkl_stage1_rows_supported(int Q, int E) { return Q <= 32 && kp_stream_width(E); }
 
 int tkl_stage1_rows_launch(const KpArgs& a0, hipStream_t stream) {
   KpArgs a = a0;
 #ifndef MM_S1_WAVES_PER_CU   // A/B builds only: 4 are resident (LDS); more give shorter ranges handed out as wavefronts retire
 #define MM_S1_WAVES_PER_CU 4
 #endif
-  int64_t waves = (int64_t)kCUs * MM_S1_WAVES_PER_CU;
-  if (waves > a.n_pairs) waves = a.n_pairs;
-  if (waves <= 0) return MM_OK;
-  a.pairs_per_wave = (a.n_pairs + waves - 1) / waves;
-  waves = (a.n_pairs + a.pairs_per_wave - 1) / a.pairs_per_wave;
+  const dim3 grid(split_pairs(a, (int64_t)kCUs * MM_S1_WAVES_PER_CU)), block(64);
+  if (grid.x == 0) return MM_OK;
   const int lds = kRing * kUnitRows * a.E * 4 + 128 + 64 + 16 * 32 * 4;
-  const dim3 grid((unsigned)waves), block(64);
-  if (a.E == 100)
-    hipLaunchKernelGGL((tkl_stage1_rows_kernel<4>), grid, block, lds, stream, a);
-  else if (a.E == 200)
-    hipLaunchKernelGGL((tkl_stage1_rows_kernel<7>), grid, block, lds, stream, a);
-  else
-    hipLaunchKernelGGL((tkl_stage1_rows_kernel<10>), grid, block, lds, stream, a);
-  return check_launch("tkl_stage1_rows_kernel");
+  return with_ns(a.E, [&](auto ns) {       // 4, 7, 10 k-steps of 32 for E = 100, 200, 300
+    hipLaunchKernelGGL((tkl_stage1_rows_kernel<3 * MM_V(ns) + 1>), grid, block, lds, stream, a);
+    return check_launch("tkl_stage1_rows_kernel");
+  });
 }
 
 }  // namespace mm

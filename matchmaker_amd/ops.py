@@ -72,16 +72,27 @@ def _k_range(op: str, k: int, nprobe: int):
         raise NativeError(f"{op}: k={k} / nprobe={nprobe} outside 1 .. 4096")
 
 
+def _pad_last(t: torch.Tensor, mult: int) -> torch.Tensor:
+    E = t.shape[-1]
+    return t if E % mult == 0 else torch.nn.functional.pad(t, (0, mult - E % mult))
+
+
 def _pad_rows(q: torch.Tensor, d: torch.Tensor, mult: int):
     """Token rows must be 16-byte multiples for the native loads.  Zero columns change neither dot products nor
     norms, so other widths (KNRM on 50-d GloVe, colbert_compression_dim 100, ...) are padded up — a copy, taken
     only for such widths.  Returns (q, d, padded E)."""
-    E = q.shape[-1]
-    Ep = (E + mult - 1) // mult * mult
-    if Ep == E:
-        return q, d, E
-    pad = (0, Ep - E)
-    return torch.nn.functional.pad(q, pad), torch.nn.functional.pad(d, pad), Ep
+    q, d = _pad_last(q, mult), _pad_last(d, mult)
+    return q, d, q.shape[-1]
+
+
+def _pad16(q: torch.Tensor, d: torch.Tensor):
+    """_pad_rows to 16 bytes of the tensors' own element type."""
+    return _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
+
+
+def _trim(g: Optional[torch.Tensor], E0: int) -> Optional[torch.Tensor]:
+    """A gradient computed at the padded width, back at the E0 columns the caller passed (a copy, taken only when padded)."""
+    return g if g is None or g.shape[-1] == E0 else g[..., :E0].contiguous()
 
 
 def _mask(m: Optional[torch.Tensor], rows: int, L: int, name: str):
@@ -188,11 +199,78 @@ def _vec(t: torch.Tensor) -> torch.Tensor:
     `kernel_alpha_scaler` [1,1,K], `kernel_bin_weights.weight` [1,K]) cost no dispatch per call."""
     if t.dtype is torch.float32 and t.is_contiguous():
         return t
+    return _flat32(t)
+
+
+def _flat32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().reshape(-1).to(torch.float32).contiguous()
 
 
 def _flags(sim_round: bool, sum_round: bool) -> int:
     return (_lib.SIM_ROUND if sim_round else 0) | (_lib.SUM_ROUND if sum_round else 0)
+
+
+def _call(dev, fn, args, size_fn=None, key=(), cached=False):
+    """The native call every scoring operator ends with: fn(*args, workspace pointer or None, workspace bytes, stream) under
+    the device guard, on the current stream (its handle is read once), then the check of the return code under fn's name.
+    size_fn(*key), key = integers, gives the workspace size (None: the entry point needs no workspace); cached: the workspace
+    is the per-stream buffer of _workspace (host-bound calls), else a fresh allocation (large ones, which the cache would hold
+    on to)."""
+    with _on(dev):
+        st = _stream(dev)
+        wsb = _ws_bytes(size_fn, *key) if size_fn is not None else 0
+        if cached:
+            ws = _workspace(dev, wsb, st)
+        else:
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+        rc = fn(*args, ws.data_ptr() if ws is not None else None, wsb, st)
+    _lib.check(rc, fn.__name__)
+
+
+# ---- checks the scoring operators share -------------------------------------------------------------------------------
+def _same_dtype(q: torch.Tensor, d: torch.Tensor):
+    if q.dtype != d.dtype:
+        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
+
+
+def _same_width(E: int, E2: int):
+    if E != E2:
+        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+
+
+def _per_query(nq: int, B: int, pairs_per_query: int):
+    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
+        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+
+
+def _qd_shapes(q: torch.Tensor, d: torch.Tensor, pairs_per_query: int):
+    """q [n_queries, Q, E] against d [n_pairs, D, E], pairs_per_query pairs per query -> (nq, Q, E, B, D)."""
+    nq, Q, E = q.shape
+    B, D, E2 = d.shape
+    _same_width(E, E2)
+    _per_query(nq, B, pairs_per_query)
+    return nq, Q, E, B, D
+
+
+def _pair_per_row(op: str, q: torch.Tensor, d: torch.Tensor):
+    """The layout of the backwards: q [B, Q, E], d [B, D, E] -> (B, Q, D, E)."""
+    if q.shape[0] != d.shape[0] or q.shape[2] != d.shape[2]:
+        raise NativeError(f"{op} needs the pair-per-row layout: q {tuple(q.shape)} vs d {tuple(d.shape)}")
+    return q.shape[0], q.shape[1], d.shape[1], q.shape[2]
+
+
+def _grad_flat(grad_out: torch.Tensor, n: int, pairs: str) -> torch.Tensor:
+    go = _flat32(grad_out)
+    if go.numel() != n:
+        raise NativeError(f"grad_out has {go.numel()} elements for {pairs} pairs")
+    return go
+
+
+def _grad_dtype(op: str, grad_dtype: Optional[torch.dtype], q: torch.Tensor) -> torch.dtype:
+    gdt = torch.float32 if grad_dtype is None else grad_dtype
+    if gdt not in (torch.float32, q.dtype):
+        raise NativeError(f"{op}: gradients are float32 or {q.dtype}, not {gdt}")
+    return gdt
 
 
 def reference_rounding(q: torch.Tensor) -> "tuple[bool, bool]":
@@ -218,29 +296,18 @@ def maxsim(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor] = No
     Returns float32 [n_pairs] (with sum_round the values are exactly representable in the vectors' dtype)."""
     dev = _dev_check(q, d, q_mask, d_mask)
     q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != d.dtype:
-        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
-    nq, Q, E = q.shape
-    B, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    _same_dtype(q, d)
+    nq, Q, E, B, D = _qd_shapes(q, d, pairs_per_query)
     qm, qp, qk = _mask(q_mask, nq, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, B, D, "d_mask")
     L = _lib.lib()
     out = torch.empty(B, dtype=torch.float32, device=dev)
     if B == 0:
         return out
-    q, d, E = _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_maxsim_workspace_bytes, B, pairs_per_query, Q, D, qk, dk)
-        st = _stream(dev)
-        ws = _workspace(dev, wsb, st)
-        rc = L.mm_maxsim_fwd(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, out.data_ptr(), B, pairs_per_query,
-                             Q, D, E, _DT[q.dtype], (1 if sim_round else 0) | (2 if sum_round else 0),
-                             ws.data_ptr() if ws is not None else None, wsb, st)
-    _lib.check(rc, "mm_maxsim_fwd")
+    q, d, E = _pad16(q, d)
+    _call(dev, L.mm_maxsim_fwd, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, out.data_ptr(), B, pairs_per_query, Q, D, E,
+                                 _DT[q.dtype], _flags(sim_round, sum_round)),
+          L.mm_maxsim_workspace_bytes, (B, pairs_per_query, Q, D, qk, dk), cached=True)
     return out
 
 
@@ -295,7 +362,7 @@ def maxsim_batched(batches, sim_round: bool = False, sum_round: bool = False):
             part = recs[i:i + MAXSIM_MAX_BATCHES]
             arr = (_MaxsimBatch * len(part))(*part)
             rc = L.mm_maxsim_fwd_batched(ctypes.cast(arr, ctypes.c_void_p), len(part), kind, kind, Q, D, E, _DT[q0.dtype],
-                                         (1 if sim_round else 0) | (2 if sum_round else 0), st)
+                                         _flags(sim_round, sum_round), st)
             _lib.check(rc, "mm_maxsim_fwd_batched")
     return views
 
@@ -326,6 +393,27 @@ def _check_ranges(doc_begin: torch.Tensor, doc_end: torch.Tensor, n_rows: int):
                           + (f" ({bad} ranges have begin > end)" if bad else ""))
 
 
+def _maxsim_ragged(dev, fn, size_fn, q, store, n_rows, doc_begin, doc_end, q_mask, pairs_per_query, check_ranges, flags):
+    """What maxsim_ragged and maxsim_ragged_fp8 share once their store is validated: `store` = the store's tensors in the
+    order the entry point `fn` takes them, n_rows = its token rows."""
+    nq, Q, E = q.shape
+    B = doc_begin.numel()
+    if doc_end.numel() != B:
+        raise NativeError("doc_begin / doc_end must have one entry per pair")
+    _per_query(nq, B, pairs_per_query)
+    doc_begin = doc_begin.to(torch.int64).contiguous()
+    doc_end = doc_end.to(torch.int64).contiguous()
+    qm, qp, qk = _mask(q_mask, nq, Q, "q_mask")
+    out = torch.empty(B, dtype=torch.float32, device=dev)
+    if B == 0:
+        return out
+    if check_ranges:
+        _check_ranges(doc_begin, doc_end, n_rows)
+    _call(dev, fn, (q.data_ptr(), *[t.data_ptr() for t in store], doc_begin.data_ptr(), doc_end.data_ptr(), qp, qk,
+                    out.data_ptr(), B, pairs_per_query, Q, E, _DT[q.dtype], flags), size_fn, (B, pairs_per_query, Q, qk))
+    return out
+
+
 def maxsim_ragged(q: torch.Tensor, tokens: torch.Tensor, doc_begin: torch.Tensor, doc_end: torch.Tensor,
                   q_mask: Optional[torch.Tensor] = None, pairs_per_query: int = 1,
                   check_ranges: bool = True, sim_round: bool = False, sum_round: bool = False) -> torch.Tensor:
@@ -342,31 +430,10 @@ def maxsim_ragged(q: torch.Tensor, tokens: torch.Tensor, doc_begin: torch.Tensor
     if q.dtype != tokens.dtype:
         raise NativeError(f"q/tokens dtype mismatch: {q.dtype} vs {tokens.dtype} (convert the query to the store's dtype)")
     tokens = tokens.contiguous()
-    nq, Q, E = q.shape
-    if tokens.shape[1] != E:
-        raise NativeError(f"embedding dims differ: {E} vs {tokens.shape[1]}")
-    B = doc_begin.numel()
-    if doc_end.numel() != B:
-        raise NativeError("doc_begin / doc_end must have one entry per pair")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
-    doc_begin = doc_begin.to(torch.int64).contiguous()
-    doc_end = doc_end.to(torch.int64).contiguous()
-    qm, qp, qk = _mask(q_mask, nq, Q, "q_mask")
+    _same_width(q.shape[2], tokens.shape[1])
     L = _lib.lib()
-    out = torch.empty(B, dtype=torch.float32, device=dev)
-    if B == 0:
-        return out
-    if check_ranges:
-        _check_ranges(doc_begin, doc_end, tokens.shape[0])
-    with torch.cuda.device(dev):
-        wsb = L.mm_maxsim_ragged_workspace_bytes(B, pairs_per_query, Q, qk)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        rc = L.mm_maxsim_ragged_fwd(q.data_ptr(), tokens.data_ptr(), doc_begin.data_ptr(), doc_end.data_ptr(), qp, qk,
-                                    out.data_ptr(), B, pairs_per_query, Q, E, _DT[q.dtype], _flags(sim_round, sum_round),
-                                    ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-    _lib.check(rc, "mm_maxsim_ragged_fwd")
-    return out
+    return _maxsim_ragged(dev, L.mm_maxsim_ragged_fwd, L.mm_maxsim_ragged_workspace_bytes, q, (tokens,), tokens.shape[0],
+                          doc_begin, doc_end, q_mask, pairs_per_query, check_ranges, _flags(sim_round, sum_round))
 
 
 def fp8_quantize_rows(x: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
@@ -419,36 +486,14 @@ def maxsim_ragged_fp8(q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
     if scales.dtype != torch.float32 or tuple(scales.shape) != (T,):
         raise NativeError(f"maxsim_ragged_fp8: scales: expected [{T}] float32 (one per row of codes), got "
                           f"{tuple(scales.shape)} {scales.dtype}")
-    nq, Q, E = q.shape
-    if codes.shape[1] != E:
-        raise NativeError(f"embedding dims differ: {E} vs {codes.shape[1]}")
+    E = q.shape[2]
+    _same_width(E, codes.shape[1])
     if E % 16:
         raise NativeError(f"maxsim_ragged_fp8: E={E} is not a multiple of 16", _lib.MM_EUNSUPPORTED)
-    codes = codes.contiguous()
-    scales = scales.contiguous()
-    B = doc_begin.numel()
-    if doc_end.numel() != B:
-        raise NativeError("doc_begin / doc_end must have one entry per pair")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
-    doc_begin = doc_begin.to(torch.int64).contiguous()
-    doc_end = doc_end.to(torch.int64).contiguous()
-    qm, qp, qk = _mask(q_mask, nq, Q, "q_mask")
     L = _lib.lib()
-    out = torch.empty(B, dtype=torch.float32, device=dev)
-    if B == 0:
-        return out
-    if check_ranges:
-        _check_ranges(doc_begin, doc_end, T)
-    with torch.cuda.device(dev):
-        wsb = L.mm_maxsim_ragged_fp8_workspace_bytes(B, pairs_per_query, Q, qk)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        rc = L.mm_maxsim_ragged_fp8_fwd(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), doc_begin.data_ptr(),
-                                        doc_end.data_ptr(), qp, qk, out.data_ptr(), B, pairs_per_query, Q, E, _DT[q.dtype],
-                                        _flags(sim_round, sum_round), ws.data_ptr() if ws is not None else None, wsb,
-                                        _stream(dev))
-    _lib.check(rc, "mm_maxsim_ragged_fp8_fwd")
-    return out
+    return _maxsim_ragged(dev, L.mm_maxsim_ragged_fp8_fwd, L.mm_maxsim_ragged_fp8_workspace_bytes, q,
+                          (codes.contiguous(), scales.contiguous()), T, doc_begin, doc_end, q_mask, pairs_per_query,
+                          check_ranges, _flags(sim_round, sum_round))
 
 
 def maxsim_bwd(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor], d_mask: Optional[torch.Tensor],
@@ -458,37 +503,21 @@ def maxsim_bwd(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor],
     one launch, summed in fp32, rounded once); see mm_maxsim_bwd in include/mm_native.h."""
     dev = _dev_check(q, d, q_mask, d_mask, grad_out)
     q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != d.dtype:
-        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
-    B, Q, E = q.shape
-    B2, D, E2 = d.shape
-    if B != B2 or E != E2:
-        raise NativeError(f"maxsim_bwd needs the pair-per-row layout: q {tuple(q.shape)} vs d {tuple(d.shape)}")
-    go = grad_out.detach().reshape(-1).to(torch.float32).contiguous()
-    if go.numel() != B:
-        raise NativeError(f"grad_out has {go.numel()} elements for {B} pairs")
+    _same_dtype(q, d)
+    B, Q, D, E0 = _pair_per_row("maxsim_bwd", q, d)
+    go = _grad_flat(grad_out, B, f"{B}")
     qm, qp, qk = _mask(q_mask, B, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, B, D, "d_mask")
     L = _lib.lib()
-    E0 = E
-    q, d, E = _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
-    gdt = torch.float32 if grad_dtype is None else grad_dtype
-    if gdt not in (torch.float32, q.dtype):
-        raise NativeError(f"maxsim_bwd: gradients are float32 or {q.dtype}, not {gdt}")
+    q, d, E = _pad16(q, d)
+    gdt = _grad_dtype("maxsim_bwd", grad_dtype, q)
     gq = torch.empty((B, Q, E), dtype=gdt, device=dev)
     gd = torch.empty((B, D, E), dtype=gdt, device=dev)
     if B:
-        with _on(dev):
-            wsb = _ws_bytes(L.mm_maxsim_bwd_workspace_bytes, B, Q, D, qk, dk)
-            st = _stream(dev)
-            ws = _workspace(dev, wsb, st)
-            rc = L.mm_maxsim_bwd(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, go.data_ptr(), gq.data_ptr(),
-                                 gd.data_ptr(), _DT[gdt], B, Q, D, E, _DT[q.dtype], ws.data_ptr() if ws is not None else None,
-                                 wsb, st)
-        _lib.check(rc, "mm_maxsim_bwd")
-    if E != E0:
-        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
-    return gq, gd
+        _call(dev, L.mm_maxsim_bwd, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, go.data_ptr(), gq.data_ptr(), gd.data_ptr(),
+                                     _DT[gdt], B, Q, D, E, _DT[q.dtype]),
+              L.mm_maxsim_bwd_workspace_bytes, (B, Q, D, qk, dk), cached=True)
+    return _trim(gq, E0), _trim(gd, E0)
 
 
 def maxsim_inbatch(q: torch.Tensor, q_mask: Optional[torch.Tensor], d: torch.Tensor,
@@ -499,26 +528,20 @@ def maxsim_inbatch(q: torch.Tensor, q_mask: Optional[torch.Tensor], d: torch.Ten
     maxsim() (the dynamic teacher calls this on fp16 vectors outside autocast: both, dynamic_teacher.py:245-246)."""
     dev = _dev_check(q, d, q_mask, d_mask)
     q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != d.dtype:
-        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
+    _same_dtype(q, d)
     Bq, Q, E = q.shape
     Bd, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    _same_width(E, E2)
     qm, qp, qk = _mask(q_mask, Bq, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, Bd, D, "d_mask")
     L = _lib.lib()
     out = torch.empty((Bq, Bd), dtype=torch.float32, device=dev)
     if Bq == 0 or Bd == 0:
         return out
-    q, d, E = _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
-    with torch.cuda.device(dev):
-        wsb = L.mm_maxsim_inbatch_workspace_bytes(Bq, Bd, Q, D, qk, dk)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        rc = L.mm_maxsim_inbatch_fwd(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, out.data_ptr(), Bq, Bd, Q, D, E,
-                                     _DT[q.dtype], 1 if bug_compatible else 0, _flags(sim_round, sum_round),
-                                     ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-    _lib.check(rc, "mm_maxsim_inbatch_fwd")
+    q, d, E = _pad16(q, d)
+    _call(dev, L.mm_maxsim_inbatch_fwd, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, out.data_ptr(), Bq, Bd, Q, D, E,
+                                         _DT[q.dtype], 1 if bug_compatible else 0, _flags(sim_round, sum_round)),
+          L.mm_maxsim_inbatch_workspace_bytes, (Bq, Bd, Q, D, qk, dk))
     return out
 
 
@@ -532,45 +555,30 @@ def maxsim_inbatch_bwd(q: torch.Tensor, q_mask: Optional[torch.Tensor], d: torch
     in its place (a frozen encoder)."""
     dev = _dev_check(q, d, q_mask, d_mask, grad_out)
     q, d = _emb(q, "q"), _emb(d, "d")
-    if q.dtype != d.dtype:
-        raise NativeError(f"q/d dtype mismatch: {q.dtype} vs {d.dtype}")
-    Bq, Q, E = q.shape
+    _same_dtype(q, d)
+    Bq, Q, E0 = q.shape
     Bd, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    _same_width(E0, E2)
     if bug_compatible and Bq != Bd:
         raise NativeError(f"maxsim_inbatch_bwd: bug_compatible masking (colbert.py:158) requires Bq == Bd (got {Bq}, {Bd})",
                           _lib.MM_EINVAL)
-    go = grad_out.detach().reshape(-1).to(torch.float32).contiguous()
-    if go.numel() != Bq * Bd:
-        raise NativeError(f"grad_out has {go.numel()} elements for {Bq} x {Bd} pairs")
+    go = _grad_flat(grad_out, Bq * Bd, f"{Bq} x {Bd}")
     qm, qp, qk = _mask(q_mask, Bq, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, Bd, D, "d_mask")
     L = _lib.lib()
-    E0 = E
-    q, d, E = _pad_rows(q, d, 4 if q.dtype == torch.float32 else 8)
-    gdt = torch.float32 if grad_dtype is None else grad_dtype
-    if gdt not in (torch.float32, q.dtype):
-        raise NativeError(f"maxsim_inbatch_bwd: gradients are float32 or {q.dtype}, not {gdt}")
+    q, d, E = _pad16(q, d)
+    gdt = _grad_dtype("maxsim_inbatch_bwd", grad_dtype, q)
     gq = torch.empty((Bq, Q, E), dtype=gdt, device=dev) if need_q else None
     gd = torch.empty((Bd, D, E), dtype=gdt, device=dev) if need_d else None
     if Bq == 0 or Bd == 0:
         return (gq.zero_()[..., :E0] if need_q else None), (gd.zero_()[..., :E0] if need_d else None)
     if not (need_q or need_d):
         return None, None
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_maxsim_inbatch_bwd_workspace_bytes, Bq, Bd, Q, D, E, qk, dk)
-        st = _stream(dev)
-        ws = _workspace(dev, wsb, st)
-        rc = L.mm_maxsim_inbatch_bwd(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, go.data_ptr(),
-                                     gq.data_ptr() if need_q else None, gd.data_ptr() if need_d else None,
-                                     _DT[gdt], Bq, Bd, Q, D, E, _DT[q.dtype], 1 if bug_compatible else 0,
-                                     ws.data_ptr() if ws is not None else None, wsb, st)
-    _lib.check(rc, "mm_maxsim_inbatch_bwd")
-    if E != E0:
-        gq = gq[..., :E0].contiguous() if need_q else None
-        gd = gd[..., :E0].contiguous() if need_d else None
-    return gq, gd
+    _call(dev, L.mm_maxsim_inbatch_bwd, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk, go.data_ptr(),
+                                         gq.data_ptr() if need_q else None, gd.data_ptr() if need_d else None, _DT[gdt],
+                                         Bq, Bd, Q, D, E, _DT[q.dtype], 1 if bug_compatible else 0),
+          L.mm_maxsim_inbatch_bwd_workspace_bytes, (Bq, Bd, Q, D, E, qk, dk), cached=True)
+    return _trim(gq, E0), _trim(gd, E0)
 
 
 def kernel_pool(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor], d_mask: Optional[torch.Tensor],
@@ -595,8 +603,7 @@ def kernel_pool(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor]
                           "and tk.yaml sets use_fp16: False)")
     nq, Q, E = q.shape
     B, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
+    _same_width(E, E2)
     if pair_query is not None:
         pq = pair_query.reshape(-1).to(torch.int32).contiguous()
         if pq.numel() != B:
@@ -606,9 +613,8 @@ def kernel_pool(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor]
             if lo < 0 or hi >= nq:
                 raise NativeError(f"pair_query values [{lo}, {hi}] outside the {nq} query rows")
         pairs_per_query = 1
-    elif pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
     else:
+        _per_query(nq, B, pairs_per_query)
         pq = None
     K = mu.numel()
     mu, sigma, alpha, w = _vec(mu), _vec(sigma), _vec(alpha), _vec(w)
@@ -623,19 +629,14 @@ def kernel_pool(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Tensor]
     pooled = torch.empty((B, Q, K), dtype=torch.float32, device=dev) if return_pooled else None
     if B:
         q, d, E = _pad_rows(q, d, 4)
-        with _on(dev):
-            wsb = _ws_bytes(L.mm_kernel_pool_workspace_bytes, max(B, nq), 1 if pq is not None else pairs_per_query, Q, D, qk, dk)
-            st = _stream(dev)
-            ws = _workspace(dev, wsb, st)
-            rc = L.mm_kernel_pool_ex_fwd2(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk,
-                                          gate.data_ptr() if gate is not None else None,
-                                          pq.data_ptr() if pq is not None else None, nq, mu.data_ptr(),
-                                          sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(), float(clamp_min),
-                                          out.data_ptr(), pk.data_ptr() if pk is not None else None,
-                                          pooled.data_ptr() if pooled is not None else None, B,
-                                          pairs_per_query, Q, D, E, K, _lib.MM_F32,
-                                          ws.data_ptr() if ws is not None else None, wsb, st)
-        _lib.check(rc, "mm_kernel_pool_ex_fwd2")
+        _call(dev, L.mm_kernel_pool_ex_fwd2, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk,
+                                              gate.data_ptr() if gate is not None else None,
+                                              pq.data_ptr() if pq is not None else None, nq, mu.data_ptr(),
+                                              sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(), float(clamp_min),
+                                              out.data_ptr(), pk.data_ptr() if pk is not None else None,
+                                              pooled.data_ptr() if pooled is not None else None, B,
+                                              pairs_per_query, Q, D, E, K, _lib.MM_F32),
+              L.mm_kernel_pool_workspace_bytes, (max(B, nq), pairs_per_query, Q, D, qk, dk), cached=True)
     res = (out, pk) if return_per_kernel else (out,)
     if return_pooled:
         res = res + (pooled,)
@@ -647,7 +648,6 @@ def kernel_pool_multi(q_list, d_list, q_mask: Optional[torch.Tensor], d_mask: Op
     """Sum over all (i, t) of kernel_pool(q_list[i], d_list[t], bin weights w[i * len(d_list) + t]) in ONE launch
     (+ a deterministic sum): Conv-KNRM's n_grams^2 match matrices and its dense layer (conv_knrm.py:130-137).
     q_list[i] [B, Q, E], d_list[t] [B, D, E] float32 (pair-per-row), w [len(q_list) * len(d_list), K].  Returns [B]."""
-    import ctypes
     q_list = [_emb(t, "q") for t in q_list]
     d_list = [_emb(t, "d") for t in d_list]
     dev = _dev_check(*q_list, *d_list, q_mask, d_mask, mu, sigma, alpha, w)
@@ -661,15 +661,12 @@ def kernel_pool_multi(q_list, d_list, q_mask: Optional[torch.Tensor], d_mask: Op
             raise NativeError(f"kernel_pool_multi: document tensors must all be float32 [{B},{D},{E}]")
     nq_, nd_ = len(q_list), len(d_list)
     K = mu.numel()
-    f = lambda t: t.detach().reshape(-1).to(torch.float32).contiguous()
-    mu, sigma, alpha, w = f(mu), f(sigma), f(alpha), f(w)
+    mu, sigma, alpha, w = _vec(mu), _vec(sigma), _vec(alpha), _vec(w)
     if w.numel() != nq_ * nd_ * K or sigma.numel() != K or alpha.numel() != K:
         raise NativeError("kernel_pool_multi: w must hold K weights per (query tensor, document tensor) combination")
-    if E % 4:
-        pad = (0, 4 - E % 4)
-        q_list = [torch.nn.functional.pad(t, pad) for t in q_list]
-        d_list = [torch.nn.functional.pad(t, pad) for t in d_list]
-        E = q_list[0].shape[-1]
+    q_list = [_pad_last(t, 4) for t in q_list]
+    d_list = [_pad_last(t, 4) for t in d_list]
+    E = q_list[0].shape[-1]
     qm, qp, qk = _mask(q_mask, B, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, B, D, "d_mask")
     L = _lib.lib()
@@ -678,13 +675,10 @@ def kernel_pool_multi(q_list, d_list, q_mask: Optional[torch.Tensor], d_mask: Op
         return out
     qa = (ctypes.c_void_p * nq_)(*[t.data_ptr() for t in q_list])
     da = (ctypes.c_void_p * nd_)(*[t.data_ptr() for t in d_list])
-    with torch.cuda.device(dev):
-        wsb = L.mm_kernel_pool_multi_workspace_bytes(B, 1, nq_, nd_, Q, D, qk, dk)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = L.mm_kernel_pool_multi_fwd(ctypes.cast(qa, ctypes.c_void_p), nq_, ctypes.cast(da, ctypes.c_void_p), nd_, qp, qk, dp, dk,
-                                        mu.data_ptr(), sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(), float(clamp_min),
-                                        out.data_ptr(), B, 1, Q, D, E, K, _lib.MM_F32, ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_kernel_pool_multi_fwd")
+    _call(dev, L.mm_kernel_pool_multi_fwd, (ctypes.cast(qa, ctypes.c_void_p), nq_, ctypes.cast(da, ctypes.c_void_p), nd_, qp, qk,
+                                            dp, dk, mu.data_ptr(), sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(),
+                                            float(clamp_min), out.data_ptr(), B, 1, Q, D, E, K, _lib.MM_F32),
+          L.mm_kernel_pool_multi_workspace_bytes, (B, 1, nq_, nd_, Q, D, qk, dk))
     return out
 
 
@@ -708,20 +702,13 @@ def kernel_pool_bwd(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Ten
     q, d = _emb(q, "q"), _emb(d, "d")
     if q.dtype != torch.float32 or d.dtype != torch.float32:
         raise NativeError("kernel_pool_bwd: float32 embeddings only")
-    B, Q, E = q.shape
-    B2, D, E2 = d.shape
-    if B != B2 or E != E2:
-        raise NativeError(f"kernel_pool_bwd needs the pair-per-row layout: q {tuple(q.shape)} vs d {tuple(d.shape)}")
+    B, Q, D, E0 = _pair_per_row("kernel_pool_bwd", q, d)
     K = mu.numel()
-    f = lambda t: t.detach().reshape(-1).to(torch.float32).contiguous()
-    mu, sigma, alpha, w = f(mu), f(sigma), f(alpha), f(w)
-    go = f(grad_out)
-    if go.numel() != B:
-        raise NativeError(f"grad_out has {go.numel()} elements for {B} pairs")
+    mu, sigma, alpha, w = _vec(mu), _vec(sigma), _vec(alpha), _vec(w)
+    go = _grad_flat(grad_out, B, f"{B}")
     qm, qp, qk = _mask(q_mask, B, Q, "q_mask")
     dm, dp, dk = _mask(d_mask, B, D, "d_mask")
     L = _lib.lib()
-    E0 = E
     q, d, E = _pad_rows(q, d, 4)
     gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
     gd = torch.empty((B, D, E), dtype=torch.float32, device=dev)
@@ -734,19 +721,15 @@ def kernel_pool_bwd(q: torch.Tensor, d: torch.Tensor, q_mask: Optional[torch.Ten
             raise NativeError(f"pooled has shape {tuple(pooled.shape)} / {pooled.dtype}, expected float32 {(B, Q, K)}")
         pooled = pooled.detach().contiguous()
     if B:
-        with torch.cuda.device(dev):
-            wsb = L.mm_kernel_pool_bwd_workspace_bytes2(B, Q, D, E, qk, dk)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-            rc = L.mm_kernel_pool_ex_bwd2(q.data_ptr(), d.data_ptr(), qp, qk, dp, dk,
-                                          gate.data_ptr() if gate is not None else None, mu.data_ptr(),
-                                          sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(), float(clamp_min),
-                                          pooled.data_ptr() if pooled is not None else None,
-                                          go.data_ptr(), gq.data_ptr(), gd.data_ptr(),
-                                          gg.data_ptr() if gg is not None else None, ga.data_ptr(), gw.data_ptr(),
-                                          B, Q, D, E, K, ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-        _lib.check(rc, "mm_kernel_pool_ex_bwd2")
-    if E != E0:
-        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
+        _call(dev, L.mm_kernel_pool_ex_bwd2, (q.data_ptr(), d.data_ptr(), qp, qk, dp, dk,
+                                              gate.data_ptr() if gate is not None else None, mu.data_ptr(),
+                                              sigma.data_ptr(), alpha.data_ptr(), w.data_ptr(), float(clamp_min),
+                                              pooled.data_ptr() if pooled is not None else None,
+                                              go.data_ptr(), gq.data_ptr(), gd.data_ptr(),
+                                              gg.data_ptr() if gg is not None else None, ga.data_ptr(), gw.data_ptr(),
+                                              B, Q, D, E, K),
+              L.mm_kernel_pool_bwd_workspace_bytes2, (B, Q, D, E, qk, dk))
+    gq, gd = _trim(gq, E0), _trim(gd, E0)
     gaw = gaw.sum(1)
     if gate is not None:
         return gq, gd, gaw[0], gaw[1], gg
@@ -791,14 +774,10 @@ def tkl_score(q_ctx: torch.Tensor, chunks: torch.Tensor, chunk_mask: torch.Tenso
     win = torch.empty((B, W), dtype=torch.float32, device=dev)
     peaks = torch.empty((B, 3), dtype=torch.int32, device=dev) if return_peaks else None
     if B:
-        with torch.cuda.device(dev):
-            wsb = L.mm_tkl_workspace_bytes(B, P, C, Q, K)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-            rc = L.mm_tkl_fwd_peaks(q_ctx.data_ptr(), chunks.data_ptr(), chunk_mask.data_ptr(), chunk_slot.data_ptr(),
-                                    q_mask.data_ptr(), params.data_ptr(), win.data_ptr(), out.data_ptr(),
-                                    peaks.data_ptr() if peaks is not None else None, B, P, C, Q, E,
-                                    K, sat, ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-        _lib.check(rc, "mm_tkl_fwd_peaks")
+        _call(dev, L.mm_tkl_fwd_peaks, (q_ctx.data_ptr(), chunks.data_ptr(), chunk_mask.data_ptr(), chunk_slot.data_ptr(),
+                                        q_mask.data_ptr(), params.data_ptr(), win.data_ptr(), out.data_ptr(),
+                                        peaks.data_ptr() if peaks is not None else None, B, P, C, Q, E, K, sat),
+              L.mm_tkl_workspace_bytes, (B, P, C, Q, K))
     if return_peaks:
         return out, win, peaks.long()
     return (out, win) if return_windows else out
@@ -823,7 +802,7 @@ def tkl_bwd(q_ctx: torch.Tensor, chunks: torch.Tensor, chunk_mask: torch.Tensor,
     q_mask = q_mask.to(torch.float32).contiguous()
     params = params.detach().to(torch.float32).contiguous()
     win = win.detach().to(torch.float32).contiguous()
-    go = grad_out.detach().reshape(-1).to(torch.float32).contiguous()
+    go = _flat32(grad_out)
     NP = params.numel()
     gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
     gc = torch.empty((P, 50, E), dtype=torch.float32, device=dev)
@@ -831,14 +810,10 @@ def tkl_bwd(q_ctx: torch.Tensor, chunks: torch.Tensor, chunk_mask: torch.Tensor,
     if B == 0:
         return gq, gc.zero_(), torch.zeros(NP, dtype=torch.float32, device=dev)
     L = _lib.lib()
-    with torch.cuda.device(dev):
-        wsb = L.mm_tkl_bwd_workspace_bytes2(B, C, Q, E)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        rc = L.mm_tkl_bwd(q_ctx.data_ptr(), chunks.data_ptr() if P else None, chunk_mask.data_ptr() if P else None,
-                          chunk_slot.data_ptr() if P else None, q_mask.data_ptr(), params.data_ptr(), win.data_ptr(), go.data_ptr(),
-                          gq.data_ptr(), gc.data_ptr() if P else None, gp.data_ptr(), B, P, C, Q, E, K, sat, ws.data_ptr(), wsb,
-                          _stream(dev))
-    _lib.check(rc, "mm_tkl_bwd")
+    _call(dev, L.mm_tkl_bwd, (q_ctx.data_ptr(), chunks.data_ptr() if P else None, chunk_mask.data_ptr() if P else None,
+                              chunk_slot.data_ptr() if P else None, q_mask.data_ptr(), params.data_ptr(), win.data_ptr(),
+                              go.data_ptr(), gq.data_ptr(), gc.data_ptr() if P else None, gp.data_ptr(), B, P, C, Q, E, K, sat),
+          L.mm_tkl_bwd_workspace_bytes2, (B, C, Q, E))
     return gq, gc, gp.sum(0)
 
 
@@ -870,7 +845,7 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
             s = torch.empty((n, k), dtype=torch.float32, device=dev)
             i = torch.empty((n, k), dtype=torch.int64, device=dev)
         st = torch.empty(n, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
+        with _on(dev):
             wsb = L.mm_dot_topk_workspace_bytes(N, n, k)
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             rc = L.mm_dot_topk_fwd(q.data_ptr(), corpus.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s.data_ptr(),
@@ -1175,7 +1150,7 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
     out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
     out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
     if nq:
-        with torch.cuda.device(dev):
+        with _on(dev):
             rc = _lib.lib().mm_topk_merge(scores.data_ptr(), ids.data_ptr(), nq, n_in, k, out_s.data_ptr(),
                                           out_i.data_ptr(), _stream(dev))
         _lib.check(rc, "mm_topk_merge")
@@ -1254,12 +1229,7 @@ def _pacrr_params(weights, biases, C: int, dev):
 
 
 def _pacrr_shapes(q, d, pairs_per_query, k):
-    nq, Q, E = q.shape
-    B, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    nq, Q, E, B, D = _qd_shapes(q, d, pairs_per_query)
     if not (1 <= k <= 32) or not (k <= D <= 2048) or not (1 <= Q <= 64) or E > 1024:
         # the reference's torch.topk raises for D < k (pacrr.py:86); the kernel's limits are in mm_native.h
         raise NativeError(f"pacrr_kmax: Q = {Q}, D = {D}, E = {E}, k = {k} outside 1 <= Q <= 64, k <= D <= 2048, "
@@ -1287,10 +1257,11 @@ def _pacrr_fwd_setup(what, q, d, weights, biases, k, pairs_per_query, check=None
     return (dev, q, d, w.data_ptr() if w is not None else None, b.data_ptr() if b is not None else None, B, Q, D, E, C, N)
 
 
-def _pacrr_bwd(name, q, d, weights, idx, grad_out, k, pairs_per_query, idx_shape, go_shape, launch, check=None):
+def _pacrr_bwd(name, fn, size_fn, q, d, weights, idx, grad_out, k, pairs_per_query, idx_shape, go_shape, size_key, extra=(),
+               check=None):
     """The backward both models share around their launch.  idx_shape / go_shape: (B, Q, N) -> the shapes idx / grad_out
-    must have; launch(L, ptrs, dims, dev) runs the model's workspace query and mm_*_bwd and returns its code, ptrs =
-    (q, d, w, idx, go, gq, gd, gw, gb) and dims = (B, pairs_per_query, Q, D, E, C, N, k).  After it: E un-padded, the
+    must have; the launch is fn(q, d, w, idx, go, gq, gd, gw, gb, B, pairs_per_query, Q, D, E, C, N, k, *extra, ..), fn =
+    mm_<name>_bwd, with a workspace of size_fn(*size_key(B, Q, D, E, C, N)).  After it: E un-padded, the
     per-pair grad_q rows summed per query in group order, grad_w / grad_b summed over the pairs and split per width."""
     what = name + "_kmax_bwd"
     dev = _dev_check(q, d, idx, grad_out)
@@ -1319,11 +1290,8 @@ def _pacrr_bwd(name, q, d, weights, idx, grad_out, k, pairs_per_query, idx_shape
     if B:
         ptrs = (q.data_ptr(), d.data_ptr(), w.data_ptr() if w is not None else None, idx.data_ptr(), go.data_ptr(),
                 gq.data_ptr(), gd.data_ptr(), gw.data_ptr() if N > 1 else None, gb.data_ptr() if N > 1 else None)
-        with _on(dev):
-            rc = launch(_lib.lib(), ptrs, (B, pairs_per_query, Q, D, E, C, N, k), dev)
-        _lib.check(rc, f"mm_{name}_bwd")
-    if E != E0:
-        gq, gd = gq[..., :E0].contiguous(), gd[..., :E0].contiguous()
+        _call(dev, fn, ptrs + (B, pairs_per_query, Q, D, E, C, N, k) + tuple(extra), size_fn, size_key(B, Q, D, E, C, N))
+    gq, gd = _trim(gq, E0), _trim(gd, E0)
     if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
         pad = nq * pairs_per_query - B
         if pad:
@@ -1351,11 +1319,8 @@ def pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, pairs_
     out = torch.empty((B, Q, k * N), dtype=torch.float32, device=dev)
     idx = torch.empty((B, Q, k * N), dtype=torch.int32, device=dev) if save else None
     if B:
-        with _on(dev):
-            rc = _lib.lib().mm_pacrr_fwd(q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
-                                         idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k,
-                                         None, 0, _stream(dev))
-        _lib.check(rc, "mm_pacrr_fwd")
+        _call(dev, _lib.lib().mm_pacrr_fwd, (q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
+                                             idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N, k))
     return (out, idx) if save else out
 
 
@@ -1364,14 +1329,10 @@ def pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tensor,
     """Backward of pacrr_kmax (mm_pacrr_bwd): idx as returned by pacrr_kmax(..., save=True) on the same inputs, grad_out
     [n_pairs, Q, k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w, grad_b) with grad_w /
     grad_b lists shaped like `weights` / their biases ([C]), summed over the pairs in a fixed order (no atomics)."""
-    def launch(L, ptrs, dims, dev):
-        B, _, Q, D, _, C, N, _ = dims
-        wsb = L.mm_pacrr_workspace_bytes(B, Q, D, C, N, k)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        return L.mm_pacrr_bwd(*ptrs, *dims, ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-
     shape = lambda B, Q, N: (B, Q, k * N)
-    return _pacrr_bwd("pacrr", q, d, weights, idx, grad_out, k, pairs_per_query, shape, shape, launch)
+    L = _lib.lib()
+    return _pacrr_bwd("pacrr", L.mm_pacrr_bwd, L.mm_pacrr_workspace_bytes, q, d, weights, idx, grad_out, k, pairs_per_query, shape, shape,
+                      lambda B, Q, D, E, C, N: (B, Q, D, C, N, k))
 
 
 def co_pacrr_views(unified_document_length: int):
@@ -1404,11 +1365,9 @@ def co_pacrr_kmax(q: torch.Tensor, d: torch.Tensor, weights, biases, k: int, vie
     out = torch.empty((B, Q, 8 * k * N), dtype=torch.float32, device=dev)
     idx = torch.empty((B, Q, N, 4 * k), dtype=torch.int32, device=dev) if save else None
     if B:
-        with _on(dev):
-            rc = _lib.lib().mm_co_pacrr_fwd(q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
-                                            idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N,
-                                            k, *views, None, 0, _stream(dev))
-        _lib.check(rc, "mm_co_pacrr_fwd")
+        _call(dev, _lib.lib().mm_co_pacrr_fwd, (q.data_ptr(), d.data_ptr(), w, b, out.data_ptr(),
+                                                idx.data_ptr() if idx is not None else None, B, pairs_per_query, Q, D, E, C, N,
+                                                k, *views))
     return (out, idx) if save else out
 
 
@@ -1418,26 +1377,16 @@ def co_pacrr_kmax_bwd(q: torch.Tensor, d: torch.Tensor, weights, idx: torch.Tens
     inputs, grad_out [n_pairs, Q, 8 k N].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w,
     grad_b) as pacrr_kmax_bwd."""
     views = [int(v) for v in views]
-
-    def launch(L, ptrs, dims, dev):
-        B, _, Q, D, E, C, N, _ = dims
-        wsb = L.mm_co_pacrr_workspace_bytes(B, Q, D, E, C, N, k)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        return L.mm_co_pacrr_bwd(*ptrs, *dims, *views, ws.data_ptr(), wsb, _stream(dev))
-
-    return _pacrr_bwd("co_pacrr", q, d, weights, idx, grad_out, k, pairs_per_query,
-                      lambda B, Q, N: (B, Q, N, 4 * k), lambda B, Q, N: (B, Q, 8 * k * N), launch,
+    L = _lib.lib()
+    return _pacrr_bwd("co_pacrr", L.mm_co_pacrr_bwd, L.mm_co_pacrr_workspace_bytes, q, d, weights, idx, grad_out, k, pairs_per_query,
+                      lambda B, Q, N: (B, Q, N, 4 * k), lambda B, Q, N: (B, Q, 8 * k * N),
+                      lambda B, Q, D, E, C, N: (B, Q, D, E, C, N, k), views,
                       lambda B, Q, D, E: _co_pacrr_check(B, Q, D, E, k, views))
 
 
 # ---------------------------------------------------------------------------------------------- DRMM
 def _drmm_shapes(q, d, pairs_per_query, bins, what):
-    nq, Q, E = q.shape
-    B, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    nq, Q, E, B, D = _qd_shapes(q, d, pairs_per_query)
     if not (1 <= Q <= 64) or not (1 <= D <= 65535) or E > 1024 or not (1 <= bins <= 16):
         raise NativeError(f"{what}: Q = {Q}, D = {D}, E = {E}, bins = {bins} outside 1 <= Q <= 64, 1 <= D <= 65535, "
                           f"E <= 1024, 1 <= bins <= 16 (MM_EUNSUPPORTED)")
@@ -1477,11 +1426,8 @@ def _drmm_call(what, q, d, bins, pairs_per_query, d_len, clamp, want_hist, head)
     if B:
         q, d, E = _pad_rows(q, d, 4)
         p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
-        with _on(dev):
-            rc = _lib.lib().mm_drmm_fwd(q.data_ptr(), d.data_ptr(), p(dl), p(hist), p(score), p(gate), per_pair, p(W1), p(b1),
-                                        p(w2), p(b2), B, pairs_per_query, Q, D, E, bins, 1 if clamp else 0, None, 0,
-                                        _stream(dev))
-        _lib.check(rc, "mm_drmm_fwd")
+        _call(dev, _lib.lib().mm_drmm_fwd, (q.data_ptr(), d.data_ptr(), p(dl), p(hist), p(score), p(gate), per_pair, p(W1),
+                                            p(b1), p(w2), p(b2), B, pairs_per_query, Q, D, E, bins, 1 if clamp else 0))
     return hist, score
 
 
@@ -1526,6 +1472,11 @@ def _mp_layers(Q, D, weights, biases, pool_sizes, what):
     return (ctypes.c_int32 * (5 * L))(*[x for r in rows for x in r]), max(cin * rows[-1][3] * rows[-1][4], 0)
 
 
+def mm_matchpyramid_workspace_bytes(B, Q, D, L, *layers):
+    """The size query on integers alone (the layer table flattened), so that _ws_bytes can key it like the others."""
+    return _lib.lib().mm_matchpyramid_workspace_bytes(B, Q, D, L, (ctypes.c_int32 * len(layers))(*layers))
+
+
 def matchpyramid_pack(weights, biases):
     """The conv weights / biases of every layer in mm_matchpyramid_fwd's packing (two float32 vectors)."""
     w = torch.cat([t.detach().to(torch.float32).reshape(-1) for t in weights])
@@ -1546,23 +1497,14 @@ def matchpyramid_features(q: torch.Tensor, d: torch.Tensor, weights, biases, poo
     q, d = _emb(q, "q"), _emb(d, "d")
     if q.dtype != torch.float32 or d.dtype != torch.float32:
         raise NativeError("matchpyramid_features: float32 embeddings only (the reference cosine rejects bf16)")
-    nq, Q, E = q.shape
-    B, D, E2 = d.shape
-    if E != E2:
-        raise NativeError(f"embedding dims differ: {E} vs {E2}")
-    if pairs_per_query < 1 or nq != (B + pairs_per_query - 1) // pairs_per_query:
-        raise NativeError(f"q has {nq} rows but {B} pairs / {pairs_per_query} per query")
+    nq, Q, E, B, D = _qd_shapes(q, d, pairs_per_query)
     layers, feat = _mp_layers(Q, D, weights, biases, pool_sizes, "matchpyramid_features")
     out = torch.empty((B, feat), dtype=torch.float32, device=dev)
     if B:
         w, b = packed if packed is not None else matchpyramid_pack(weights, biases)
         q, d, E = _pad_rows(q, d, 4)
         L = len(weights)
-        need = _lib.lib().mm_matchpyramid_workspace_bytes(B, Q, D, L, layers)
-        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
-        with _on(dev):
-            rc = _lib.lib().mm_matchpyramid_fwd(q.data_ptr(), d.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), B,
-                                                pairs_per_query, Q, D, E, L, layers, ws.data_ptr() if need else None, need,
-                                                _stream(dev))
-        _lib.check(rc, "mm_matchpyramid_fwd")
+        _call(dev, _lib.lib().mm_matchpyramid_fwd, (q.data_ptr(), d.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(), B,
+                                                    pairs_per_query, Q, D, E, L, layers),
+              mm_matchpyramid_workspace_bytes, (B, Q, D, L, *layers))
     return out
