@@ -812,6 +812,29 @@ int mm_maxsim_ragged_fp8_fwd(const void* q, const uint8_t* codes, const float* s
                              int64_t n_pairs, int64_t pairs_per_query, int Q, int E, int q_dtype, int flags,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * fp8 token search: mm_dot_topk_fwd over an fp8 store (additive: MM_ABI_VERSION unchanged).
+ *
+ * Replaces, for a store held as codes + scales, the same reference lines as mm_dot_topk_fwd: the flat inner-product index
+ *           FaissBaseIndexer.search                      matchmaker/retrieval/faiss_indices.py:22-36
+ *           called per query batch at                    matchmaker/dense_retrieval.py:391
+ *
+ *   score[q, t] = scales[t] * sum_k queries[q, k] * deq(codes[t, k])
+ *   queries [nq, E] MM_F16 or MM_BF16 (MM_F32 returns MM_EUNSUPPORTED) and NOT quantised; codes [n_rows, E] uint8 (OCP
+ *   e4m3fn) + scales [n_rows] float32 as mm_fp8_quantize_rows writes them; E in {128, 256, 384, 512, 768}.  The codes are
+ *   converted to the query's type in registers (exact) and multiplied on the 16-bit MFMA: every product is exact, the sum
+ *   is fp32, and the power-of-two scale multiplies the finished dot product (exact) before the threshold test.
+ *   out_scores / out_idx / the tie rule (score descending, lower row first) / the (-inf, -1) padding when n_rows < k /
+ *   status 0, 1, 2 with m_scale / k <= 4096 / n_rows < 2^31 are mm_dot_topk_fwd's.  The sample pass and the filter pass
+ *   give the same bits for one (query, row) pair.  queries and codes 16-byte aligned, scales 4-byte aligned.  No load uses
+ *   a row index >= n_rows.
+ *   workspace: mm_dot_topk_fp8_workspace_bytes(n_rows, nq, k) bytes. */
+size_t mm_dot_topk_fp8_workspace_bytes(int64_t n_rows, int nq, int k);
+
+int mm_dot_topk_fp8_fwd(const void* queries, const uint8_t* codes, const float* scales, int64_t n_rows, int nq, int E,
+                        int q_dtype, int k, float m_scale, float* out_scores, int64_t* out_idx, int32_t* status,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

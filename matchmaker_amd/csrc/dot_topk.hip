@@ -38,7 +38,6 @@
 
 namespace mm {
 
-constexpr int kDotSample = 16384;  // sample size (documents) of phase 1 when the shard is larger
 constexpr int kSortMax = 16384;    // rows of sort_rows_kernel are padded to a power of two <= this
 
 enum { DOT_SAMPLE = 0, DOT_FILTER = 1 };
@@ -1044,24 +1043,69 @@ static int launch_dot_e(const DotArgs& a, int nq_launch, const DotGeom& g, hipSt
   }
 }
 
-}  // namespace mm
-
-using namespace mm;
-
-static int dot_cap(int64_t n_docs, int k) {  // candidate list capacity per query
+int dot_cap(int64_t n_docs, int k) {  // candidate list capacity per query
   int c = pow2_ge(4 * k);
   if (c < 1024) c = 1024;
   if (n_docs <= 4096 && c < 4096) c = 4096;  // small shards: everything is a candidate
   return c;
 }
 
-extern "C" size_t mm_dot_topk_workspace_bytes(int64_t n_docs, int nq, int k) {
+// ---- the selection phases as host-side helpers (mm_internal.h): mm_dot_topk_fwd below and mm_dot_topk_fp8_fwd
+// (dot_topk_fp8.hip) run the same workspace layout, threshold rule and launches around their own streaming kernel
+size_t dot_sel_bytes(int64_t n_docs, int nq, int k) {
   if (n_docs <= 0 || nq <= 0 || k <= 0) return 0;
   const int cap = dot_cap(n_docs, k);
   const int64_t s = n_docs < kDotSample ? n_docs : kDotSample;
   // sample scores | tau | survivor counts | candidate scores + indices
   return a256((size_t)nq * s * 4) + 2 * a256((size_t)nq * 4) + 2 * a256((size_t)nq * cap * 4);
 }
+
+DotSel dot_sel_carve(void* workspace, int64_t n_docs, int nq, int k) {
+  DotSel d;
+  d.cap = dot_cap(n_docs, k);
+  d.S = n_docs < kDotSample ? n_docs : kDotSample;
+  char* ws = (char*)workspace;
+  d.all = (float*)ws;            ws += a256((size_t)nq * d.S * 4);
+  d.tau = (float*)ws;            ws += a256((size_t)nq * 4);
+  d.count = (int32_t*)ws;        ws += a256((size_t)nq * 4);
+  d.cand_score = (float*)ws;     ws += a256((size_t)nq * d.cap * 4);
+  d.cand_idx = (int32_t*)ws;
+  return d;
+}
+
+int dot_sample_m(int64_t n_docs, int64_t S, int k, float m_scale) {
+  // expected survivors of the full pass ~ m * n_docs / S: aim at 2.5 k of the 4 k capacity (x the caller's retry factor)
+  double mt = 2.5 * k * m_scale * (double)S / (double)n_docs;
+  int m = (int)(mt + 0.5);
+  if (m < 4) m = 4;
+  if (m > S) m = (int)S;
+  return m;
+}
+
+void launch_fill_tau(const DotSel& d, int nq, float v, hipStream_t stream) {
+  hipLaunchKernelGGL(fill_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, d.tau, nq, v);
+}
+
+void launch_sample_tau(const DotSel& d, int nq, int m, hipStream_t stream) {
+  hipLaunchKernelGGL(sample_tau_kernel, dim3(nq), dim3(1024), 0, stream, d.all, d.S, (int)d.S, m, d.tau);
+}
+
+int launch_topk_rows(const DotSel& d, int nq, int k, int64_t n_total, float* out_scores, int64_t* out_idx, int32_t* status,
+                     hipStream_t stream) {
+  const int cap = d.cap;
+  const size_t lds_rows = (size_t)cap * 8 + kSelMax * 8 + 256 * 4 + 32;
+  if (lds_rows > 64 * 1024)
+    (void)hipFuncSetAttribute((const void*)topk_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
+  hipLaunchKernelGGL(topk_rows_kernel, dim3(nq), dim3(1024), lds_rows, stream, d.cand_score, d.cand_idx, d.count, cap, k,
+                     n_total, out_scores, out_idx, status);
+  return check_launch("topk_rows_kernel");
+}
+
+}  // namespace mm
+
+using namespace mm;
+
+extern "C" size_t mm_dot_topk_workspace_bytes(int64_t n_docs, int nq, int k) { return dot_sel_bytes(n_docs, nq, k); }
 
 extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t n_docs, int nq, int E, int dtype, int k,
                                float m_scale, float* out_scores, int64_t* out_idx, int32_t* status, void* workspace,
@@ -1080,14 +1124,14 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
 
   const DotGeom g = dot_geom(n_docs, nq);
   const bool small = n_docs <= 4096;  // everything is a candidate: no sampling
-  const int cap = dot_cap(n_docs, k);
-  const int64_t S = n_docs < kDotSample ? n_docs : kDotSample;
-  char* ws = (char*)workspace;
-  float* all = (float*)ws;            ws += a256((size_t)nq * S * 4);
-  float* tau = (float*)ws;            ws += a256((size_t)nq * 4);
-  int32_t* count = (int32_t*)ws;      ws += a256((size_t)nq * 4);
-  float* cand_score = (float*)ws;     ws += a256((size_t)nq * cap * 4);
-  int32_t* cand_idx = (int32_t*)ws;
+  const DotSel sel = dot_sel_carve(workspace, n_docs, nq, k);
+  const int cap = sel.cap;
+  const int64_t S = sel.S;
+  float* all = sel.all;
+  float* tau = sel.tau;
+  int32_t* count = sel.count;
+  float* cand_score = sel.cand_score;
+  int32_t* cand_idx = sel.cand_idx;
 
   DotArgs a{};
   a.q = queries; a.c = corpus; a.nq = nq; a.E = E; a.q_base = 0;
@@ -1095,18 +1139,13 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
 
   // phase 1: threshold per query
   if (small) {
-    hipLaunchKernelGGL(fill_tau_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, tau, nq, -__builtin_huge_valf());
+    launch_fill_tau(sel, nq, -__builtin_huge_valf(), stream);
   } else {
     a.ndocs = S; a.stride = n_docs / S; a.all_out = all; a.ld_all = S;
     const DotGeom gs = dot_geom(S, nq);
     const int e = dtype == MM_BF16 ? launch_dot_e<MM_BF16, DOT_SAMPLE>(a, nq, gs, stream) : launch_dot_e<MM_F16, DOT_SAMPLE>(a, nq, gs, stream);
     if (e) return e;
-    // expected survivors of the full pass ~ m * n_docs / S: aim at 2.5 k of the 4 k capacity (x the caller's retry factor)
-    double mt = 2.5 * k * m_scale * (double)S / (double)n_docs;
-    int m = (int)(mt + 0.5);
-    if (m < 4) m = 4;
-    if (m > S) m = (int)S;
-    hipLaunchKernelGGL(sample_tau_kernel, dim3(nq), dim3(1024), 0, stream, all, S, (int)S, m, tau);
+    launch_sample_tau(sel, nq, dot_sample_m(n_docs, S, k, m_scale), stream);
   }
   if (int e = check_launch("dot_topk threshold")) return e;
 
@@ -1128,12 +1167,7 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
     if (e) return e;
   }
   // phase 3: exact top-k of the survivors
-  const size_t lds_rows = (size_t)cap * 8 + kSelMax * 8 + 256 * 4 + 32;
-  if (lds_rows > 64 * 1024)
-    (void)hipFuncSetAttribute((const void*)topk_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_rows);
-  hipLaunchKernelGGL(topk_rows_kernel, dim3(nq), dim3(1024), lds_rows, stream, cand_score, cand_idx, count, cap, k,
-                     n_docs, out_scores, out_idx, status);
-  if (int e = check_launch("topk_rows_kernel")) return e;
+  if (int e = launch_topk_rows(sel, nq, k, n_docs, out_scores, out_idx, status, stream)) return e;
   if (a.prof) {  // tools only: synchronous dump of the phase counters
     static unsigned long long host[8 * 32 * 32 * 4 * 8];
     (void)hipStreamSynchronize(stream);

@@ -161,6 +161,29 @@ bool kp128_maxsim_supported(int Q, int E);
 int kp128_maxsim_f32(const float* q, const float* d, PackedMask qm, PackedMask dm, float* out, int64_t n_pairs,
                      int64_t pairs_per_query, int Q, int D, int E, hipStream_t stream);
 
+// dot_topk.hip: the selection phases of the flat inner-product top-k (threshold from a sample, candidate lists, exact top-k
+// of the survivors), shared by mm_dot_topk_fwd and mm_dot_topk_fp8_fwd (dot_topk_fp8.hip), which differ in the streaming
+// kernel between them only.  The workspace of a call is dot_sel_bytes(): sample scores [nq, S] | tau [nq] | survivor
+// counts [nq] | candidate scores and rows [nq, cap] each.
+constexpr int kDotSample = 16384;  // sample size (documents) of phase 1 when the shard is larger
+struct DotSel {
+  float* all;         // [nq, S] scores of the strided sample
+  float* tau;         // [nq] thresholds
+  int32_t* count;     // [nq] survivors (may exceed cap: overflow)
+  float* cand_score;  // [nq, cap]
+  int32_t* cand_idx;  // [nq, cap]
+  int cap;
+  int64_t S;          // min(n_docs, kDotSample)
+};
+int dot_cap(int64_t n_docs, int k);
+size_t dot_sel_bytes(int64_t n_docs, int nq, int k);
+DotSel dot_sel_carve(void* workspace, int64_t n_docs, int nq, int k);
+int dot_sample_m(int64_t n_docs, int64_t S, int k, float m_scale);   // the sample rank that becomes the threshold
+void launch_fill_tau(const DotSel& d, int nq, float v, hipStream_t stream);             // fill_tau_kernel
+void launch_sample_tau(const DotSel& d, int nq, int m, hipStream_t stream);             // sample_tau_kernel
+int launch_topk_rows(const DotSel& d, int nq, int k, int64_t n_total, float* out_scores, int64_t* out_idx, int32_t* status,
+                     hipStream_t stream);                                                // topk_rows_kernel
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);

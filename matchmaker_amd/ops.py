@@ -817,21 +817,11 @@ def tkl_bwd(q_ctx: torch.Tensor, chunks: torch.Tensor, chunk_mask: torch.Tensor,
     return gq, gc, gp.sum(0)
 
 
-def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: int = 6):
-    """Exact brute-force inner-product top-k over one shard (faiss IndexFlatIP.search semantics;
-    matchmaker/retrieval/faiss_indices.py:22-36, :49-74; score = bert_dot.py:62).
-
-    queries [nq, E], corpus [N, E] float16 / bfloat16 on the same device, E in {128,...,768} (pad
-    otherwise).  Returns (scores [nq, k] float32 descending, idx [nq, k] int64 rows of `corpus`,
-    -1 / -inf padded when N < k).  The native call thresholds every query from a sample of the
-    shard; queries whose threshold let too few / too many candidates through (status != 0, rare)
-    are re-run with a moved threshold until every row is exact."""
-    dev = _dev_check(queries, corpus)
-    _pair16("dot_topk", queries, corpus, "[nq, E]", "[N, E]")
-    queries, corpus = queries.contiguous(), corpus.contiguous()
-    nq, E = queries.shape
-    N = corpus.shape[0]
-    L = _lib.lib()
+def _topk_reruns(name: str, dev, queries: torch.Tensor, N: int, k: int, max_rounds: int, size_fn, call):
+    """The status-driven loop of the flat top-k operators (dot_topk, dot_topk_fp8): one native call over every query, then
+    re-runs of the queries whose sampled threshold let too few / too many candidates through, with the threshold scale
+    bisected per query.  call(q, n, scale, s_ptr, i_ptr, st_ptr, ws_ptr, wsb, stream) -> (return code, native symbol)."""
+    nq = queries.shape[0]
     out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
     out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
     if nq == 0:
@@ -846,11 +836,10 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
             i = torch.empty((n, k), dtype=torch.int64, device=dev)
         st = torch.empty(n, dtype=torch.int32, device=dev)
         with _on(dev):
-            wsb = L.mm_dot_topk_workspace_bytes(N, n, k)
+            wsb = size_fn(N, n, k)
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            rc = L.mm_dot_topk_fwd(q.data_ptr(), corpus.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s.data_ptr(),
-                                   i.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-        _lib.check(rc, "mm_dot_topk_fwd")
+            rc, what = call(q, n, scale, s.data_ptr(), i.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
+        _lib.check(rc, what)
         return s, i, st
 
     _, _, st = run(queries, 1.0, out_s, out_i)        # straight into the caller's tensors (no 84 MB staging copy)
@@ -888,8 +877,62 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
         bad = still
         if not bad:
             return out_s, out_i
-    raise NativeError(f"dot_topk: {len(bad)} queries without an exact top-{k} after {max_rounds} threshold re-runs "
+    raise NativeError(f"{name}: {len(bad)} queries without an exact top-{k} after {max_rounds} threshold re-runs "
                       "(more than 4k documents tie at the k-th score?)")
+
+
+def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: int = 6):
+    """Exact brute-force inner-product top-k over one shard (faiss IndexFlatIP.search semantics;
+    matchmaker/retrieval/faiss_indices.py:22-36, :49-74; score = bert_dot.py:62).
+
+    queries [nq, E], corpus [N, E] float16 / bfloat16 on the same device, E in {128,...,768} (pad
+    otherwise).  Returns (scores [nq, k] float32 descending, idx [nq, k] int64 rows of `corpus`,
+    -1 / -inf padded when N < k).  The native call thresholds every query from a sample of the
+    shard; queries whose threshold let too few / too many candidates through (status != 0, rare)
+    are re-run with a moved threshold until every row is exact."""
+    dev = _dev_check(queries, corpus)
+    _pair16("dot_topk", queries, corpus, "[nq, E]", "[N, E]")
+    queries, corpus = queries.contiguous(), corpus.contiguous()
+    nq, E = queries.shape
+    N = corpus.shape[0]
+    L = _lib.lib()
+
+    def call(q, n, scale, s, i, st, ws, wsb, stream):
+        return L.mm_dot_topk_fwd(q.data_ptr(), corpus.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s, i, st, ws, wsb,
+                                 stream), "mm_dot_topk_fwd"
+
+    return _topk_reruns("dot_topk", dev, queries, N, k, max_rounds, L.mm_dot_topk_workspace_bytes, call)
+
+
+def dot_topk_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, k: int, max_rounds: int = 6):
+    """dot_topk over an fp8 token store (mm_dot_topk_fp8_fwd): codes [N, E] uint8 + scales [N] float32 as fp8_quantize_rows
+    writes them, queries [nq, E] fp16 or bf16 (NOT quantised: the codes are converted to the query's type in registers,
+    exactly, and the row scale multiplies the finished fp32 dot product).  score[q, t] = scales[t] * <queries[q],
+    deq(codes[t])>.  E in {128, 256, 384, 512, 768}.  Returns (scores [nq, k] float32 descending, idx [nq, k] int64 rows
+    of the store, -1 / -inf padded when N < k); equal scores go to the lower row; the same status-driven re-runs as
+    dot_topk make every row exact."""
+    dev = _dev_check(queries, codes, scales)
+    if queries.dim() != 2 or queries.dtype not in _DT:
+        raise NativeError(f"dot_topk_fp8: queries: expected [nq, E] float16 / bfloat16, got {tuple(queries.shape)} {queries.dtype}")
+    if queries.dtype == torch.float32:
+        raise NativeError("dot_topk_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit MFMA "
+                          "operand)", _lib.MM_EUNSUPPORTED)
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise NativeError(f"dot_topk_fp8: codes: expected [N, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
+    N = codes.shape[0]
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (N,):
+        raise NativeError(f"dot_topk_fp8: scales: expected [{N}] float32 (one per row of codes), got "
+                          f"{tuple(scales.shape)} {scales.dtype}")
+    nq, E = queries.shape
+    _same_width(E, codes.shape[1])
+    queries, codes, scales = queries.contiguous(), codes.contiguous(), scales.contiguous()
+    L = _lib.lib()
+
+    def call(q, n, scale, s, i, st, ws, wsb, stream):
+        return L.mm_dot_topk_fp8_fwd(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s, i,
+                                     st, ws, wsb, stream), "mm_dot_topk_fp8_fwd"
+
+    return _topk_reruns("dot_topk_fp8", dev, queries, N, k, max_rounds, L.mm_dot_topk_fp8_workspace_bytes, call)
 
 
 def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Tensor, probes: torch.Tensor, k: int):

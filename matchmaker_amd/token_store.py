@@ -19,8 +19,13 @@ rows in place (no gather, no padding).
 fp8 mode (opt-in): the store is `codes` [T, E] uint8 (OCP e4m3fn) + `scales` [T] float32 (one power of two per
 row) instead of the 16-bit matrix — half the resident bytes (158 GB -> 81 GB for MS MARCO at dim 128) and half the bytes the
 MaxSim stage streams.  `quantize_fp8()`, `from_reference_parts(..., fp8=True)`, `load(..., fp8=True)` and `load_fp8()` build
-one; aggregate / rank_hits / search_device / search then score through ops.maxsim_ragged_fp8.  The token search still needs
-16-bit rows: pass `index=` (an indexer that holds its own vectors) or keep them with `keep_tokens=True`.
+one; aggregate / rank_hits / search_device / search then score through ops.maxsim_ragged_fp8.  The token search runs on the
+codes themselves with `token_search="fp8"` (ops.dot_topk_fp8): an fp8-ONLY store then retrieves end to end and
+the memory figure holds for the whole of search().  Without it the token search needs 16-bit rows, as before: `index=` (an
+indexer that holds its own vectors) or the rows kept with `keep_tokens=True`.
+`row_shard=` runs a flat token search (16-bit or fp8) over consecutive shards of that many rows and merges the per-shard
+lists (ops.topk_merge): the one-call search places its sampled threshold only up to about 1.3 M rows at k' = 128
+(DESIGN §3.12); `row_shard = 2**20` is the recommended setting for stores beyond that.
 """
 import glob
 import os
@@ -35,7 +40,8 @@ from . import ops
 class TokenStore:
     def __init__(self, tokens: Optional[torch.Tensor], seq_ids: Sequence, begin: np.ndarray, end: np.ndarray,
                  topk_fn=None, candidates_fn=None, maxsim_fn=None, merge_fn=None, *, codes: Optional[torch.Tensor] = None,
-                 scales: Optional[torch.Tensor] = None, source_dtype: Optional[torch.dtype] = None, quantize_fn=None):
+                 scales: Optional[torch.Tensor] = None, source_dtype: Optional[torch.dtype] = None, quantize_fn=None,
+                 topk_fp8_fn=None):
         """topk_fn(queries, matrix, k) / candidates_fn(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap) /
         maxsim_fn(q, tokens, begin, end, None, pairs_per_query=, check_ranges=, sim_round=) / merge_fn(scores, ids, k) are what
         search() runs; they default to ops.dot_topk / ops.colbert_candidates / ops.maxsim_ragged / ops.topk_merge (the CPU
@@ -44,7 +50,8 @@ class TokenStore:
         may then be None (the 16-bit rows are not resident) or the rows kept for the token search.  maxsim_fn is then called as
         maxsim_fn(q, codes, scales, begin, end, None, pairs_per_query=, check_ranges=, sim_round=) and defaults to
         ops.maxsim_ragged_fp8; source_dtype is the dtype the rows were quantised from (it picks the query's 16-bit type);
-        quantize_fn(x) -> (codes, scales) is what quantize_fp8() and the fp8 loaders run (default ops.fp8_quantize_rows)."""
+        quantize_fn(x) -> (codes, scales) is what quantize_fp8() and the fp8 loaders run (default ops.fp8_quantize_rows);
+        topk_fp8_fn(q16, codes, scales, k) is the token search of token_search="fp8" (default ops.dot_topk_fp8)."""
         self._fp8 = codes is not None
         if self._fp8:
             if scales is None or codes.dim() != 2 or codes.dtype != torch.uint8 or tuple(scales.shape) != (codes.shape[0],):
@@ -58,6 +65,7 @@ class TokenStore:
         self._maxsim = maxsim_fn if maxsim_fn is not None else (ops.maxsim_ragged_fp8 if self._fp8 else ops.maxsim_ragged)
         self._merge = merge_fn if merge_fn is not None else ops.topk_merge
         self._quantize = quantize_fn if quantize_fn is not None else ops.fp8_quantize_rows
+        self._topk_fp8 = topk_fp8_fn if topk_fp8_fn is not None else ops.dot_topk_fp8
         self._tokens = tokens                         # [T, E] on the scoring device (read-only: the ranges below were validated against it)
         self._tokens_lowp = None                      # fp16 image of an fp32 store, built on the first use_fp16 aggregate()
         self._codes, self._scales = codes, scales
@@ -176,7 +184,7 @@ class TokenStore:
         codes, scales = self._quantize(self._tokens)
         return TokenStore(self._tokens if keep_tokens else None, self.seq_ids, self._begin, self._end, topk_fn=self._topk,
                           candidates_fn=self._candidates, maxsim_fn=maxsim_fn, merge_fn=self._merge, codes=codes, scales=scales,
-                          source_dtype=self._tokens.dtype, quantize_fn=self._quantize)
+                          source_dtype=self._tokens.dtype, quantize_fn=self._quantize, topk_fp8_fn=self._topk_fp8)
 
     def save_fp8(self, folder: str) -> None:
         """Writes an fp8 store with numpy: codes.npy [T, E] uint8, scales.npy [T] float32 and docs.npz (seq_ids, begin, end,
@@ -268,28 +276,50 @@ class TokenStore:
 
     # ------------------------------------------------------------------ retrieval: query token vectors -> ranked documents
     def token_hits(self, query_vecs: torch.Tensor, token_top_k: int, index=None,
-                   query_chunk: Optional[int] = None) -> torch.Tensor:
+                   query_chunk: Optional[int] = None, token_search: Optional[str] = None,
+                   row_shard: Optional[int] = None) -> torch.Tensor:
         """Steps 1-3 of search_device: hit_rows [nq, Q * token_top_k] int64 = for every LIVE query token (a vector with a
         non-zero element; `search_type="encode"` multiplies by the mask, so padding is zero rows) the exact token_top_k rows of
         the store by inner product of the 16-bit values (ops.dot_topk: equal scores go to the lower row), -1 for dead tokens.
         index: an IVFFlatIPIndexer built with index_resident(ids=arange(T), vectors=tokens), so that its ids are token rows
         (its probed lists are then searched instead of the whole matrix).  query_chunk bounds the tokens per search call.
-        An fp8 store has no fp8 token search: it needs index=, or the rows kept by keep_tokens=True."""
+        token_search="fp8" (an fp8 store only, not together with index=): the search runs over codes + scales
+        (ops.dot_topk_fp8; the query in the 16-bit type of the rows the store was quantised from, fp16 for an fp32 source), so an
+        fp8-only store needs neither index= nor keep_tokens=True.  None: the 16-bit search as before — an fp8 store then
+        needs index=, or the rows kept by keep_tokens=True.
+        row_shard (a positive multiple of 64; the flat searches only, not with index=): the rows are searched in consecutive
+        shards of row_shard rows and a running [n, k] list is merged with each shard's result (ops.topk_merge, the running
+        list first: equal scores still go to the lower row).  None: one call.  2**20 is the recommended shard for stores
+        beyond the one-call envelope of DESIGN §3.12."""
         nq, Q, E = query_vecs.shape
         k = int(token_top_k)
         if k < 1 or Q * k > ops.COLBERT_MAX_HITS:
             raise ops.NativeError(f"TokenStore.search: Q * token_top_k = {Q} * {k} hits per query outside 1 .. "
                                   f"{ops.COLBERT_MAX_HITS} (the candidate kernel sorts a query's hits in 64 KB of LDS)",
                                   ops._lib.MM_EUNSUPPORTED)
-        if self._tokens is None and index is None:
+        if token_search is not None:
+            if token_search != "fp8":
+                raise ops.NativeError(f"TokenStore.token_hits: token_search={token_search!r} (None or \"fp8\")")
+            if not self._fp8:
+                raise ops.NativeError("TokenStore.token_hits: token_search=\"fp8\" needs an fp8 store (quantize_fp8() makes one)")
+            if index is not None:
+                raise ops.NativeError("TokenStore.token_hits: token_search= and index= are two searches — pass one")
+        if row_shard is not None:
+            if index is not None:
+                raise ops.NativeError("TokenStore.token_hits: row_shard= shards the flat search — not with index=")
+            if int(row_shard) != row_shard or row_shard <= 0 or row_shard % 64:
+                raise ops.NativeError(f"TokenStore.token_hits: row_shard={row_shard!r} must be a positive multiple of 64")
+        fp8_search = token_search == "fp8"
+        if self._tokens is None and index is None and not fp8_search:
             raise ops.NativeError("TokenStore.token_hits: an fp8 store holds no 16-bit rows to search — pass index= (an "
-                                  "indexer over the token rows) or build the store with keep_tokens=True",
+                                  "indexer over the token rows) or build the store with keep_tokens=True"
+                                  " (or search the codes themselves: token_search=\"fp8\")",
                                   ops._lib.MM_EUNSUPPORTED)
         dev = self._device
         q = query_vecs.to(dev).reshape(nq * Q, E)
         live = torch.nonzero((q != 0).any(dim=1)).flatten()
         hits = torch.full((nq * Q, k), -1, dtype=torch.int64, device=dev)
-        if self._tokens is None:                         # fp8 store + index: the dtype the 16-bit matrix would have had
+        if self._tokens is None or fp8_search:           # fp8 store + index / fp8 search: the dtype the 16-bit matrix would have had
             matrix = None
             qs = q.to(self._source_dtype if self._source_dtype != torch.float32 else torch.float16)
         else:
@@ -298,9 +328,33 @@ class TokenStore:
         step = int(query_chunk) if query_chunk else max(int(live.numel()), 1)
         for a in range(0, int(live.numel()), step):
             sel = live[a: a + step]
-            rows = index.search_device(qs[sel], k)[1] if index is not None else self._topk(qs[sel].contiguous(), matrix, k)[1]
+            if index is not None:
+                rows = index.search_device(qs[sel], k)[1]
+            else:
+                rows = self._flat_search(qs[sel].contiguous(), matrix, k, fp8_search, row_shard)
             hits[sel] = rows
         return hits.view(nq, Q * k)
+
+    def _flat_search(self, q16: torch.Tensor, matrix: Optional[torch.Tensor], k: int, fp8_search: bool,
+                     row_shard: Optional[int]) -> torch.Tensor:
+        """rows [n, k] of the flat token search: over codes + scales (fp8_search) or the 16-bit matrix, in one call or in
+        consecutive shards of row_shard rows merged into a running list (see token_hits())."""
+        def one(lo, hi):
+            if fp8_search:
+                return self._topk_fp8(q16, self._codes[lo:hi], self._scales[lo:hi], k)
+            return self._topk(q16, matrix[lo:hi], k)
+        T = self._n_rows
+        if row_shard is None or row_shard >= T:
+            return one(0, T)[1]
+        run_s = run_i = None
+        for lo in range(0, T, int(row_shard)):
+            s, i = one(lo, min(lo + int(row_shard), T))
+            i = torch.where(i >= 0, i + lo, i)           # -1 (a shard shorter than k) stays -1
+            if run_s is None:
+                run_s, run_i = s, i
+            else:                                        # the running list first: input order on ties = lower row first
+                run_s, run_i = self._merge(torch.cat([run_s, s], dim=1), torch.cat([run_i, i], dim=1), k)
+        return run_i
 
     def rank_hits(self, query_vecs: torch.Tensor, hit_rows: torch.Tensor, top_n: int, use_fp16: bool = True,
                   trim: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -332,9 +386,11 @@ class TokenStore:
         return self._merge(scores, cand_doc.to(torch.int64), int(top_n))
 
     def search_device(self, query_vecs: torch.Tensor, top_n: int, token_top_k: int, use_fp16: bool = True, index=None,
-                      query_chunk: Optional[int] = None, trim: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+                      query_chunk: Optional[int] = None, trim: bool = True, token_search: Optional[str] = None,
+                      row_shard: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """ColBERT retrieval (dense_retrieval.py:391-412) for query_vecs [nq, Q, E], without a host round trip per query:
-          1-3. token_hits(): the token_top_k best token rows of every live query token;
+          1-3. token_hits(): the token_top_k best token rows of every live query token (token_search / row_shard as there:
+               token_search="fp8" makes the whole retrieval run on an fp8-only store);
           4.   the candidates = the documents that own at least one hit row (ops.colbert_candidates);
           5.   one read-back of the largest candidate count, to trim the slots (trim=False: none, see rank_hits());
           6.   forward_aggregation of the query against every candidate, exactly as aggregate() computes it (use_fp16 as
@@ -342,14 +398,17 @@ class TokenStore:
           7.   the top_n by score, equal scores to the lower document index.
         Returns (scores [nq, top_n] float32 descending, doc_idx [nq, top_n] int64 = positions in self.seq_ids); (-inf, -1)
         where a query has fewer than top_n candidates."""
-        hits = self.token_hits(query_vecs, token_top_k, index=index, query_chunk=query_chunk)
+        hits = self.token_hits(query_vecs, token_top_k, index=index, query_chunk=query_chunk, token_search=token_search,
+                               row_shard=row_shard)
         return self.rank_hits(query_vecs, hits, top_n, use_fp16=use_fp16, trim=trim)
 
     def search(self, query_vecs: torch.Tensor, top_n: int, token_top_k: int, use_fp16: bool = True, index=None,
-               query_chunk: Optional[int] = None) -> List[List[Tuple[object, float]]]:
+               query_chunk: Optional[int] = None, token_search: Optional[str] = None,
+               row_shard: Optional[int] = None) -> List[List[Tuple[object, float]]]:
         """search_device() mapped to the reference's result shape: per query [(seq_id, score)] best first, like
         `validation_results[query_id]` (:410-412); shorter than top_n when the query has fewer candidates."""
-        s, d = self.search_device(query_vecs, top_n, token_top_k, use_fp16=use_fp16, index=index, query_chunk=query_chunk)
+        s, d = self.search_device(query_vecs, top_n, token_top_k, use_fp16=use_fp16, index=index, query_chunk=query_chunk,
+                                  token_search=token_search, row_shard=row_shard)
         s, d = s.cpu().numpy(), d.cpu().numpy()
         ids = self.seq_ids
         return [[(ids[j], float(x)) for x, j in zip(s[i], d[i]) if j >= 0] for i in range(s.shape[0])]
