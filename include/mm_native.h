@@ -835,6 +835,36 @@ int mm_dot_topk_fp8_fwd(const void* queries, const uint8_t* codes, const float* 
                         int q_dtype, int k, float m_scale, float* out_scores, int64_t* out_idx, int32_t* status,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * fp8 IVF list scan: mm_ivf_scan_fwd over lists held as an fp8 store (additive: MM_ABI_VERSION unchanged).
+ *
+ * Replaces, for lists held as codes + scales, the same reference lines as mm_ivf_scan_fwd:
+ *           the list scan of FaissIVFIndexer.search      matchmaker/retrieval/faiss_indices.py:106-145
+ *           (the coarse quantiser stays mm_dot_topk_fwd over the 16-bit centroids).
+ *
+ *   score(q, t) = scales[t] * sum_k queries[q, k] * deq(codes[t, k])   for every row t of the lists named in probes[q, :]
+ *   codes [n_rows, E] uint8 (OCP e4m3fn) + scales [n_rows] float32 powers of two as mm_fp8_quantize_rows writes them,
+ *   stored list by list: list l is the rows list_begin[l] .. list_begin[l + 1] (list_begin [nlist + 1] int64, non-decreasing;
+ *   lists may be empty).  queries [nq, E] MM_F16 or MM_BF16 (MM_F32 returns MM_EUNSUPPORTED) and NOT quantised;
+ *   E in {128, 256, 384, 512, 768}.  The codes are converted to the query's type in registers (exact) and multiplied on
+ *   the 16-bit MFMA: every product is exact, the sum is fp32, and the row's scale multiplies the finished dot product
+ *   (exact) before the score is written.
+ *   probes / out_scores / out_rows (rows of `codes`) / the EXACT top-k of the probed union / the tie rule (score
+ *   descending, lower row first) / the (-inf, -1) padding / k <= 4096, nprobe <= 4096, n_rows and nq * nprobe below 2^31 /
+ *   one enqueue on `stream` with no read-back and no allocation (graph-capturable as a single chain) are
+ *   mm_ivf_scan_fwd's.  queries and codes 16-byte aligned, scales 4-byte aligned.  No load uses a row index >= n_rows:
+ *   rows past the end of a list's partial last 32-row block are clamped into the list, codes and scale alike, and never
+ *   written.  No floating-point atomics in scoring: two calls give the same bits.
+ *   workspace: mm_ivf_scan_fp8_workspace_bytes(...) = mm_ivf_scan_workspace_bytes(n_rows, nlist, nq, nprobe, k) bytes; one
+ *   byte less returns MM_EWORKSPACE with nothing written. */
+size_t mm_ivf_scan_fp8_workspace_bytes(int64_t n_rows, int nlist, int nq, int nprobe, int k);
+
+int mm_ivf_scan_fp8_fwd(const void* queries, const uint8_t* codes, const float* scales,
+                        const int64_t* list_begin, const int32_t* probes,
+                        int64_t n_rows, int nlist, int nq, int nprobe, int E, int q_dtype, int k,
+                        float* out_scores, int64_t* out_rows,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,8 @@ SIGNATURES = {
     "mm_maxsim_ragged_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_dot_topk_fp8_workspace_bytes": (_sz, [_i64, _i, _i]),
     "mm_dot_topk_fp8_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _c.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mm_ivf_scan_fp8_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
+    "mm_ivf_scan_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,4 +1,5 @@
-// Shared scaffolding of the list-major scans (ivf_scan.hip: 16-bit rows; ah_scan.hip: 4-bit codes): the ragged candidate
+// Shared scaffolding of the list-major scans (ivf_scan.hip: 16-bit rows; ah_scan.hip: 4-bit codes; ivf_scan_fp8.hip: e4m3fn
+// codes + row scales): the ragged candidate
 // rows, the 32-row task table, the rounds, the counting sort of the (query, list) pairs by list and the exact radix
 // selection.  A scan supplies its own score kernel (one wavefront per 32-row block of a list, which writes every
 // candidate score of the round) and runs through ivf_run.  Kernels have internal linkage: every translation unit that
@@ -41,11 +42,12 @@ inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct IvfArgs {
   const void* q;            // [nq, E]
-  const void* v;            // [n, E] rows (ivf_scan) / [n, E / 4] codes (ah_scan)
+  const void* v;            // [n, E] rows (ivf_scan) / [n, E / 4] codes (ah_scan) / [n, E] e4m3fn codes (ivf_scan_fp8)
   const int64_t* lb;        // [nlist + 1]
   const int32_t* probes;    // [nq, nprobe]
   const void* codebook;     // ah_scan: [E / 2, 16, 2], the dtype of q
   const float* probe_scores;  // ah_scan: [nq, nprobe] added to every score of the pair's list
+  const float* scales;      // ivf_scan_fp8: [n] power-of-two row scales, multiplied into the finished dot product
   int64_t n;
   int nlist, nq, nprobe, k;
   int64_t S;

@@ -1,0 +1,135 @@
+// IVF list scan over an fp8 token store (codes + row scales) for MI355X (gfx950 / CDNA4).
+//
+// The fp8 twin of ivf_scan.hip: the same reference lines (the list scan of FaissIVFIndexer.search,
+// matchmaker/retrieval/faiss_indices.py:106-145), the same semantics (for every query the EXACT k best scores over the union
+// of the lists named in its probe row, descending, lower row first on equal scores), with the lists held as the fp8 token
+// store holds its rows: codes [n, E] OCP e4m3fn bytes + scales [n] float32 powers of two (mm_fp8_quantize_rows), list by list.
+//
+//   score(q, t) = scales[t] * sum_k queries[q, k] * deq(codes[t, k])
+//
+// The preparation, the rounds, the grouping and the selection are ivf_device.h's, shared with ivf_scan.hip and ah_scan.hip;
+// the score kernel is this file's:
+//
+//   ivf_fp8_score_kernel   one wavefront per 32-row block of a list.  The block's codes are read ONCE (8 bytes per lane and
+//                          k-step: 128 NSL bytes per row, half of the 16-bit scan's), converted ONCE to the query's 16-bit
+//                          type (cvt8 at scale 1.0: exact) into the MFMA A fragments and multiplied against every query that
+//                          probes the list, 32 queries per v_mfma_f32_32x32x16 chain.  Every product is exact and the sum is
+//                          fp32.  A lane's 16 accumulators are 16 different rows, so the 32 row scales are fetched once per
+//                          block, one lane per row, and handed to the lanes that need them by 16 cross-lane reads — once per
+//                          block, not once per query tile.  The scale multiplies the FINISHED dot product (a power of two:
+//                          exact) before the score is stored.  No LDS, no atomics: two calls give the same bits.
+//
+// Bounds: a lane past the end of a partial last block reads the block's LAST row (codes and scale alike) and never stores;
+// no load uses a row index >= n_rows.
+#include "fp8_device.h"
+#include "ivf_device.h"
+
+namespace mm {
+using namespace ivf_dev;
+
+// A = the block's rows (lane (r, h): row r, codes 16 s + 8 h .. + 7 of k-step s, converted), B = 32 of the queries that probe
+// the list (lane (r, h): query r, same elements); D: lane's column = its query, register i = row (i & 3) + 8 (i >> 2) + 4 h.
+template <int DT, int NSL>
+__global__ void __launch_bounds__(256) ivf_fp8_score_kernel(const IvfArgs a, int round) {
+  constexpr int CB = NSL * 128;   // bytes per row of codes
+  constexpr int QB = NSL * 256;   // bytes per query
+  constexpr int KS = NSL * 8;     // k-steps of 16
+  const int qa = a.qbeg[round];
+  if (qa >= a.qbeg[round + 1]) return;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t t = (int64_t)blockIdx.x * 4 + w;
+  if (t >= a.tstart[a.nlist]) return;
+  const int l = a.blk_list[t];
+  const int nqs = a.cnt[l];
+  if (nqs == 0) return;
+  int64_t lb, len;
+  ivf_list_range(a, l, &lb, &len);
+  const int row0 = (int)(t - a.tstart[l]) * 32;
+  const int rows = (int)(len - row0 < 32 ? len - row0 : 32);   // >= 1 by construction of the task table
+  if (rows <= 0) return;
+  const int64_t base0 = a.prefix[qa];
+
+  short8 af[KS];
+  float sc[16];
+  {
+    const int64_t trow = lb + row0 + (r < rows ? r : rows - 1);   // never past the list
+    const uint8_t* arow = (const uint8_t*)a.v + trow * CB + h * 8;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) af[s] = cvt8<DT>(*(const u32x2*)(arow + s * 16));
+    // lane r (h = 0) holds the scale of row r; register i of a lane is row (i & 3) + 8 (i >> 2) + 4 h
+    const float mine = h == 0 ? a.scales[trow] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sc[i] = __shfl(mine, (i & 3) + 8 * (i >> 2) + 4 * h, 64);
+  }
+  const int32_t* pl = a.pairs + a.start[l];
+  for (int t0 = 0; t0 < nqs; t0 += 32) {
+    const int qi = t0 + r < nqs ? t0 + r : nqs - 1;
+    const int64_t p = pl[qi];
+    const int q = (int)(p / a.nprobe);
+    const char* qrow = (const char*)a.q + (int64_t)q * QB + h * 16;
+    f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
+#pragma unroll
+    for (int s = 0; s < KS; s += 2) {
+      acc0 = IvfMfma<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
+      acc1 = IvfMfma<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
+    }
+    if (t0 + r < nqs) {
+      float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+        if (row < rows) dst[row] = (acc0[i] + acc1[i]) * sc[i];
+      }
+    }
+  }
+}
+
+template <int DT>
+static int ivf_fp8_launch_score(const IvfArgs& a, int round, int E, unsigned grid, hipStream_t stream) {
+  switch (E) {
+    case 128: hipLaunchKernelGGL((ivf_fp8_score_kernel<DT, 1>), dim3(grid), dim3(256), 0, stream, a, round); break;
+    case 256: hipLaunchKernelGGL((ivf_fp8_score_kernel<DT, 2>), dim3(grid), dim3(256), 0, stream, a, round); break;
+    case 384: hipLaunchKernelGGL((ivf_fp8_score_kernel<DT, 3>), dim3(grid), dim3(256), 0, stream, a, round); break;
+    case 512: hipLaunchKernelGGL((ivf_fp8_score_kernel<DT, 4>), dim3(grid), dim3(256), 0, stream, a, round); break;
+    case 768: hipLaunchKernelGGL((ivf_fp8_score_kernel<DT, 6>), dim3(grid), dim3(256), 0, stream, a, round); break;
+    default: return set_error(MM_EUNSUPPORTED, "ivf_scan_fp8: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
+  }
+  return check_launch("ivf_fp8_score_kernel");
+}
+
+}  // namespace mm
+
+using namespace mm;
+
+extern "C" size_t mm_ivf_scan_fp8_workspace_bytes(int64_t n_rows, int nlist, int nq, int nprobe, int k) {
+  (void)k;
+  return ivf_workspace_bytes(n_rows, nlist, nq, nprobe);
+}
+
+extern "C" int mm_ivf_scan_fp8_fwd(const void* queries, const uint8_t* codes, const float* scales, const int64_t* list_begin,
+                                   const int32_t* probes, int64_t n_rows, int nlist, int nq, int nprobe, int E, int q_dtype,
+                                   int k, float* out_scores, int64_t* out_rows, void* workspace, size_t workspace_bytes,
+                                   void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!queries || !list_begin || !probes || !out_scores || !out_rows || ((!codes || !scales) && n_rows > 0))
+    return set_error(MM_EINVAL, "ivf_scan_fp8: null pointer");
+  if (q_dtype == MM_F32)
+    return set_error(MM_EUNSUPPORTED, "ivf_scan_fp8: the query is fp16 or bf16 (an fp32 query has no exact 16-bit MFMA operand)");
+  if (int e = ivf_check("ivf_scan_fp8", n_rows, nlist, nq, nprobe, E, q_dtype, k)) return e;
+  if ((((uintptr_t)queries | (uintptr_t)codes) & 15) || ((uintptr_t)scales & 3))
+    return set_error(MM_EINVAL, "ivf_scan_fp8: queries / codes must be 16-byte aligned, scales 4-byte aligned");
+  const size_t need = mm_ivf_scan_fp8_workspace_bytes(n_rows, nlist, nq, nprobe, k);
+  if (!workspace || workspace_bytes < need) return set_error(MM_EWORKSPACE, "ivf_scan_fp8: workspace needs %zu bytes", need);
+
+  IvfArgs a{};
+  a.q = queries; a.v = codes; a.scales = scales; a.lb = list_begin; a.probes = probes;
+  a.n = n_rows; a.nlist = nlist; a.nq = nq; a.nprobe = nprobe; a.k = k;
+  a.out_s = out_scores; a.out_r = out_rows;
+  return ivf_run(a, workspace, stream, "ivf_scan_fp8", [&](const IvfArgs& b, int r, const IvfGeom& g) {
+    const unsigned grid_score = (unsigned)((g.max_tasks + 3) / 4);
+    return q_dtype == MM_BF16 ? ivf_fp8_launch_score<MM_BF16>(b, r, E, grid_score, stream)
+                              : ivf_fp8_launch_score<MM_F16>(b, r, E, grid_score, stream);
+  });
+}

@@ -970,6 +970,52 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     return out_s, out_r
 
 
+def ivf_scan_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, list_begin: torch.Tensor,
+                 probes: torch.Tensor, k: int):
+    """ivf_scan over lists held as an fp8 token store (mm_ivf_scan_fp8_fwd; the same reference lines as ivf_scan):
+    codes [n, E] uint8 + scales [n] float32 as fp8_quantize_rows writes them, stored list by list (list l = rows
+    list_begin[l] .. list_begin[l + 1]); queries [nq, E] fp16 or bf16 (NOT quantised: the codes are converted to the
+    query's type in registers, exactly, and the row scale multiplies the finished fp32 dot product).  score[q, t] =
+    scales[t] * <queries[q], deq(codes[t])> for every row t of the lists in probes[q] ([nq, nprobe] int32, -1 = no list; a
+    list named twice in one row: undefined result, memory stays in bounds).  E in {128, 256, 384, 512, 768}.  Returns
+    (scores [nq, k] float32 descending, rows [nq, k] int64 rows of `codes`; -inf / -1 padded when the probed lists hold
+    fewer than k rows; equal scores: lower row first).  One enqueue on the current stream, no read-back: graph-capturable."""
+    dev = _dev_check(queries, codes, scales, list_begin, probes)
+    if queries.dim() != 2 or queries.dtype not in _DT:
+        raise NativeError(f"ivf_scan_fp8: queries: expected [nq, E] float16 / bfloat16, got {tuple(queries.shape)} {queries.dtype}")
+    if queries.dtype == torch.float32:
+        raise NativeError("ivf_scan_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit MFMA "
+                          "operand)", _lib.MM_EUNSUPPORTED)
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise NativeError(f"ivf_scan_fp8: codes: expected [n, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
+    n = codes.shape[0]
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (n,):
+        raise NativeError(f"ivf_scan_fp8: scales: expected [{n}] float32 (one per row of codes), got "
+                          f"{tuple(scales.shape)} {scales.dtype}")
+    nq, E = queries.shape
+    _same_width(E, codes.shape[1])
+    _native_width("ivf_scan_fp8", E)
+    _list_begin_check("ivf_scan_fp8", list_begin)
+    _probes_check("ivf_scan_fp8", probes, nq)
+    _k_range("ivf_scan_fp8", k, probes.shape[1])
+    queries, codes, scales = queries.contiguous(), codes.contiguous(), scales.contiguous()
+    list_begin, probes = list_begin.contiguous(), probes.contiguous()
+    nlist, nprobe = list_begin.shape[0] - 1, probes.shape[1]
+    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    if nq == 0:
+        return out_s, out_r
+    L = _lib.lib()
+    with _on(dev):
+        wsb = _ws_bytes(L.mm_ivf_scan_fp8_workspace_bytes, n, nlist, nq, nprobe, k)
+        ws = _workspace(dev, wsb)
+        rc = L.mm_ivf_scan_fp8_fwd(queries.data_ptr(), codes.data_ptr() if n else None, scales.data_ptr() if n else None,
+                                   list_begin.data_ptr(), probes.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
+                                   out_s.data_ptr(), out_r.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
+    _lib.check(rc, "mm_ivf_scan_fp8_fwd")
+    return out_s, out_r
+
+
 def _ah_codebook_check(what: str, codebook: torch.Tensor, E: int, dtype):
     if codebook.dim() != 3 or tuple(codebook.shape) != (E // 2, 16, 2) or codebook.dtype != dtype:
         raise NativeError(f"{what}: codebook must be {dtype} [{E // 2}, 16, 2], got {codebook.dtype} {tuple(codebook.shape)}")

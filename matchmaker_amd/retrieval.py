@@ -13,6 +13,9 @@ IVFFlatIPIndexer (faiss_index_type: ivf) has the surface of `FaissIVFIndexer` (f
 k-means centroids, the shard stored list by list, probe selection with the same top-k kernel and the exact scan of
 the probed lists by mm_ivf_scan_fwd.
 
+IVFFp8IPIndexer is IVFFlatIPIndexer with the lists held as the fp8 token store holds its rows (e4m3fn codes + one power-of-two
+scale per row) and scanned by mm_ivf_scan_fp8_fwd: the token index of an fp8-only ColBERT store at half the bytes.
+
 DynamicIVFIndexer has the surface of `FaissDynamicIndexer` (faiss_indices.py:307-428), the index behind TAS-Balanced query
 clustering (matchmaker/distillation/query_clusterer.py:187-221): k-means over the query vectors, one probe, entries that
 can be replaced.  Its k-means (`spherical_kmeans`) runs on mm_kmeans_assign / mm_kmeans_segment_sum; IVFFlatIPIndexer
@@ -425,6 +428,7 @@ class IVFFlatIPIndexer(_ShardedIndex):
 
     def load(self, path: str, config_overwrites=None):
         """faiss_indices.py:143-145: the probe count comes from config_overwrites["faiss_ivf_search_probe_count"]."""
+        _refuse_other_ivf_archive(self._rank_path(path), _IVF_FP8_MAGIC, "an IVFFlatIPIndexer", "IVFFp8IPIndexer")
         z = self._read_archive(self._rank_path(path), "an IVFFlatIPIndexer", _IVF_MAGIC, _IVF_FORMAT, "centroids",
                                rebuild_with="prepare() / index()")
         self.centroids = torch.from_numpy(z["centroids"]).to(self.device)
@@ -435,6 +439,130 @@ class IVFFlatIPIndexer(_ShardedIndex):
         self.nprobe = int(z["nprobe"])
         if config_overwrites is not None and "faiss_ivf_search_probe_count" in config_overwrites:
             self.nprobe = int(config_overwrites["faiss_ivf_search_probe_count"])
+
+
+_IVF_FP8_MAGIC = "matchmaker_amd.IVFFp8IPIndexer"
+_IVF_FP8_FORMAT = 1
+
+
+class IVFFp8IPIndexer(IVFFlatIPIndexer):
+    """IVFFlatIPIndexer whose lists hold the fp8 token store's rows: `codes` [n, E_pad] uint8 (OCP e4m3fn) +
+    `scales` [n] float32 (one power of two per row) list by list, with `ids` and `list_begin` as before — half the bytes of
+    the 16-bit lists, and no 16-bit copy of the rows.  Training, the centroid table (16-bit), the probe selection, the
+    sharding and the merge are inherited; the probed lists are scanned by ops.ivf_scan_fp8 (the EXACT top_n of
+    scale * <query, deq(code)> over their union).
+
+    One assignment rule: a row goes to the list of the maximum-inner-product centroid of the value the index STORES,
+    deq(code) * scale as float16 — whether it arrives as 16-bit vectors (index / index_resident: quantised first) or as
+    codes + scales (index_codes), so the two build bit-equal indices.  `save` / `load` use an archive of their own."""
+
+    DEQ_CHUNK = 1 << 20          # rows dequantised to float16 at a time (assignment, training sample)
+
+    def __init__(self, config, device=None, group=None, topk_fn=None, scan_fn=None, merge_fn=None, native_kmeans: bool = False,
+                 assign_fn=None, sum_fn=None, quantize_fn=None):
+        """As IVFFlatIPIndexer, with scan_fn(queries, codes, scales, list_begin, probes, k) defaulting to ops.ivf_scan_fp8
+        and quantize_fn(x) -> (codes, scales) to ops.fp8_quantize_rows."""
+        super().__init__(config, device=device, group=group, topk_fn=topk_fn,
+                         scan_fn=scan_fn if scan_fn is not None else ops.ivf_scan_fp8, merge_fn=merge_fn,
+                         native_kmeans=native_kmeans, assign_fn=assign_fn, sum_fn=sum_fn)
+        self._quantize = quantize_fn if quantize_fn is not None else ops.fp8_quantize_rows
+        self.codes: Optional[torch.Tensor] = None             # [n_local, E_pad] uint8 list by list
+        self.scales: Optional[torch.Tensor] = None            # [n_local] float32, same order
+
+    @property
+    def vectors(self):
+        raise ops.NativeError("IVFFp8IPIndexer.vectors: the lists hold no 16-bit rows — read .codes / .scales "
+                              "(ops.fp8_dequantize_rows gives their values)")
+
+    @vectors.setter
+    def vectors(self, value):                                 # the base constructor's `self.vectors = None` lands here
+        if value is not None:
+            raise ops.NativeError("IVFFp8IPIndexer.vectors: the lists hold no 16-bit rows — fill the index with "
+                                  "index_resident() / index_codes(), which set .codes / .scales")
+
+    def _check_codes(self, what: str, codes: torch.Tensor, scales: torch.Tensor):
+        if (codes.dim() != 2 or codes.dtype != torch.uint8 or codes.shape[1] != self.E_pad or scales.dtype != torch.float32
+                or tuple(scales.shape) != (codes.shape[0],)):
+            raise ops.NativeError(f"IVFFp8IPIndexer.{what}: need uint8 [n, {self.E_pad}] codes and float32 [n] scales, got "
+                                  f"{codes.dtype} {tuple(codes.shape)} / {scales.dtype} {tuple(scales.shape)}")
+
+    def train_codes(self, codes: torch.Tensor, scales: torch.Tensor, subsample=-1):
+        """train_resident() on rows that arrive as an fp8 store: the seeded sample (all rows without a subsample in (0, 1))
+        dequantised to float16."""
+        self._check_codes("train_codes", codes, scales)
+        gen = torch.Generator().manual_seed(self.seed)
+        keep = self._train_rows(codes.shape[0], subsample, gen)
+        self._check_train_size(codes.shape[0] if keep is None else keep.numel())
+        if keep is not None:
+            keep = keep.to(codes.device)
+            codes, scales = codes[keep], scales[keep]
+        x = torch.cat([ops.fp8_dequantize_rows(codes[a: a + self.DEQ_CHUNK], scales[a: a + self.DEQ_CHUNK], self.dtype)
+                       for a in range(0, max(codes.shape[0], 1), self.DEQ_CHUNK)])
+        self._train(x, gen)
+
+    def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        """This rank's shard as device tensors (vectors [n_local, E_pad] float16, ids [n_local] int64): quantised, then
+        index_codes."""
+        self._check_resident(ids, vectors)
+        self.index_codes(ids, *self._quantize(vectors.contiguous()))
+
+    def index_codes(self, ids: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor):
+        """This rank's shard as an fp8 store (codes [n_local, E_pad] uint8, scales [n_local] float32, ids [n_local] int64):
+        every row goes to the list of the best centroid of deq(code) * scale as float16, DEQ_CHUNK rows at a time; the shard
+        is then stored list by list (stable: input order inside a list)."""
+        if self.centroids is None:
+            raise ops.NativeError("IVFFp8IPIndexer.index_codes: prepare() / train_codes() (or load()) first")
+        self._check_codes("index_codes", codes, scales)
+        if ids.shape[0] != codes.shape[0]:
+            raise ops.NativeError(f"IVFFp8IPIndexer.index_codes: {ids.shape[0]} ids for {codes.shape[0]} rows")
+        a = torch.empty(codes.shape[0], dtype=torch.int64, device=codes.device)
+        for lo in range(0, codes.shape[0], self.DEQ_CHUNK):
+            x = ops.fp8_dequantize_rows(codes[lo: lo + self.DEQ_CHUNK], scales[lo: lo + self.DEQ_CHUNK], self.dtype)
+            a[lo: lo + self.DEQ_CHUNK] = self._assign(x.contiguous(), self.centroids)
+        order, self.list_begin, _ = _lists_of(a, self.nlist)
+        self.codes = codes[order].contiguous()
+        self.scales = scales[order].contiguous()
+        self.ids = ids.to(torch.int64)[order].contiguous()
+
+    def search_device(self, query_vec, top_n: int, return_probes: bool = False):
+        """search() on device tensors; -inf / -1 where the probed lists ran out."""
+        qd = _device_queries(query_vec, self.dtype, self.E_pad, self.token_dim, self.device)
+        probes = self._topk(qd, self.centroids, min(self.nprobe, self.nlist))[1].to(torch.int32)
+        s, rows = self._scan(qd, self.codes, self.scales, self.list_begin, probes, top_n)
+        s, ids = self._finish(s, self._ids_of(rows), top_n)
+        return (s, ids, probes) if return_probes else (s, ids)
+
+    def save(self, path: str):
+        """One numpy .npz archive (this rank's shard; `path + ".rank<r>"` with several ranks)."""
+        self._write_archive(self._rank_path(path), _IVF_FP8_MAGIC, _IVF_FP8_FORMAT, nprobe=self.nprobe, centroids=self.centroids,
+                            list_begin=self.list_begin, codes=self.codes, scales=self.scales, ids=self.ids)
+
+    def load(self, path: str, config_overwrites=None):
+        """As IVFFlatIPIndexer.load: the probe count comes from config_overwrites["faiss_ivf_search_probe_count"]."""
+        p = self._rank_path(path)
+        _refuse_other_ivf_archive(p, _IVF_MAGIC, "an IVFFp8IPIndexer", "IVFFlatIPIndexer")
+        z = self._read_archive(p, "an IVFFp8IPIndexer", _IVF_FP8_MAGIC, _IVF_FP8_FORMAT, "centroids",
+                               rebuild_with="prepare() / index()")
+        self.centroids = torch.from_numpy(z["centroids"]).to(self.device)
+        self.list_begin = torch.from_numpy(z["list_begin"]).to(self.device)
+        self.codes = torch.from_numpy(z["codes"]).to(self.device)
+        self.scales = torch.from_numpy(z["scales"]).to(self.device)
+        self.ids = torch.from_numpy(z["ids"]).to(self.device)
+        self.nlist = self.centroids.shape[0]
+        self.nprobe = int(z["nprobe"])
+        if config_overwrites is not None and "faiss_ivf_search_probe_count" in config_overwrites:
+            self.nprobe = int(config_overwrites["faiss_ivf_search_probe_count"])
+
+
+def _refuse_other_ivf_archive(p: str, other_magic: str, what: str, other_class: str):
+    """The two IVF classes share a surface, not a file: an archive of the other one is refused by its writer's name."""
+    with open(p, "rb") as f:
+        if f.read(2) != b"PK":
+            return
+    z = np.load(p, allow_pickle=False)
+    if "magic" in z.files and str(z["magic"]) == other_magic:
+        raise ops.NativeError(f"{p} is not {what} file: it was written by {other_class} (load it with that class, or build "
+                              "the index again)")
 
 
 class DynamicIVFIndexer(_DeviceIndex):

@@ -21,8 +21,10 @@ row) instead of the 16-bit matrix — half the resident bytes (158 GB -> 81 GB f
 MaxSim stage streams.  `quantize_fp8()`, `from_reference_parts(..., fp8=True)`, `load(..., fp8=True)` and `load_fp8()` build
 one; aggregate / rank_hits / search_device / search then score through ops.maxsim_ragged_fp8.  The token search runs on the
 codes themselves with `token_search="fp8"` (ops.dot_topk_fp8): an fp8-ONLY store then retrieves end to end and
-the memory figure holds for the whole of search().  Without it the token search needs 16-bit rows, as before: `index=` (an
-indexer that holds its own vectors) or the rows kept with `keep_tokens=True`.
+the memory figure holds for the whole of search().  `build_token_index(config)` gives the IVF alternative to that brute-force
+search: for an fp8 store an IVFFp8IPIndexer whose lists are codes + scales as well (ops.ivf_scan_fp8), passed as
+`index=`.  Without either the token search needs 16-bit rows, as before: an `index=` that holds 16-bit vectors of its own, or
+the rows kept with `keep_tokens=True`.
 `row_shard=` runs a flat token search (16-bit or fp8) over consecutive shards of that many rows and merges the per-shard
 lists (ops.topk_merge): the one-call search places its sampled threshold only up to about 1.3 M rows at k' = 128
 (DESIGN §3.12); `row_shard = 2**20` is the recommended setting for stores beyond that.
@@ -275,18 +277,49 @@ class TokenStore:
         return self._source_dtype if self._source_dtype in (torch.float16, torch.bfloat16) else torch.bfloat16
 
     # ------------------------------------------------------------------ retrieval: query token vectors -> ranked documents
+    def build_token_index(self, config, subsample=-1, native_kmeans: bool = True, **fns):
+        """An IVF index over the token rows, for token_hits(index=) / search_device(index=): its ids are token rows.
+        config: the indexer's keys (faiss_ivf_list_count, faiss_ivf_search_probe_count, optionally random_seed); token_dim is
+        the store's width.  An fp8 store gets an IVFFp8IPIndexer trained on a seeded sample of the rows
+        dequantised to float16 (train_codes) and filled with index_codes(arange(T), codes, scales): the lists are a
+        list-ordered copy of codes + scales, no 16-bit row is ever resident.  A 16-bit store gets an IVFFlatIPIndexer trained
+        and filled with the float16 rows (train_resident / index_resident).  subsample in (0, 1) trains on that fraction of
+        the rows; fns: the indexer's *_fn arguments (the CPU test-suite injects stand-ins)."""
+        from .retrieval import IVFFlatIPIndexer, IVFFp8IPIndexer, _pad_dim
+        E = int(self._codes.shape[1] if self._fp8 else self._tokens.shape[1])
+        if _pad_dim(E) != E:
+            raise ops.NativeError(f"TokenStore.build_token_index: the store's width {E} is not one of 128, 256, 384, 512, 768 "
+                                  "(pad the rows)", ops._lib.MM_EUNSUPPORTED)
+        cfg = dict(config)
+        cfg["token_dim"] = E
+        ids = torch.arange(self._n_rows, dtype=torch.int64, device=self._device)
+        if self._fp8:
+            ix = IVFFp8IPIndexer(cfg, device=self._device, native_kmeans=native_kmeans, **fns)
+            ix.train_codes(self._codes, self._scales, subsample=subsample)
+            ix.index_codes(ids, self._codes, self._scales)
+        else:
+            fns.pop("quantize_fn", None)                 # (the 16-bit lists quantise nothing)
+            ix = IVFFlatIPIndexer(cfg, device=self._device, native_kmeans=native_kmeans, **fns)
+            rows = self._scoring_tokens(True)
+            rows = rows if rows.dtype == torch.float16 else rows.to(torch.float16)
+            ix.train_resident(rows, subsample=subsample)
+            ix.index_resident(ids, rows)
+        return ix
+
     def token_hits(self, query_vecs: torch.Tensor, token_top_k: int, index=None,
                    query_chunk: Optional[int] = None, token_search: Optional[str] = None,
                    row_shard: Optional[int] = None) -> torch.Tensor:
         """Steps 1-3 of search_device: hit_rows [nq, Q * token_top_k] int64 = for every LIVE query token (a vector with a
         non-zero element; `search_type="encode"` multiplies by the mask, so padding is zero rows) the exact token_top_k rows of
         the store by inner product of the 16-bit values (ops.dot_topk: equal scores go to the lower row), -1 for dead tokens.
-        index: an IVFFlatIPIndexer built with index_resident(ids=arange(T), vectors=tokens), so that its ids are token rows
-        (its probed lists are then searched instead of the whole matrix).  query_chunk bounds the tokens per search call.
+        index: an indexer whose ids are token rows — what build_token_index() returns (an IVFFp8IPIndexer over codes + scales
+        for an fp8 store, an IVFFlatIPIndexer for a 16-bit one), or an IVFFlatIPIndexer built by hand with
+        index_resident(ids=arange(T), vectors=tokens); its probed lists are then searched instead of the whole matrix.
+        query_chunk bounds the tokens per search call.
         token_search="fp8" (an fp8 store only, not together with index=): the search runs over codes + scales
         (ops.dot_topk_fp8; the query in the 16-bit type of the rows the store was quantised from, fp16 for an fp32 source), so an
         fp8-only store needs neither index= nor keep_tokens=True.  None: the 16-bit search as before — an fp8 store then
-        needs index=, or the rows kept by keep_tokens=True.
+        needs index= (build_token_index() makes one that holds fp8 lists), or the rows kept by keep_tokens=True.
         row_shard (a positive multiple of 64; the flat searches only, not with index=): the rows are searched in consecutive
         shards of row_shard rows and a running [n, k] list is merged with each shard's result (ops.topk_merge, the running
         list first: equal scores still go to the lower row).  None: one call.  2**20 is the recommended shard for stores
@@ -312,8 +345,8 @@ class TokenStore:
         fp8_search = token_search == "fp8"
         if self._tokens is None and index is None and not fp8_search:
             raise ops.NativeError("TokenStore.token_hits: an fp8 store holds no 16-bit rows to search — pass index= (an "
-                                  "indexer over the token rows) or build the store with keep_tokens=True"
-                                  " (or search the codes themselves: token_search=\"fp8\")",
+                                  "indexer over the token rows; build_token_index() makes an fp8 one) or build the store "
+                                  "with keep_tokens=True (or search the codes themselves: token_search=\"fp8\")",
                                   ops._lib.MM_EUNSUPPORTED)
         dev = self._device
         q = query_vecs.to(dev).reshape(nq * Q, E)
