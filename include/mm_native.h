@@ -745,6 +745,54 @@ int mm_matchpyramid_fwd(const float* q, const float* d, const float* conv_w, con
                         int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int n_layers, const int32_t* layers,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* MatchPyramid, training.  mm_matchpyramid_fwd_save is the forward above (the same instruction sequence for the values, in both
+ * kernel instantiations: `features` has the bits mm_matchpyramid_fwd gives) that additionally writes the state the backward
+ * routes through, so that no conv output is ever recomputed:
+ *
+ *   pooled  [n_pairs, S] float32, S = sum_l C_l ph_l pw_l: per pair, layer after layer, the layer's pooled output
+ *           [C_l, ph_l, pw_l] (the next layer's input; the last layer's block equals features[p])
+ *   argmax  [n_pairs, S] int32, the same layout: for every pooled element the flat index row * Wo + col into its channel's
+ *           conv-output plane (Ho x Wo = (H + k1 - k0) x (W + k0 - k1)), the convention of
+ *           F.adaptive_max_pool2d(return_indices=True).
+ *   Tie rule: the FIRST maximum in row-major order of the window, i.e. among equal candidates the lowest flat index, as torch
+ *           does on CPU and GPU.  The maximum is taken after ReLU, so a window without a positive value reports its first
+ *           element (and carries no gradient).  Exact ties are routine: conv windows that see only zeros equal the bias.
+ *   workspace mm_matchpyramid_fwd_save_workspace_bytes(..) bytes (its own size query: the kernel keeps one row-index tile per
+ *           wavefront in LDS, which can move a plane from the LDS to the workspace; that changes no bit).
+ *
+ * mm_matchpyramid_bwd: the gradients of sum(features * grad_features) from that state.
+ *
+ *   q, d, conv_w, layers   as in the forward (conv_b is not needed)
+ *   pooled, argmax         as written by mm_matchpyramid_fwd_save on the same inputs (an index outside its plane is clamped)
+ *   grad_features          [n_pairs, C_L ph_L pw_L] float32
+ *   grad_q  [n_pairs, Q, E] PER PAIR (the caller adds the pairs of a query when pairs_per_query > 1), grad_d [n_pairs, D, E]
+ *   grad_w, grad_b         in the packed layout of conv_w / conv_b, summed over the batch
+ *   Per pair from the last layer down: the conv-output gradient has one entry per pooled element (g_e at argmax_e where
+ *   pooled_e > 0: ReLU's backward, 0 at 0; entries that share a position add); grad_b[c] += sum_e g_e;
+ *   grad_w[c, k] += sum_e g_e In[argmax_e + k], In the saved pooled output of the layer below (the recomputed cosine plane for
+ *   layer 0) with the forward's zero padding; the input gradient is the transposed convolution, computed as a gather; then the
+ *   cosine's backward through x / (|x| + 1e-13) (a zero row takes only g / (|x| + 1e-13): torch's zero subgradient of the norm).
+ *   Exact fp32 (fma chains in fixed orders), NO floating-point atomics: two calls give the same bits, and grad_q / grad_d of a
+ *   pair do not depend on the rest of the batch.  A persistent grid; the weight / bias gradients accumulate per workgroup
+ *   over its pairs in pair order and a second small launch adds the workgroups' partials in workgroup order.
+ *   workspace mm_matchpyramid_bwd_workspace_bytes(..) bytes: one slot per resident workgroup, at most 256 MiB however large
+ *   n_pairs is.  The size queries return 0 for an unsupported shape.
+ *   Limits and errors: the forward's envelope; anything else returns MM_EUNSUPPORTED before any launch; NULL pointers or
+ *   pairs_per_query < 1 return MM_EINVAL; n_pairs = 0 writes nothing.
+ */
+size_t mm_matchpyramid_fwd_save_workspace_bytes(int64_t n_pairs, int Q, int D, int n_layers, const int32_t* layers);
+
+int mm_matchpyramid_fwd_save(const float* q, const float* d, const float* conv_w, const float* conv_b, float* features,
+                             float* pooled, int32_t* argmax, int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E,
+                             int n_layers, const int32_t* layers, void* workspace, size_t workspace_bytes, void* stream);
+
+size_t mm_matchpyramid_bwd_workspace_bytes(int64_t n_pairs, int Q, int D, int n_layers, const int32_t* layers);
+
+int mm_matchpyramid_bwd(const float* q, const float* d, const float* conv_w, const float* pooled, const int32_t* argmax,
+                        const float* grad_features, float* grad_q, float* grad_d, float* grad_w, float* grad_b,
+                        int64_t n_pairs, int64_t pairs_per_query, int Q, int D, int E, int n_layers, const int32_t* layers,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * ColBERT retrieval, candidate generation: token hits -> per query the documents that own a hit, with their row ranges.
  *

@@ -85,6 +85,11 @@ SIGNATURES = {
     "mm_drmm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "mm_matchpyramid_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
     "mm_matchpyramid_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mm_matchpyramid_fwd_save_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
+    "mm_matchpyramid_fwd_save": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "mm_matchpyramid_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
+    "mm_matchpyramid_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz,
+                                 _vp]),
     "mm_colbert_candidates_workspace_bytes": (_sz, [_i, _i]),
     "mm_colbert_candidates": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mm_fp8_quantize_rows": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),

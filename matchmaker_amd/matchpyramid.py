@@ -6,9 +6,10 @@ state_dict keys — `conv_layers.conv <i>.{weight,bias}` (the Sequential is buil
 
 The reference launches a cosine and, per layer, a pad, a Conv2d, a ReLU and an AdaptiveMaxPool2d, every activation through
 HBM.  Here :74-92 is ONE launch in libmm_native.so (mm_matchpyramid_fwd) when the inputs are on the GPU and neither an input
-nor a parameter needs a gradient; the three dense layers stay torch.  Otherwise — training, CPU tensors, shapes the kernel
-refuses with MM_EUNSUPPORTED — the module's own torch layers run, which are the reference's.  Any other native error is
-re-raised.
+nor a parameter needs a gradient; the three dense layers stay torch.  Otherwise — training (by default), CPU tensors, shapes
+the kernel refuses with MM_EUNSUPPORTED — the module's own torch layers run, which are the reference's.  Any other native
+error is re-raised.  Training can go through the native pair mm_matchpyramid_fwd_save / mm_matchpyramid_bwd instead: set the
+attribute `native_backward = True` (class docstring: why it is off by default).
 
 Reference behaviour kept: the masks never enter; the pad / kernel transposition of :50-51 (pad right by
 k[0] - 1 and below by k[1] - 1 for a k[0] x k[1] kernel); allennlp's cosine restated (x / (|x| + 1e-13))."""
@@ -32,7 +33,18 @@ class CosineMatrixAttention(nn.Module):
 
 
 class MatchPyramid(nn.Module):
-    """Text Matching as Image Recognition, Pang et al., AAAI'16 — native cosine + conv pyramid + adaptive max pooling."""
+    """Text Matching as Image Recognition, Pang et al., AAAI'16 — native cosine + conv pyramid + adaptive max pooling.
+
+    native_backward (an attribute, no constructor argument: the reference's signature is kept): when something needs a
+    gradient, the inputs are on the GPU and the shape is supported, `features` goes through
+    torch.ops.mm_native.matchpyramid_features_train (mm_matchpyramid_fwd_save + mm_matchpyramid_bwd, exact fp32, no atomics)
+    instead of the module's torch layers.
+
+    Default False, by measurement (tools/bench_matchpyramid.py on one MI355X, Q30 / D200 / E300, the default pyramid, 64
+    pairs, forward + backward of the whole module, both paths in one process): native 2.93 ms, eager 1.33 ms — the native
+    step is SLOWER (0.45 x; 2,048 pairs: 33.0 ms against 19.0 ms), so it is opt-in.  DESIGN.md §3.11."""
+
+    native_backward = False
 
     @staticmethod
     def from_config(config, word_embeddings_out_dim):
@@ -79,15 +91,19 @@ class MatchPyramid(nn.Module):
         return conv_result.view(conv_result.size(0), -1)
 
     def features(self, query_embeddings: torch.Tensor, document_embeddings: torch.Tensor) -> torch.Tensor:
-        native = query_embeddings.is_cuda and document_embeddings.is_cuda and not (
-            torch.is_grad_enabled() and (query_embeddings.requires_grad or document_embeddings.requires_grad
-                                         or any(p.requires_grad for p in self.conv_layers.parameters())))
-        if native:
+        on_gpu = query_embeddings.is_cuda and document_embeddings.is_cuda
+        needs_grad = torch.is_grad_enabled() and (query_embeddings.requires_grad or document_embeddings.requires_grad
+                                                  or any(p.requires_grad for p in self.conv_layers.parameters()))
+        if on_gpu and (self.native_backward or not needs_grad):
             convs = self._convs()
+            ws, bs = [c.weight for c in convs], [c.bias for c in convs]
             try:
-                return ops.matchpyramid_features(query_embeddings.float(), document_embeddings.float(),
-                                                 [c.weight for c in convs], [c.bias for c in convs], self.pool_sizes,
-                                                 packed=self._packed_params(convs))
+                if needs_grad:
+                    flat = [x for p in self.pool_sizes for x in p]
+                    return torch.ops.mm_native.matchpyramid_features_train(query_embeddings.float(),
+                                                                           document_embeddings.float(), ws, bs, flat, 1)[0]
+                return ops.matchpyramid_features(query_embeddings.float(), document_embeddings.float(), ws, bs,
+                                                 self.pool_sizes, packed=self._packed_params(convs))
             except ops.NativeError as e:
                 if getattr(e, "code", None) != _lib.MM_EUNSUPPORTED:
                     raise

@@ -1597,3 +1597,93 @@ def matchpyramid_features(q: torch.Tensor, d: torch.Tensor, weights, biases, poo
                                                     pairs_per_query, Q, D, E, L, layers),
               mm_matchpyramid_workspace_bytes, (B, Q, D, L, *layers))
     return out
+
+
+def mm_matchpyramid_fwd_save_workspace_bytes(B, Q, D, L, *layers):
+    return _lib.lib().mm_matchpyramid_fwd_save_workspace_bytes(B, Q, D, L, (ctypes.c_int32 * len(layers))(*layers))
+
+
+def mm_matchpyramid_bwd_workspace_bytes(B, Q, D, L, *layers):
+    return _lib.lib().mm_matchpyramid_bwd_workspace_bytes(B, Q, D, L, (ctypes.c_int32 * len(layers))(*layers))
+
+
+def matchpyramid_saved_size(weights, pool_sizes) -> int:
+    """S = sum_l C_l ph_l pw_l: the pooled elements of one pair over all layers (the row length of the saved state)."""
+    return sum(int(w.shape[0]) * int(p[0]) * int(p[1]) for w, p in zip(weights, pool_sizes))
+
+
+def matchpyramid_features_save(q: torch.Tensor, d: torch.Tensor, weights, biases, pool_sizes, pairs_per_query: int = 1,
+                               packed=None):
+    """matchpyramid_features for training (mm_matchpyramid_fwd_save): -> (features, saved), features the same bits as
+    matchpyramid_features, saved = (pooled [n_pairs, S] float32, argmax [n_pairs, S] int32), S = sum_l C_l ph_l pw_l: per
+    pair, layer after layer, every layer's pooled output [C_l, ph_l, pw_l] and for each of its elements the flat index
+    row * Wo + col into the channel's conv output (F.adaptive_max_pool2d(return_indices=True)'s convention; among equal
+    maxima the first in row-major order).  matchpyramid_bwd takes `saved`."""
+    dev = _dev_check(q, d, *weights, *biases)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("matchpyramid_features_save: float32 embeddings only (the reference cosine rejects bf16)")
+    nq, Q, E, B, D = _qd_shapes(q, d, pairs_per_query)
+    layers, feat = _mp_layers(Q, D, weights, biases, pool_sizes, "matchpyramid_features_save")
+    S = matchpyramid_saved_size(weights, pool_sizes)
+    out = torch.empty((B, feat), dtype=torch.float32, device=dev)
+    pooled = torch.empty((B, S), dtype=torch.float32, device=dev)
+    argmax = torch.empty((B, S), dtype=torch.int32, device=dev)
+    if B:
+        w, b = packed if packed is not None else matchpyramid_pack(weights, biases)
+        q, d, E = _pad_rows(q, d, 4)
+        L = len(weights)
+        _call(dev, _lib.lib().mm_matchpyramid_fwd_save, (q.data_ptr(), d.data_ptr(), w.data_ptr(), b.data_ptr(), out.data_ptr(),
+                                                         pooled.data_ptr(), argmax.data_ptr(), B, pairs_per_query, Q, D, E, L,
+                                                         layers),
+              mm_matchpyramid_fwd_save_workspace_bytes, (B, Q, D, L, *layers))
+    return out, (pooled, argmax)
+
+
+def matchpyramid_bwd(q: torch.Tensor, d: torch.Tensor, weights, biases, pool_sizes, saved, grad_features: torch.Tensor,
+                     pairs_per_query: int = 1, packed=None):
+    """Backward of matchpyramid_features_save (mm_matchpyramid_bwd): saved as returned by it on the same inputs,
+    grad_features [n_pairs, C_L ph_L pw_L].  Returns float32 (grad_q [n_queries, Q, E], grad_d [n_pairs, D, E], grad_w,
+    grad_b), the lists shaped like `weights` / `biases`, summed over the pairs in a fixed order (no atomics: two calls give
+    the same bits).  For pairs_per_query > 1 the per-pair grad_q rows of a query are summed here, in pair order."""
+    pooled, argmax = saved
+    dev = _dev_check(q, d, pooled, argmax, grad_features, *weights, *biases)
+    q, d = _emb(q, "q"), _emb(d, "d")
+    if q.dtype != torch.float32 or d.dtype != torch.float32:
+        raise NativeError("matchpyramid_bwd: float32 embeddings only")
+    nq, Q, E0, B, D = _qd_shapes(q, d, pairs_per_query)
+    layers, feat = _mp_layers(Q, D, weights, biases, pool_sizes, "matchpyramid_bwd")
+    S = matchpyramid_saved_size(weights, pool_sizes)
+    if tuple(pooled.shape) != (B, S) or pooled.dtype != torch.float32 or tuple(argmax.shape) != (B, S) \
+            or argmax.dtype != torch.int32:
+        raise NativeError(f"matchpyramid_bwd: saved must be (float32, int32) [{B}, {S}], got {pooled.dtype} "
+                          f"{tuple(pooled.shape)}, {argmax.dtype} {tuple(argmax.shape)}")
+    go = grad_features.detach().to(torch.float32).contiguous()
+    if tuple(go.shape) != (B, feat):
+        raise NativeError(f"matchpyramid_bwd: grad_features must be [{B}, {feat}], got {tuple(go.shape)}")
+    pooled, argmax = pooled.contiguous(), argmax.contiguous()
+    w, _ = packed if packed is not None else matchpyramid_pack(weights, biases)
+    q, d, E = _pad_rows(q, d, 4)
+    gq = torch.empty((B, Q, E), dtype=torch.float32, device=dev)
+    gd = torch.empty((B, D, E), dtype=torch.float32, device=dev)
+    gw = torch.zeros(w.numel(), dtype=torch.float32, device=dev)
+    gb = torch.zeros(sum(int(t.shape[0]) for t in weights), dtype=torch.float32, device=dev)
+    if B:
+        L = len(weights)
+        _call(dev, _lib.lib().mm_matchpyramid_bwd, (q.data_ptr(), d.data_ptr(), w.data_ptr(), pooled.data_ptr(), argmax.data_ptr(),
+                                                    go.data_ptr(), gq.data_ptr(), gd.data_ptr(), gw.data_ptr(), gb.data_ptr(), B,
+                                                    pairs_per_query, Q, D, E, L, layers),
+              mm_matchpyramid_bwd_workspace_bytes, (B, Q, D, L, *layers))
+    gq, gd = _trim(gq, E0), _trim(gd, E0)
+    if pairs_per_query > 1:       # per-pair rows -> per query (padded to whole groups, then summed in group order)
+        pad = nq * pairs_per_query - B
+        if pad:
+            gq = torch.cat([gq, gq.new_zeros((pad, Q, E0))])
+        gq = gq.view(nq, pairs_per_query, Q, E0).sum(1)
+    grad_w, grad_b, wo, bo = [], [], 0, 0
+    for t, bs in zip(weights, biases):
+        grad_w.append(gw[wo:wo + t.numel()].view(t.shape).clone())     # separate tensors (no views of one buffer)
+        grad_b.append(gb[bo:bo + t.shape[0]].view(bs.shape).clone())
+        wo += t.numel()
+        bo += int(t.shape[0])
+    return gq, gd, grad_w, grad_b

@@ -388,6 +388,67 @@ matchpyramid_features.register_autograd(_matchpyramid_backward, setup_context=_m
 torch.library.register_autocast(_NS + "::matchpyramid_features", "cuda", torch.float32)
 
 
+def _mp_pools(pool_sizes):
+    return [(pool_sizes[2 * i], pool_sizes[2 * i + 1]) for i in range(len(pool_sizes) // 2)]
+
+
+@torch.library.custom_op(_NS + "::matchpyramid_features_train", mutates_args=(), device_types="cuda")
+def matchpyramid_features_train(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor], pool_sizes: List[int],
+                                pairs_per_query: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(features, pooled, argmax): matchpyramid_features (the same bits) with the state its backward routes through
+    (ops.matchpyramid_features_save): pooled [n_pairs, S] float32 and argmax [n_pairs, S] int32, S = sum_l C_l ph_l pw_l.
+    Differentiable in q, d, weights and biases through `features` only; no gradient flows through the saved state.
+    (pairs_per_query has no default, as in pacrr_kmax.)"""
+    out, (pooled, argmax) = ops.matchpyramid_features_save(q, d, weights, biases, _mp_pools(pool_sizes), pairs_per_query)
+    return out, pooled, argmax
+
+
+@matchpyramid_features_train.register_fake
+def _(q, d, weights, biases, pool_sizes, pairs_per_query):
+    B = d.shape[0]
+    S = sum(w.shape[0] * pool_sizes[2 * i] * pool_sizes[2 * i + 1] for i, w in enumerate(weights))
+    return (q.new_empty((B, weights[-1].shape[0] * pool_sizes[-2] * pool_sizes[-1]), dtype=torch.float32),
+            q.new_empty((B, S), dtype=torch.float32), q.new_empty((B, S), dtype=torch.int32))
+
+
+@torch.library.custom_op(_NS + "::matchpyramid_features_train_backward", mutates_args=(), device_types="cuda")
+def matchpyramid_features_train_backward(q: Tensor, d: Tensor, weights: List[Tensor], biases: List[Tensor],
+                                         pool_sizes: List[int], pooled: Tensor, argmax: Tensor, grad_out: Tensor,
+                                         pairs_per_query: int = 1) -> Tuple[Tensor, Tensor, List[Tensor], List[Tensor]]:
+    """No autograd formula: a double backward raises."""
+    gq, gd, gw, gb = ops.matchpyramid_bwd(q, d, weights, biases, _mp_pools(pool_sizes), (pooled, argmax), grad_out,
+                                          pairs_per_query)
+    return gq, gd, gw, gb
+
+
+@matchpyramid_features_train_backward.register_fake
+def _(q, d, weights, biases, pool_sizes, pooled, argmax, grad_out, pairs_per_query=1):
+    return (q.new_empty(q.shape, dtype=torch.float32), d.new_empty(d.shape, dtype=torch.float32),
+            [w.new_empty(w.shape, dtype=torch.float32) for w in weights],
+            [b.new_empty(b.shape, dtype=torch.float32) for b in biases])
+
+
+def _matchpyramid_train_setup(ctx, inputs, output):
+    q, d, weights, biases, pool_sizes, ppq = inputs
+    ctx.save_for_backward(q, d, output[1], output[2], *weights, *biases)
+    ctx.meta = (list(pool_sizes), ppq, len(weights))
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+def _matchpyramid_train_backward(ctx, g, _gpooled, _gargmax):
+    q, d, pooled, argmax, *params = ctx.saved_tensors
+    pool_sizes, ppq, L = ctx.meta
+    weights, biases = params[:L], params[L:]
+    gq, gd, gw, gb = torch.ops.mm_native.matchpyramid_features_train_backward(q, d, weights, biases, pool_sizes, pooled,
+                                                                              argmax, g.contiguous(), ppq)
+    return (gq.to(q.dtype), gd.to(d.dtype), [t.to(w.dtype) for t, w in zip(gw, weights)],
+            [t.to(b.dtype) for t, b in zip(gb, biases)], None, None)
+
+
+matchpyramid_features_train.register_autograd(_matchpyramid_train_backward, setup_context=_matchpyramid_train_setup)
+torch.library.register_autocast(_NS + "::matchpyramid_features_train", "cuda", torch.float32)
+
+
 # ---------------------------------------------------------------------------------------------- ColBERT retrieval
 @torch.library.custom_op(_NS + "::colbert_candidates", mutates_args=(), device_types="cuda")
 def colbert_candidates(hit_rows: Tensor, begin_sorted: Tensor, end_sorted: Tensor, doc_of_sorted: Tensor, T: int,
