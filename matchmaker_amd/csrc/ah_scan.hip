@@ -111,20 +111,6 @@ __global__ void __launch_bounds__(256) ah_score_kernel(const IvfArgs a, int roun
 }
 
 template <int DT>
-static int ah_launch_score(const IvfArgs& a, int round, int E, unsigned grid, hipStream_t stream) {
-  const size_t lds = (size_t)E * 32;
-  switch (E) {
-    case 128: hipLaunchKernelGGL((ah_score_kernel<DT, 1>), dim3(grid), dim3(256), lds, stream, a, round); break;
-    case 256: hipLaunchKernelGGL((ah_score_kernel<DT, 2>), dim3(grid), dim3(256), lds, stream, a, round); break;
-    case 384: hipLaunchKernelGGL((ah_score_kernel<DT, 3>), dim3(grid), dim3(256), lds, stream, a, round); break;
-    case 512: hipLaunchKernelGGL((ah_score_kernel<DT, 4>), dim3(grid), dim3(256), lds, stream, a, round); break;
-    case 768: hipLaunchKernelGGL((ah_score_kernel<DT, 6>), dim3(grid), dim3(256), lds, stream, a, round); break;
-    default: return set_error(MM_EUNSUPPORTED, "ah_scan: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
-  }
-  return check_launch("ah_score_kernel");
-}
-
-template <int DT>
 __device__ __forceinline__ float to_f32(short v);
 template <>
 __device__ __forceinline__ float to_f32<MM_F16>(short v) { return (float)__builtin_bit_cast(_Float16, v); }
@@ -166,21 +152,6 @@ __global__ void __launch_bounds__(256) gather_dot_kernel(const void* queries, co
   }
 }
 
-template <int DT>
-static int gather_dot_launch(const void* q, const void* v, const int64_t* rows, float* out, int64_t n, int nq, int R, int E,
-                             hipStream_t stream) {
-  const int wpq = (R + 63) / 64;
-  const dim3 grid((unsigned)((int64_t)nq * wpq)), block(256);
-  switch (E) {
-    case 128: hipLaunchKernelGGL((gather_dot_kernel<DT, 1>), grid, block, 0, stream, q, v, rows, out, n, R, wpq); break;
-    case 256: hipLaunchKernelGGL((gather_dot_kernel<DT, 2>), grid, block, 0, stream, q, v, rows, out, n, R, wpq); break;
-    case 384: hipLaunchKernelGGL((gather_dot_kernel<DT, 3>), grid, block, 0, stream, q, v, rows, out, n, R, wpq); break;
-    case 512: hipLaunchKernelGGL((gather_dot_kernel<DT, 4>), grid, block, 0, stream, q, v, rows, out, n, R, wpq); break;
-    default: hipLaunchKernelGGL((gather_dot_kernel<DT, 6>), grid, block, 0, stream, q, v, rows, out, n, R, wpq); break;
-  }
-  return check_launch("gather_dot_kernel");
-}
-
 }  // namespace mm
 
 using namespace mm;
@@ -207,11 +178,16 @@ extern "C" int mm_ah_scan_fwd(const void* queries, const uint8_t* codes, const v
   a.q = queries; a.v = codes; a.codebook = codebook; a.probe_scores = probe_scores; a.lb = list_begin; a.probes = probes;
   a.n = n_vectors; a.nlist = nlist; a.nq = nq; a.nprobe = nprobe; a.k = k;
   a.out_s = out_scores; a.out_r = out_rows;
-  return ivf_run(a, workspace, stream, "ah_scan", [&](const IvfArgs& b, int r, const IvfGeom& g) {
+  return ivf_run(a, WsCursor(workspace, workspace_bytes), stream, "ah_scan", [&](const IvfArgs& b, int r, const IvfGeom& g) {
     // two workgroups per CU stay resident (192 VGPRs of A fragments at E 768); they walk the task table with a grid stride
     const int64_t wgs = (g.max_tasks + 3) / 4;
     const unsigned grid = (unsigned)(wgs < 4 * kCUs ? wgs : 4 * kCUs);
-    return dtype == MM_BF16 ? ah_launch_score<MM_BF16>(b, r, E, grid, stream) : ah_launch_score<MM_F16>(b, r, E, grid, stream);
+    return with_dtype16(dtype, [&](auto dt) {
+      return with_nsl(E, [&](auto nsl) {
+        hipLaunchKernelGGL((ah_score_kernel<MM_V(dt), MM_V(nsl)>), dim3(grid), dim3(256), (size_t)E * 32, stream, b, r);
+        return check_launch("ah_score_kernel");
+      });
+    });
   });
 }
 
@@ -221,10 +197,16 @@ extern "C" int mm_gather_dot(const void* queries, const void* vectors, const int
   if (!queries || !rows || !out || (!vectors && n_vectors > 0)) return set_error(MM_EINVAL, "gather_dot: null pointer");
   if (n_vectors < 0 || nq <= 0 || R <= 0) return set_error(MM_EINVAL, "gather_dot: non-positive shape");
   if (dtype != MM_F16 && dtype != MM_BF16) return set_error(MM_EUNSUPPORTED, "gather_dot: float16 / bfloat16 vectors only");
-  if (E != 128 && E != 256 && E != 384 && E != 512 && E != 768)
+  if (!stream_width(E))
     return set_error(MM_EUNSUPPORTED, "gather_dot: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
   if ((int64_t)nq * ((R + 63) / 64) >= (1LL << 31)) return set_error(MM_EUNSUPPORTED, "gather_dot: more than 2^31-1 workgroups");
   if (((uintptr_t)queries | (uintptr_t)vectors) & 15) return set_error(MM_EINVAL, "gather_dot: 16-byte alignment required");
-  return dtype == MM_BF16 ? gather_dot_launch<MM_BF16>(queries, vectors, rows, out, n_vectors, nq, R, E, stream)
-                          : gather_dot_launch<MM_F16>(queries, vectors, rows, out, n_vectors, nq, R, E, stream);
+  const int wpq = (R + 63) / 64;
+  return with_dtype16(dtype, [&](auto dt) {
+    return with_nsl(E, [&](auto nsl) {
+      hipLaunchKernelGGL((gather_dot_kernel<MM_V(dt), MM_V(nsl)>), dim3((unsigned)((int64_t)nq * wpq)), dim3(256), 0, stream, queries,
+                         vectors, rows, out, n_vectors, R, wpq);
+      return check_launch("gather_dot_kernel");
+    });
+  });
 }

@@ -971,7 +971,6 @@ __global__ void __launch_bounds__(256) fill_tau_kernel(float* tau, int n, float 
   if (i < n) tau[i] = v;
 }
 
-static size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 static int pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 // Launch geometry of one call: NQT query tiles per wavefront, query groups of 128 * NQT, at most 32
@@ -1032,15 +1031,13 @@ static int launch_dot(const DotArgs& a0, int nq_launch, int T, hipStream_t strea
 template <int DT, int MODE>
 static int launch_dot_e(const DotArgs& a, int nq_launch, const DotGeom& g, hipStream_t stream) {
   // NQT = 2 (64 queries per wavefront: every LDS read feeds two MFMAs) once there are enough queries
-  const bool two = g.nqt == 2;
-  switch (a.E / 128) {
-    case 1: return two ? launch_dot<DT, 1, 2, MODE>(a, nq_launch, g.T, stream) : launch_dot<DT, 1, 1, MODE>(a, nq_launch, g.T, stream);
-    case 2: return two ? launch_dot<DT, 2, 2, MODE>(a, nq_launch, g.T, stream) : launch_dot<DT, 2, 1, MODE>(a, nq_launch, g.T, stream);
-    case 3: return two ? launch_dot<DT, 3, 2, MODE>(a, nq_launch, g.T, stream) : launch_dot<DT, 3, 1, MODE>(a, nq_launch, g.T, stream);
-    case 4: return two ? launch_dot<DT, 4, 2, MODE>(a, nq_launch, g.T, stream) : launch_dot<DT, 4, 1, MODE>(a, nq_launch, g.T, stream);
-    case 6: return two ? launch_dot<DT, 6, 2, MODE>(a, nq_launch, g.T, stream) : launch_dot<DT, 6, 1, MODE>(a, nq_launch, g.T, stream);
-    default: return set_error(MM_EUNSUPPORTED, "dot_topk: E=%d (supported: 128, 256, 384, 512, 768; pad the vectors)", a.E);
-  }
+  // (this is the entry point's only width test, and it stays what it was: on E / 128, not stream_width(E))
+  if (const int nsl = a.E / 128; nsl < 1 || nsl == 5 || nsl > 6)
+    return set_error(MM_EUNSUPPORTED, "dot_topk: E=%d (supported: 128, 256, 384, 512, 768; pad the vectors)", a.E);
+  return with_nsl(a.E, [&](auto nsl) {
+    return g.nqt == 2 ? launch_dot<DT, MM_V(nsl), 2, MODE>(a, nq_launch, g.T, stream)
+                      : launch_dot<DT, MM_V(nsl), 1, MODE>(a, nq_launch, g.T, stream);
+  });
 }
 
 int dot_cap(int64_t n_docs, int k) {  // candidate list capacity per query
@@ -1052,25 +1049,23 @@ int dot_cap(int64_t n_docs, int k) {  // candidate list capacity per query
 
 // ---- the selection phases as host-side helpers (mm_internal.h): mm_dot_topk_fwd below and mm_dot_topk_fp8_fwd
 // (dot_topk_fp8.hip) run the same workspace layout, threshold rule and launches around their own streaming kernel
-size_t dot_sel_bytes(int64_t n_docs, int nq, int k) {
-  if (n_docs <= 0 || nq <= 0 || k <= 0) return 0;
-  const int cap = dot_cap(n_docs, k);
-  const int64_t s = n_docs < kDotSample ? n_docs : kDotSample;
-  // sample scores | tau | survivor counts | candidate scores + indices
-  return a256((size_t)nq * s * 4) + 2 * a256((size_t)nq * 4) + 2 * a256((size_t)nq * cap * 4);
-}
-
-DotSel dot_sel_carve(void* workspace, int64_t n_docs, int nq, int k) {
+DotSel dot_sel_carve(WsCursor& ws, int64_t n_docs, int nq, int k) {
   DotSel d;
   d.cap = dot_cap(n_docs, k);
   d.S = n_docs < kDotSample ? n_docs : kDotSample;
-  char* ws = (char*)workspace;
-  d.all = (float*)ws;            ws += a256((size_t)nq * d.S * 4);
-  d.tau = (float*)ws;            ws += a256((size_t)nq * 4);
-  d.count = (int32_t*)ws;        ws += a256((size_t)nq * 4);
-  d.cand_score = (float*)ws;     ws += a256((size_t)nq * d.cap * 4);
-  d.cand_idx = (int32_t*)ws;
+  d.all = ws.take<float>((size_t)nq * d.S);
+  d.tau = ws.take<float>((size_t)nq);
+  d.count = ws.take<int32_t>((size_t)nq);
+  d.cand_score = ws.take<float>((size_t)nq * d.cap);
+  d.cand_idx = ws.take<int32_t>((size_t)nq * d.cap);
   return d;
+}
+
+size_t dot_sel_bytes(int64_t n_docs, int nq, int k) {
+  if (n_docs <= 0 || nq <= 0 || k <= 0) return 0;
+  WsCursor measure;
+  dot_sel_carve(measure, n_docs, nq, k);
+  return measure.used;
 }
 
 int dot_sample_m(int64_t n_docs, int64_t S, int k, float m_scale) {
@@ -1124,7 +1119,8 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
 
   const DotGeom g = dot_geom(n_docs, nq);
   const bool small = n_docs <= 4096;  // everything is a candidate: no sampling
-  const DotSel sel = dot_sel_carve(workspace, n_docs, nq, k);
+  WsCursor ws(workspace, workspace_bytes);
+  const DotSel sel = dot_sel_carve(ws, n_docs, nq, k);
   const int cap = sel.cap;
   const int64_t S = sel.S;
   float* all = sel.all;
@@ -1143,8 +1139,7 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
   } else {
     a.ndocs = S; a.stride = n_docs / S; a.all_out = all; a.ld_all = S;
     const DotGeom gs = dot_geom(S, nq);
-    const int e = dtype == MM_BF16 ? launch_dot_e<MM_BF16, DOT_SAMPLE>(a, nq, gs, stream) : launch_dot_e<MM_F16, DOT_SAMPLE>(a, nq, gs, stream);
-    if (e) return e;
+    if (int e = with_dtype16(dtype, [&](auto dt) { return launch_dot_e<MM_V(dt), DOT_SAMPLE>(a, nq, gs, stream); })) return e;
     launch_sample_tau(sel, nq, dot_sample_m(n_docs, S, k, m_scale), stream);
   }
   if (int e = check_launch("dot_topk threshold")) return e;
@@ -1162,10 +1157,7 @@ extern "C" int mm_dot_topk_fwd(const void* queries, const void* corpus, int64_t 
     }();
     a.prof = prof_buf;
   }
-  {
-    const int e = dtype == MM_BF16 ? launch_dot_e<MM_BF16, DOT_FILTER>(a, nq, g, stream) : launch_dot_e<MM_F16, DOT_FILTER>(a, nq, g, stream);
-    if (e) return e;
-  }
+  if (int e = with_dtype16(dtype, [&](auto dt) { return launch_dot_e<MM_V(dt), DOT_FILTER>(a, nq, g, stream); })) return e;
   // phase 3: exact top-k of the survivors
   if (int e = launch_topk_rows(sel, nq, k, n_docs, out_scores, out_idx, status, stream)) return e;
   if (a.prof) {  // tools only: synchronous dump of the phase counters

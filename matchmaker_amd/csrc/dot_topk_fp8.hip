@@ -304,7 +304,8 @@ extern "C" int mm_dot_topk_fp8_fwd(const void* queries, const uint8_t* codes, co
   if (!workspace || workspace_bytes < need) return set_error(MM_EWORKSPACE, "dot_topk_fp8: workspace needs %zu bytes", need);
   if (!(m_scale > 0.0f)) m_scale = 1.0f;
 
-  const DotSel sel = dot_sel_carve(workspace, n_rows, nq, k);
+  WsCursor ws(workspace, workspace_bytes);
+  const DotSel sel = dot_sel_carve(ws, n_rows, nq, k);
   const bool small = n_rows <= 4096;  // everything is a candidate: no sampling
   DotFp8Args a{};
   a.q = queries; a.codes = codes; a.scales = scales; a.nq = nq;

@@ -347,7 +347,8 @@ extern "C" int mm_graph_search_fwd(const void* queries, const void* vectors, con
   a.gtable = (int32_t*)workspace;
   a.out_s = out_scores; a.out_r = out_rows; a.stats = stats;
 
-  const void* kern = dtype == MM_BF16 ? gs_kernel<MM_BF16>(E) : gs_kernel<MM_F16>(E);
+  const void* kern = nullptr;
+  with_dtype16(dtype, [&](auto dt) { kern = gs_kernel<MM_V(dt)>(E); return MM_OK; });
   if (g.lds > 64 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds);
   void* params[] = {(void*)&a};
   if (hipLaunchKernel(kern, dim3(g.grid), dim3(kGsThreads), params, g.lds, stream) != hipSuccess) {

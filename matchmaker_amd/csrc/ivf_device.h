@@ -38,8 +38,6 @@ inline IvfGeom ivf_geom(int64_t n, int nlist, int nq) {
   return g;
 }
 
-inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 struct IvfArgs {
   const void* q;            // [nq, E]
   const void* v;            // [n, E] rows (ivf_scan) / [n, E / 4] codes (ah_scan) / [n, E] e4m3fn codes (ivf_scan_fp8)
@@ -328,12 +326,30 @@ inline int pow2_ge_i(int v) {
   return p;
 }
 
+// The workspace of a scan, stated once: block by block in the order of IvfArgs.  On a measuring cursor this leaves the size in
+// ws.used (ivf_workspace_bytes), on a call's workspace it sets the pointers of `a` (ivf_run).
+inline void ivf_layout(IvfArgs& a, const IvfGeom& g, WsCursor& ws) {
+  const size_t pairs = (size_t)a.nq * a.nprobe, nq = (size_t)a.nq, nlist = (size_t)a.nlist;
+  a.seg_off = ws.take<int32_t>(pairs);
+  a.pairs = ws.take<int32_t>(pairs);
+  a.total = ws.take<int32_t>(nq);
+  a.prefix = ws.take<int64_t>(nq + 1);
+  a.qbeg = ws.take<int32_t>((size_t)g.rounds + 1);
+  a.tstart = ws.take<int32_t>(nlist + 1);
+  a.start = ws.take<int32_t>(nlist + 1);
+  a.blk_list = ws.take<int32_t>((size_t)g.max_tasks);
+  a.cnt = ws.take<int32_t>(2 * nlist);      // cnt | fill in ONE block: a round zeroes both with one memset
+  a.fill = a.cnt ? a.cnt + nlist : nullptr;
+  a.cand = ws.take<float>((size_t)g.cap);
+}
+
 inline size_t ivf_workspace_bytes(int64_t n_vectors, int nlist, int nq, int nprobe) {
   if (n_vectors < 0 || nlist <= 0 || nq <= 0 || nprobe <= 0) return 0;
-  const IvfGeom g = ivf_geom(n_vectors, nlist, nq);
-  const size_t pairs = (size_t)nq * nprobe;
-  return a256(pairs * 4) * 2 + a256((size_t)nq * 4) + a256(((size_t)nq + 1) * 8) + a256(((size_t)g.rounds + 1) * 4) +
-         a256(((size_t)nlist + 1) * 4) * 2 + a256((size_t)g.max_tasks * 4) + a256((size_t)nlist * 8) + a256((size_t)g.cap * 4);
+  IvfArgs a{};
+  a.n = n_vectors; a.nlist = nlist; a.nq = nq; a.nprobe = nprobe;
+  WsCursor measure;
+  ivf_layout(a, ivf_geom(n_vectors, nlist, nq), measure);
+  return measure.used;
 }
 
 // The checks both scans share (`what` names the caller), before any launch.
@@ -344,30 +360,21 @@ inline int ivf_check(const char* what, int64_t n_vectors, int nlist, int nq, int
     return set_error(MM_EUNSUPPORTED, "%s: k=%d / nprobe=%d exceed %d / %d", what, k, nprobe, kIvfMaxK, kIvfMaxProbe);
   if (n_vectors >= (1LL << 31) || (int64_t)nq * nprobe >= (1LL << 31))
     return set_error(MM_EUNSUPPORTED, "%s: more than 2^31-1 vectors or (query, probe) pairs in one call", what);
-  if (E != 128 && E != 256 && E != 384 && E != 512 && E != 768)
+  if (!stream_width(E))
     return set_error(MM_EUNSUPPORTED, "%s: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", what, E);
   return MM_OK;
 }
 
-// Carves the workspace, enqueues the preparation and every round.  `a` arrives with the inputs, the shape and the outputs
-// set; score(a, round, g) enqueues the caller's score kernel for one round and returns MM_OK or an error.
+// Carves the workspace (which the caller has compared with ivf_workspace_bytes), enqueues the preparation and every round.
+// `a` arrives with the inputs, the shape and the outputs set; score(a, round, g) enqueues the caller's score kernel for one
+// round and returns MM_OK or an error.
 template <typename Score>
-int ivf_run(IvfArgs a, void* workspace, hipStream_t stream, const char* what, Score score) {
+int ivf_run(IvfArgs a, WsCursor ws, hipStream_t stream, const char* what, Score score) {
   const IvfGeom g = ivf_geom(a.n, a.nlist, a.nq);
   const size_t pairs = (size_t)a.nq * a.nprobe;
   const int nlist = a.nlist, nq = a.nq, k = a.k;
   a.S = g.S;
-  char* ws = (char*)workspace;
-  a.seg_off = (int32_t*)ws;  ws += a256(pairs * 4);
-  a.pairs = (int32_t*)ws;    ws += a256(pairs * 4);
-  a.total = (int32_t*)ws;    ws += a256((size_t)nq * 4);
-  a.prefix = (int64_t*)ws;   ws += a256(((size_t)nq + 1) * 8);
-  a.qbeg = (int32_t*)ws;     ws += a256(((size_t)g.rounds + 1) * 4);
-  a.tstart = (int32_t*)ws;   ws += a256(((size_t)nlist + 1) * 4);
-  a.start = (int32_t*)ws;    ws += a256(((size_t)nlist + 1) * 4);
-  a.blk_list = (int32_t*)ws; ws += a256((size_t)g.max_tasks * 4);
-  a.cnt = (int32_t*)ws;      a.fill = a.cnt + nlist;  ws += a256((size_t)nlist * 8);
-  a.cand = (float*)ws;
+  ivf_layout(a, g, ws);
 
   hipLaunchKernelGGL(ivf_rows_kernel, dim3((nq + 3) / 4), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(ivf_tasks_kernel, dim3(1), dim3(1024), 0, stream, a);

@@ -90,19 +90,6 @@ __global__ void __launch_bounds__(256) ivf_score_kernel(const IvfArgs a, int rou
   }
 }
 
-template <int DT>
-static int ivf_launch_score(const IvfArgs& a, int round, int E, unsigned grid, hipStream_t stream) {
-  switch (E) {
-    case 128: hipLaunchKernelGGL((ivf_score_kernel<DT, 1>), dim3(grid), dim3(256), 0, stream, a, round); break;
-    case 256: hipLaunchKernelGGL((ivf_score_kernel<DT, 2>), dim3(grid), dim3(256), 0, stream, a, round); break;
-    case 384: hipLaunchKernelGGL((ivf_score_kernel<DT, 3>), dim3(grid), dim3(256), 0, stream, a, round); break;
-    case 512: hipLaunchKernelGGL((ivf_score_kernel<DT, 4>), dim3(grid), dim3(256), 0, stream, a, round); break;
-    case 768: hipLaunchKernelGGL((ivf_score_kernel<DT, 6>), dim3(grid), dim3(256), 0, stream, a, round); break;
-    default: return set_error(MM_EUNSUPPORTED, "ivf_scan: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
-  }
-  return check_launch("ivf_score_kernel");
-}
-
 }  // namespace mm
 
 using namespace mm;
@@ -127,9 +114,13 @@ extern "C" int mm_ivf_scan_fwd(const void* queries, const void* vectors, const i
   a.q = queries; a.v = vectors; a.lb = list_begin; a.probes = probes;
   a.n = n_vectors; a.nlist = nlist; a.nq = nq; a.nprobe = nprobe; a.k = k;
   a.out_s = out_scores; a.out_r = out_rows;
-  return ivf_run(a, workspace, stream, "ivf_scan", [&](const IvfArgs& b, int r, const IvfGeom& g) {
+  return ivf_run(a, WsCursor(workspace, workspace_bytes), stream, "ivf_scan", [&](const IvfArgs& b, int r, const IvfGeom& g) {
     const unsigned grid_score = (unsigned)((g.max_tasks + 3) / 4);
-    return dtype == MM_BF16 ? ivf_launch_score<MM_BF16>(b, r, E, grid_score, stream)
-                            : ivf_launch_score<MM_F16>(b, r, E, grid_score, stream);
+    return with_dtype16(dtype, [&](auto dt) {
+      return with_nsl(E, [&](auto nsl) {
+        hipLaunchKernelGGL((ivf_score_kernel<MM_V(dt), MM_V(nsl)>), dim3(grid_score), dim3(256), 0, stream, b, r);
+        return check_launch("ivf_score_kernel");
+      });
+    });
   });
 }

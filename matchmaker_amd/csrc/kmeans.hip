@@ -35,8 +35,6 @@ constexpr int kKmSplit = 512;     // rows per chunk of the segment sum
 constexpr int kKmTile = 128;      // rows of x per workgroup of the assignment (4 wavefronts x 32)
 constexpr int kKmBlock = 32;      // centroids per LDS block
 
-static size_t km_a256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 template <int DT>
 struct KmMfma;
 template <>
@@ -137,32 +135,6 @@ __global__ void __launch_bounds__(256) kmeans_assign_kernel(const void* __restri
     out_list[row] = arg;
     out_score[row] = best;
   }
-}
-
-template <int DT>
-static int km_launch_assign(const void* x, const void* cent, int64_t n, int nlist, int E, int32_t* out_list, float* out_score,
-                            hipStream_t stream) {
-  const unsigned grid = (unsigned)((n + kKmTile - 1) / kKmTile);
-  const size_t lds = (size_t)2 * kKmBlock * (E * 2 + 16);
-#define MM_KM_CASE(NSL)                                                                                                     \
-  hipLaunchKernelGGL((kmeans_assign_kernel<DT, NSL>), dim3(grid), dim3(256), lds, stream, x, cent, n, nlist, out_list, out_score)
-  switch (E) {
-    case 128: MM_KM_CASE(1); break;
-    case 256: MM_KM_CASE(2); break;
-    case 384: MM_KM_CASE(3); break;
-    case 512: MM_KM_CASE(4); break;
-    case 768: {
-      // 99,328 bytes of LDS: above the 64 KiB a kernel gets without asking
-      const hipError_t attr = hipFuncSetAttribute((const void*)kmeans_assign_kernel<DT, 6>,
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (attr != hipSuccess) return set_error(MM_ELAUNCH, "kmeans_assign: %zu bytes of LDS refused: %s", lds, hipGetErrorString(attr));
-      MM_KM_CASE(6);
-      break;
-    }
-    default: return set_error(MM_EUNSUPPORTED, "kmeans_assign: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
-  }
-#undef MM_KM_CASE
-  return check_launch("kmeans_assign_kernel");
 }
 
 // ---- segment sums ---------------------------------------------------------------------------------------------------------
@@ -293,7 +265,12 @@ __global__ void __launch_bounds__(256) kms_combine_kernel(const KmsArgs a) {
   }
 }
 
-static bool km_dim_ok(int E) { return E == 128 || E == 256 || E == 384 || E == 512 || E == 768; }
+// The workspace of the segment sum, stated once: the size query runs it on a measuring cursor, the entry point on its workspace.
+static void kms_layout(KmsArgs& a, WsCursor& ws) {
+  a.max_tasks = a.n / kKmSplit + a.nlist;
+  a.tstart = ws.take<int32_t>((size_t)a.nlist + 1);
+  a.partial = ws.take<float>((size_t)a.max_tasks * a.E);
+}
 
 }  // namespace mm
 
@@ -307,17 +284,31 @@ extern "C" int mm_kmeans_assign(const void* x, const void* centroids, int64_t n,
   if (dtype != MM_F16 && dtype != MM_BF16) return set_error(MM_EUNSUPPORTED, "kmeans_assign: float16 / bfloat16 vectors only");
   if (nlist < 1 || nlist > kKmMaxLists) return set_error(MM_EUNSUPPORTED, "kmeans_assign: nlist=%d outside 1 .. %d", nlist, kKmMaxLists);
   if (n >= (1LL << 31)) return set_error(MM_EUNSUPPORTED, "kmeans_assign: more than 2^31-1 rows in one call");
-  if (!km_dim_ok(E)) return set_error(MM_EUNSUPPORTED, "kmeans_assign: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
+  if (!stream_width(E)) return set_error(MM_EUNSUPPORTED, "kmeans_assign: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
   if (((uintptr_t)x | (uintptr_t)centroids) & 15) return set_error(MM_EINVAL, "kmeans_assign: 16-byte alignment required");
   if (n == 0) return MM_OK;
-  return dtype == MM_BF16 ? km_launch_assign<MM_BF16>(x, centroids, n, nlist, E, out_list, out_score, stream)
-                          : km_launch_assign<MM_F16>(x, centroids, n, nlist, E, out_list, out_score, stream);
+  const unsigned grid = (unsigned)((n + kKmTile - 1) / kKmTile);
+  const size_t lds = (size_t)2 * kKmBlock * (E * 2 + 16);
+  return with_dtype16(dtype, [&](auto dt) {
+    return with_nsl(E, [&](auto nsl) {
+      const auto kernel = kmeans_assign_kernel<MM_V(dt), MM_V(nsl)>;
+      if constexpr (MM_V(nsl) == 6) {     // 99,328 bytes of LDS: above the 64 KiB a kernel gets without asking
+        const hipError_t attr = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (attr != hipSuccess) return set_error(MM_ELAUNCH, "kmeans_assign: %zu bytes of LDS refused: %s", lds, hipGetErrorString(attr));
+      }
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, x, centroids, n, nlist, out_list, out_score);
+      return check_launch("kmeans_assign_kernel");
+    });
+  });
 }
 
 extern "C" size_t mm_kmeans_segment_sum_workspace_bytes(int64_t n, int nlist, int E) {
   if (n < 0 || nlist <= 0 || E <= 0) return 0;
-  const size_t max_tasks = (size_t)(n / kKmSplit) + (size_t)nlist;
-  return km_a256(((size_t)nlist + 1) * 4) + km_a256(max_tasks * (size_t)E * 4);
+  KmsArgs a{};
+  a.n = n; a.nlist = nlist; a.E = E;
+  WsCursor measure;
+  kms_layout(a, measure);
+  return measure.used;
 }
 
 extern "C" int mm_kmeans_segment_sum(const void* x, const int64_t* order, const int64_t* list_begin, int64_t n, int nlist, int E,
@@ -329,7 +320,7 @@ extern "C" int mm_kmeans_segment_sum(const void* x, const int64_t* order, const 
   if (nlist < 1 || nlist > kKmMaxLists)
     return set_error(MM_EUNSUPPORTED, "kmeans_segment_sum: nlist=%d outside 1 .. %d", nlist, kKmMaxLists);
   if (n >= (1LL << 31)) return set_error(MM_EUNSUPPORTED, "kmeans_segment_sum: more than 2^31-1 rows in one call");
-  if (!km_dim_ok(E))
+  if (!stream_width(E))
     return set_error(MM_EUNSUPPORTED, "kmeans_segment_sum: E=%d is not one of 128, 256, 384, 512, 768 (pad the vectors)", E);
   if (((uintptr_t)x | (uintptr_t)sums) & 15) return set_error(MM_EINVAL, "kmeans_segment_sum: 16-byte alignment required");
   const size_t need = mm_kmeans_segment_sum_workspace_bytes(n, nlist, E);
@@ -337,16 +328,16 @@ extern "C" int mm_kmeans_segment_sum(const void* x, const int64_t* order, const 
 
   KmsArgs a{};
   a.x = x; a.order = order; a.lb = list_begin; a.n = n; a.nlist = nlist; a.E = E; a.sums = sums;
-  a.max_tasks = n / kKmSplit + nlist;
-  char* ws = (char*)workspace;
-  a.tstart = (int32_t*)ws;  ws += km_a256(((size_t)nlist + 1) * 4);
-  a.partial = (float*)ws;
+  WsCursor ws(workspace, workspace_bytes);
+  kms_layout(a, ws);
   hipLaunchKernelGGL(kms_tasks_kernel, dim3(1), dim3(1024), 0, stream, a);
   if (n > 0) {
     const int RL = 256 / (E >> 3);
     const size_t lds = (size_t)RL * E * 4;
-    if (dtype == MM_BF16) hipLaunchKernelGGL(kms_partial_kernel<MM_BF16>, dim3((unsigned)a.max_tasks), dim3(256), lds, stream, a);
-    else hipLaunchKernelGGL(kms_partial_kernel<MM_F16>, dim3((unsigned)a.max_tasks), dim3(256), lds, stream, a);
+    with_dtype16(dtype, [&](auto dt) {
+      hipLaunchKernelGGL(kms_partial_kernel<MM_V(dt)>, dim3((unsigned)a.max_tasks), dim3(256), lds, stream, a);
+      return MM_OK;
+    });
   }
   hipLaunchKernelGGL(kms_combine_kernel, dim3(nlist), dim3(256), 0, stream, a);
   return check_launch("kmeans_segment_sum");

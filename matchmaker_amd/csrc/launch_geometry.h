@@ -1,4 +1,5 @@
-// Host arithmetic of the scoring launches: which pairs a wavefront scores, and the workspace cursor of the entry points.
+// Host arithmetic of the launches: which pairs a wavefront scores, and the workspace cursor of the entry points, which both
+// measures and carves the layout of the retrieval operators' workspaces.
 // Nothing from HIP is included: any C++17 compiler takes this header on its own (tests/test_launch_geometry_cpu.py does).
 #pragma once
 #include <stddef.h>
@@ -54,11 +55,29 @@ inline bool stream_width(int E) { return E == 128 || E == 256 || E == 384 || E =
 // ... and those of kernel pooling's K-sliced stream (TK, TKL), NS = E / 100
 inline bool kp_stream_width(int E) { return E == 100 || E == 200 || E == 300; }
 
-// What is left of a call's workspace; a null workspace has no bytes.
+// Workspace blocks start on 256-byte boundaries.
+inline size_t a256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// What is left of a call's workspace; a null workspace has no bytes.  take<T>(count) reserves the next block of the layout,
+// a256(count * sizeof(T)) bytes, and counts it in `used`.  A cursor without a base measures: every take returns null and
+// `used` ends as the size of the layout, so an operator states its layout ONCE, in a function that its size query runs on a
+// measuring cursor and its entry point (after comparing `used` of that run with the bytes it was given) on the workspace.
 struct WsCursor {
   char* p;
   size_t left;
+  size_t used = 0;
+  WsCursor() : p(nullptr), left(0) {}
   WsCursor(void* workspace, size_t bytes) : p((char*)workspace), left(workspace ? bytes : 0) {}
+  template <class T>
+  T* take(size_t count) {
+    const size_t b = a256(count * sizeof(T));
+    used += b;
+    if (!p) return nullptr;      // no pointer is formed from a null base
+    T* block = (T*)p;
+    p += b;
+    left = left > b ? left - b : 0;
+    return block;
+  }
 };
 
 }  // namespace mm

@@ -163,8 +163,8 @@ int kp128_maxsim_f32(const float* q, const float* d, PackedMask qm, PackedMask d
 
 // dot_topk.hip: the selection phases of the flat inner-product top-k (threshold from a sample, candidate lists, exact top-k
 // of the survivors), shared by mm_dot_topk_fwd and mm_dot_topk_fp8_fwd (dot_topk_fp8.hip), which differ in the streaming
-// kernel between them only.  The workspace of a call is dot_sel_bytes(): sample scores [nq, S] | tau [nq] | survivor
-// counts [nq] | candidate scores and rows [nq, cap] each.
+// kernel between them only.  The workspace of a call is laid out by dot_sel_carve (dot_sel_bytes() runs it on a measuring
+// cursor): sample scores [nq, S] | tau [nq] | survivor counts [nq] | candidate scores and rows [nq, cap] each.
 constexpr int kDotSample = 16384;  // sample size (documents) of phase 1 when the shard is larger
 struct DotSel {
   float* all;         // [nq, S] scores of the strided sample
@@ -177,7 +177,7 @@ struct DotSel {
 };
 int dot_cap(int64_t n_docs, int k);
 size_t dot_sel_bytes(int64_t n_docs, int nq, int k);
-DotSel dot_sel_carve(void* workspace, int64_t n_docs, int nq, int k);
+DotSel dot_sel_carve(WsCursor& ws, int64_t n_docs, int nq, int k);
 int dot_sample_m(int64_t n_docs, int64_t S, int k, float m_scale);   // the sample rank that becomes the threshold
 void launch_fill_tau(const DotSel& d, int nq, float v, hipStream_t stream);             // fill_tau_kernel
 void launch_sample_tau(const DotSel& d, int nq, int m, hipStream_t stream);             // sample_tau_kernel

@@ -72,6 +72,31 @@ def _k_range(op: str, k: int, nprobe: int):
         raise NativeError(f"{op}: k={k} / nprobe={nprobe} outside 1 .. 4096")
 
 
+def _queries16(op: str, queries: torch.Tensor):
+    if queries.dim() != 2 or queries.dtype not in _DT:
+        raise NativeError(f"{op}: queries: expected [nq, E] float16 / bfloat16, got {tuple(queries.shape)} {queries.dtype}")
+
+
+def _fp8_store(op: str, row: str, q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor) -> int:
+    """The fp8 store of an operator and its query: codes [rows, E] uint8, scales [rows] float32, q fp16 or bf16.  `row` is
+    the letter the operator's messages give the row count.  Returns the rows."""
+    if q.dtype == torch.float32:
+        raise NativeError(f"{op}: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit MFMA operand)",
+                          _lib.MM_EUNSUPPORTED)
+    if codes.dim() != 2 or codes.dtype != torch.uint8:
+        raise NativeError(f"{op}: codes: expected [{row}, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
+    rows = codes.shape[0]
+    if scales.dtype != torch.float32 or tuple(scales.shape) != (rows,):
+        raise NativeError(f"{op}: scales: expected [{rows}] float32 (one per row of codes), got "
+                          f"{tuple(scales.shape)} {scales.dtype}")
+    return rows
+
+
+def _topk_out(dev, nq: int, k: int):
+    """The (scores [nq, k] float32, rows [nq, k] int64) pair the top-k operators return."""
+    return torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.int64, device=dev)
+
+
 def _pad_last(t: torch.Tensor, mult: int) -> torch.Tensor:
     E = t.shape[-1]
     return t if E % mult == 0 else torch.nn.functional.pad(t, (0, mult - E % mult))
@@ -210,20 +235,23 @@ def _flags(sim_round: bool, sum_round: bool) -> int:
     return (_lib.SIM_ROUND if sim_round else 0) | (_lib.SUM_ROUND if sum_round else 0)
 
 
-def _call(dev, fn, args, size_fn=None, key=(), cached=False):
-    """The native call every scoring operator ends with: fn(*args, workspace pointer or None, workspace bytes, stream) under
-    the device guard, on the current stream (its handle is read once), then the check of the return code under fn's name.
+def _call(dev, fn, args, size_fn=None, key=(), cached=False, stream_only=False):
+    """The native call every operator ends with: fn(*args, workspace pointer or None, workspace bytes, stream) under the
+    device guard, on the current stream (its handle is read once), then the check of the return code under fn's name.
     size_fn(*key), key = integers, gives the workspace size (None: the entry point needs no workspace); cached: the workspace
     is the per-stream buffer of _workspace (host-bound calls), else a fresh allocation (large ones, which the cache would hold
-    on to)."""
+    on to).  stream_only: the entry point's signature has no workspace arguments, fn(*args, stream)."""
     with _on(dev):
         st = _stream(dev)
-        wsb = _ws_bytes(size_fn, *key) if size_fn is not None else 0
-        if cached:
-            ws = _workspace(dev, wsb, st)
+        if stream_only:
+            rc = fn(*args, st)
         else:
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
-        rc = fn(*args, ws.data_ptr() if ws is not None else None, wsb, st)
+            wsb = _ws_bytes(size_fn, *key) if size_fn is not None else 0
+            if cached:
+                ws = _workspace(dev, wsb, st)
+            else:
+                ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if wsb else None
+            rc = fn(*args, ws.data_ptr() if ws is not None else None, wsb, st)
     _lib.check(rc, fn.__name__)
 
 
@@ -373,9 +401,7 @@ def hbm_stream_probe(t: torch.Tensor, nt: bool = True) -> None:
     dev = _dev_check(t)
     t = t.contiguous()
     nbytes = (t.numel() * t.element_size()) // 8192 * 8192
-    with _on(dev):
-        rc = _lib.lib().mm_hbm_stream_probe(t.data_ptr(), nbytes, 1 if nt else 0, _stream(dev))
-    _lib.check(rc, "mm_hbm_stream_probe")
+    _call(dev, _lib.lib().mm_hbm_stream_probe, (t.data_ptr(), nbytes, 1 if nt else 0), stream_only=True)
 
 
 def _check_ranges(doc_begin: torch.Tensor, doc_end: torch.Tensor, n_rows: int):
@@ -451,9 +477,8 @@ def fp8_quantize_rows(x: torch.Tensor) -> "tuple[torch.Tensor, torch.Tensor]":
     scales = torch.empty(T, dtype=torch.float32, device=dev)
     if T == 0:
         return codes, scales
-    with _on(dev):
-        rc = _lib.lib().mm_fp8_quantize_rows(x.data_ptr(), T, E, _DT[x.dtype], codes.data_ptr(), scales.data_ptr(), _stream(dev))
-    _lib.check(rc, "mm_fp8_quantize_rows")
+    _call(dev, _lib.lib().mm_fp8_quantize_rows, (x.data_ptr(), T, E, _DT[x.dtype], codes.data_ptr(), scales.data_ptr()),
+          stream_only=True)
     return codes, scales
 
 
@@ -477,15 +502,7 @@ def maxsim_ragged_fp8(q: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor
     dtype as in maxsim_ragged.  Returns float32 [n_pairs]."""
     dev = _dev_check(q, codes, scales, doc_begin, doc_end, q_mask)
     q = _emb(q, "q")
-    if q.dtype == torch.float32:
-        raise NativeError("maxsim_ragged_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit "
-                          "MFMA operand)", _lib.MM_EUNSUPPORTED)
-    if codes.dim() != 2 or codes.dtype != torch.uint8:
-        raise NativeError(f"maxsim_ragged_fp8: codes: expected [T, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
-    T = codes.shape[0]
-    if scales.dtype != torch.float32 or tuple(scales.shape) != (T,):
-        raise NativeError(f"maxsim_ragged_fp8: scales: expected [{T}] float32 (one per row of codes), got "
-                          f"{tuple(scales.shape)} {scales.dtype}")
+    T = _fp8_store("maxsim_ragged_fp8", "T", q, codes, scales)
     E = q.shape[2]
     _same_width(E, codes.shape[1])
     if E % 16:
@@ -817,13 +834,14 @@ def tkl_bwd(q_ctx: torch.Tensor, chunks: torch.Tensor, chunk_mask: torch.Tensor,
     return gq, gc, gp.sum(0)
 
 
-def _topk_reruns(name: str, dev, queries: torch.Tensor, N: int, k: int, max_rounds: int, size_fn, call):
+def _topk_reruns(name: str, dev, fn, size_fn, queries: torch.Tensor, store, k: int, max_rounds: int):
     """The status-driven loop of the flat top-k operators (dot_topk, dot_topk_fp8): one native call over every query, then
     re-runs of the queries whose sampled threshold let too few / too many candidates through, with the threshold scale
-    bisected per query.  call(q, n, scale, s_ptr, i_ptr, st_ptr, ws_ptr, wsb, stream) -> (return code, native symbol)."""
-    nq = queries.shape[0]
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    bisected per query.  fn = the entry point, store = the tensors it takes between the queries and the row count (the
+    first one has a row per store row); every run gets a fresh workspace of size_fn(N, n, k) bytes."""
+    nq, E = queries.shape
+    N = store[0].shape[0]
+    out_s, out_i = _topk_out(dev, nq, k)
     if nq == 0:
         return out_s, out_i
     if N == 0:
@@ -832,14 +850,10 @@ def _topk_reruns(name: str, dev, queries: torch.Tensor, N: int, k: int, max_roun
     def run(q, scale, s=None, i=None):
         n = q.shape[0]
         if s is None:
-            s = torch.empty((n, k), dtype=torch.float32, device=dev)
-            i = torch.empty((n, k), dtype=torch.int64, device=dev)
+            s, i = _topk_out(dev, n, k)
         st = torch.empty(n, dtype=torch.int32, device=dev)
-        with _on(dev):
-            wsb = size_fn(N, n, k)
-            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            rc, what = call(q, n, scale, s.data_ptr(), i.data_ptr(), st.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-        _lib.check(rc, what)
+        _call(dev, fn, (q.data_ptr(), *[t.data_ptr() for t in store], N, n, E, _DT[q.dtype], k, scale, s.data_ptr(),
+                        i.data_ptr(), st.data_ptr()), size_fn, (N, n, k))
         return s, i, st
 
     _, _, st = run(queries, 1.0, out_s, out_i)        # straight into the caller's tensors (no 84 MB staging copy)
@@ -893,15 +907,8 @@ def dot_topk(queries: torch.Tensor, corpus: torch.Tensor, k: int, max_rounds: in
     dev = _dev_check(queries, corpus)
     _pair16("dot_topk", queries, corpus, "[nq, E]", "[N, E]")
     queries, corpus = queries.contiguous(), corpus.contiguous()
-    nq, E = queries.shape
-    N = corpus.shape[0]
     L = _lib.lib()
-
-    def call(q, n, scale, s, i, st, ws, wsb, stream):
-        return L.mm_dot_topk_fwd(q.data_ptr(), corpus.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s, i, st, ws, wsb,
-                                 stream), "mm_dot_topk_fwd"
-
-    return _topk_reruns("dot_topk", dev, queries, N, k, max_rounds, L.mm_dot_topk_workspace_bytes, call)
+    return _topk_reruns("dot_topk", dev, L.mm_dot_topk_fwd, L.mm_dot_topk_workspace_bytes, queries, (corpus,), k, max_rounds)
 
 
 def dot_topk_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, k: int, max_rounds: int = 6):
@@ -912,27 +919,12 @@ def dot_topk_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tenso
     of the store, -1 / -inf padded when N < k); equal scores go to the lower row; the same status-driven re-runs as
     dot_topk make every row exact."""
     dev = _dev_check(queries, codes, scales)
-    if queries.dim() != 2 or queries.dtype not in _DT:
-        raise NativeError(f"dot_topk_fp8: queries: expected [nq, E] float16 / bfloat16, got {tuple(queries.shape)} {queries.dtype}")
-    if queries.dtype == torch.float32:
-        raise NativeError("dot_topk_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit MFMA "
-                          "operand)", _lib.MM_EUNSUPPORTED)
-    if codes.dim() != 2 or codes.dtype != torch.uint8:
-        raise NativeError(f"dot_topk_fp8: codes: expected [N, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
-    N = codes.shape[0]
-    if scales.dtype != torch.float32 or tuple(scales.shape) != (N,):
-        raise NativeError(f"dot_topk_fp8: scales: expected [{N}] float32 (one per row of codes), got "
-                          f"{tuple(scales.shape)} {scales.dtype}")
-    nq, E = queries.shape
-    _same_width(E, codes.shape[1])
-    queries, codes, scales = queries.contiguous(), codes.contiguous(), scales.contiguous()
+    _queries16("dot_topk_fp8", queries)
+    _fp8_store("dot_topk_fp8", "N", queries, codes, scales)
+    _same_width(queries.shape[1], codes.shape[1])
     L = _lib.lib()
-
-    def call(q, n, scale, s, i, st, ws, wsb, stream):
-        return L.mm_dot_topk_fp8_fwd(q.data_ptr(), codes.data_ptr(), scales.data_ptr(), N, n, E, _DT[q.dtype], k, scale, s, i,
-                                     st, ws, wsb, stream), "mm_dot_topk_fp8_fwd"
-
-    return _topk_reruns("dot_topk_fp8", dev, queries, N, k, max_rounds, L.mm_dot_topk_fp8_workspace_bytes, call)
+    return _topk_reruns("dot_topk_fp8", dev, L.mm_dot_topk_fp8_fwd, L.mm_dot_topk_fp8_workspace_bytes, queries.contiguous(),
+                        (codes.contiguous(), scales.contiguous()), k, max_rounds)
 
 
 def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Tensor, probes: torch.Tensor, k: int):
@@ -955,18 +947,14 @@ def ivf_scan(queries: torch.Tensor, vectors: torch.Tensor, list_begin: torch.Ten
     list_begin, probes = list_begin.contiguous(), probes.contiguous()
     nq, E = queries.shape
     n, nlist, nprobe = vectors.shape[0], list_begin.shape[0] - 1, probes.shape[1]
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_s, out_r = _topk_out(dev, nq, k)
     if nq == 0:
         return out_s, out_r
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_ivf_scan_workspace_bytes, n, nlist, nq, nprobe, k)
-        ws = _workspace(dev, wsb)
-        rc = L.mm_ivf_scan_fwd(queries.data_ptr(), vectors.data_ptr() if n else None, list_begin.data_ptr(), probes.data_ptr(),
-                               n, nlist, nq, nprobe, E, _DT[queries.dtype], k, out_s.data_ptr(), out_r.data_ptr(),
-                               ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_ivf_scan_fwd")
+    _call(dev, L.mm_ivf_scan_fwd, (queries.data_ptr(), vectors.data_ptr() if n else None, list_begin.data_ptr(),
+                                   probes.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k, out_s.data_ptr(),
+                                   out_r.data_ptr()),
+          L.mm_ivf_scan_workspace_bytes, (n, nlist, nq, nprobe, k), cached=True)
     return out_s, out_r
 
 
@@ -981,17 +969,8 @@ def ivf_scan_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tenso
     (scores [nq, k] float32 descending, rows [nq, k] int64 rows of `codes`; -inf / -1 padded when the probed lists hold
     fewer than k rows; equal scores: lower row first).  One enqueue on the current stream, no read-back: graph-capturable."""
     dev = _dev_check(queries, codes, scales, list_begin, probes)
-    if queries.dim() != 2 or queries.dtype not in _DT:
-        raise NativeError(f"ivf_scan_fp8: queries: expected [nq, E] float16 / bfloat16, got {tuple(queries.shape)} {queries.dtype}")
-    if queries.dtype == torch.float32:
-        raise NativeError("ivf_scan_fp8: the query is fp16 or bf16 (convert it; an fp32 query has no exact 16-bit MFMA "
-                          "operand)", _lib.MM_EUNSUPPORTED)
-    if codes.dim() != 2 or codes.dtype != torch.uint8:
-        raise NativeError(f"ivf_scan_fp8: codes: expected [n, E] uint8, got {tuple(codes.shape)} {codes.dtype}")
-    n = codes.shape[0]
-    if scales.dtype != torch.float32 or tuple(scales.shape) != (n,):
-        raise NativeError(f"ivf_scan_fp8: scales: expected [{n}] float32 (one per row of codes), got "
-                          f"{tuple(scales.shape)} {scales.dtype}")
+    _queries16("ivf_scan_fp8", queries)
+    n = _fp8_store("ivf_scan_fp8", "n", queries, codes, scales)
     nq, E = queries.shape
     _same_width(E, codes.shape[1])
     _native_width("ivf_scan_fp8", E)
@@ -1001,18 +980,14 @@ def ivf_scan_fp8(queries: torch.Tensor, codes: torch.Tensor, scales: torch.Tenso
     queries, codes, scales = queries.contiguous(), codes.contiguous(), scales.contiguous()
     list_begin, probes = list_begin.contiguous(), probes.contiguous()
     nlist, nprobe = list_begin.shape[0] - 1, probes.shape[1]
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_s, out_r = _topk_out(dev, nq, k)
     if nq == 0:
         return out_s, out_r
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_ivf_scan_fp8_workspace_bytes, n, nlist, nq, nprobe, k)
-        ws = _workspace(dev, wsb)
-        rc = L.mm_ivf_scan_fp8_fwd(queries.data_ptr(), codes.data_ptr() if n else None, scales.data_ptr() if n else None,
-                                   list_begin.data_ptr(), probes.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
-                                   out_s.data_ptr(), out_r.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_ivf_scan_fp8_fwd")
+    _call(dev, L.mm_ivf_scan_fp8_fwd, (queries.data_ptr(), codes.data_ptr() if n else None, scales.data_ptr() if n else None,
+                                       list_begin.data_ptr(), probes.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
+                                       out_s.data_ptr(), out_r.data_ptr()),
+          L.mm_ivf_scan_fp8_workspace_bytes, (n, nlist, nq, nprobe, k), cached=True)
     return out_s, out_r
 
 
@@ -1048,11 +1023,8 @@ def ah_encode(x: torch.Tensor, lists: torch.Tensor, centroids: torch.Tensor, cod
     codes = torch.empty((n, E // 4), dtype=torch.uint8, device=dev)
     if n == 0:
         return codes
-    L = _lib.lib()
-    with _on(dev):
-        rc = L.mm_ah_encode(x.data_ptr(), lists.data_ptr(), centroids.data_ptr(), codebook.data_ptr(), n, centroids.shape[0], E,
-                            _DT[x.dtype], eta, passes, codes.data_ptr(), _stream(dev))
-    _lib.check(rc, "mm_ah_encode")
+    _call(dev, _lib.lib().mm_ah_encode, (x.data_ptr(), lists.data_ptr(), centroids.data_ptr(), codebook.data_ptr(), n,
+                                         centroids.shape[0], E, _DT[x.dtype], eta, passes, codes.data_ptr()), stream_only=True)
     return codes
 
 
@@ -1085,18 +1057,14 @@ def ah_scan(queries: torch.Tensor, codes: torch.Tensor, codebook: torch.Tensor, 
     queries, codes, list_begin = queries.contiguous(), codes.contiguous(), list_begin.contiguous()
     probes, probe_scores = probes.contiguous(), probe_scores.contiguous()
     n, nlist, nprobe = codes.shape[0], list_begin.shape[0] - 1, probes.shape[1]
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_s, out_r = _topk_out(dev, nq, k)
     if nq == 0:
         return out_s, out_r
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_ah_scan_workspace_bytes, n, nlist, nq, nprobe, k)
-        ws = _workspace(dev, wsb)
-        rc = L.mm_ah_scan_fwd(queries.data_ptr(), codes.data_ptr() if n else None, codebook.data_ptr(), list_begin.data_ptr(),
-                              probes.data_ptr(), probe_scores.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
-                              out_s.data_ptr(), out_r.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_ah_scan_fwd")
+    _call(dev, L.mm_ah_scan_fwd, (queries.data_ptr(), codes.data_ptr() if n else None, codebook.data_ptr(), list_begin.data_ptr(),
+                                  probes.data_ptr(), probe_scores.data_ptr(), n, nlist, nq, nprobe, E, _DT[queries.dtype], k,
+                                  out_s.data_ptr(), out_r.data_ptr()),
+          L.mm_ah_scan_workspace_bytes, (n, nlist, nq, nprobe, k), cached=True)
     return out_s, out_r
 
 
@@ -1118,11 +1086,8 @@ def gather_dot(queries: torch.Tensor, vectors: torch.Tensor, rows: torch.Tensor)
     out = torch.empty((nq, R), dtype=torch.float32, device=dev)
     if nq == 0 or R == 0:
         return out
-    L = _lib.lib()
-    with _on(dev):
-        rc = L.mm_gather_dot(queries.data_ptr(), vectors.data_ptr() if vectors.shape[0] else None, rows.data_ptr(),
-                             vectors.shape[0], nq, R, E, _DT[queries.dtype], out.data_ptr(), _stream(dev))
-    _lib.check(rc, "mm_gather_dot")
+    _call(dev, _lib.lib().mm_gather_dot, (queries.data_ptr(), vectors.data_ptr() if vectors.shape[0] else None, rows.data_ptr(),
+                                          vectors.shape[0], nq, R, E, _DT[queries.dtype], out.data_ptr()), stream_only=True)
     return out
 
 
@@ -1153,20 +1118,15 @@ def graph_search(queries: torch.Tensor, vectors: torch.Tensor, neighbors: torch.
         queries, vectors, E = _pad_rows(queries, vectors, 128)
     queries, vectors = queries.contiguous(), vectors.contiguous()
     neighbors, entry_rows = neighbors.contiguous(), entry_rows.contiguous()
-    out_s = torch.empty((nq, max(int(k), 0)), dtype=torch.float32, device=dev)
-    out_r = torch.empty((nq, max(int(k), 0)), dtype=torch.int64, device=dev)
+    out_s, out_r = _topk_out(dev, nq, max(int(k), 0))
     stats = torch.empty((nq, 2), dtype=torch.int32, device=dev) if return_stats else None
     if nq == 0:
         return (out_s, out_r, stats) if return_stats else (out_s, out_r)
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_graph_search_workspace_bytes, n, nq, M, int(ef), int(width), n_entry, int(max_iters))
-        ws = _workspace(dev, wsb)
-        rc = L.mm_graph_search_fwd(queries.data_ptr(), vectors.data_ptr(), neighbors.data_ptr(), entry_rows.data_ptr(), n, nq, E,
-                                   _DT[queries.dtype], M, n_entry, int(ef), int(width), int(max_iters), int(k),
-                                   out_s.data_ptr(), out_r.data_ptr(), stats.data_ptr() if return_stats else None,
-                                   ws.data_ptr() if ws is not None else None, wsb, _stream(dev))
-    _lib.check(rc, "mm_graph_search_fwd")
+    _call(dev, L.mm_graph_search_fwd, (queries.data_ptr(), vectors.data_ptr(), neighbors.data_ptr(), entry_rows.data_ptr(), n, nq,
+                                       E, _DT[queries.dtype], M, n_entry, int(ef), int(width), int(max_iters), int(k),
+                                       out_s.data_ptr(), out_r.data_ptr(), stats.data_ptr() if return_stats else None),
+          L.mm_graph_search_workspace_bytes, (n, nq, M, int(ef), int(width), n_entry, int(max_iters)), cached=True)
     return (out_s, out_r, stats) if return_stats else (out_s, out_r)
 
 
@@ -1190,11 +1150,8 @@ def kmeans_assign(x: torch.Tensor, centroids: torch.Tensor):
     out_s = torch.empty(n, dtype=torch.float32, device=dev)
     if n == 0:
         return out_l, out_s
-    L = _lib.lib()
-    with _on(dev):
-        rc = L.mm_kmeans_assign(x.data_ptr(), centroids.data_ptr(), n, nlist, E, _DT[x.dtype], out_l.data_ptr(),
-                                out_s.data_ptr(), _stream(dev))
-    _lib.check(rc, "mm_kmeans_assign")
+    _call(dev, _lib.lib().mm_kmeans_assign, (x.data_ptr(), centroids.data_ptr(), n, nlist, E, _DT[x.dtype], out_l.data_ptr(),
+                                             out_s.data_ptr()), stream_only=True)
     return out_l, out_s
 
 
@@ -1220,12 +1177,9 @@ def kmeans_segment_sum(x: torch.Tensor, order: torch.Tensor, list_begin: torch.T
     x, order, list_begin = x.contiguous(), order.contiguous(), list_begin.contiguous()
     sums = torch.empty((nlist, E), dtype=torch.float32, device=dev)
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_kmeans_segment_sum_workspace_bytes, n, nlist, E)
-        ws = _workspace(dev, wsb)
-        rc = L.mm_kmeans_segment_sum(x.data_ptr() if n else None, order.data_ptr() if n else None, list_begin.data_ptr(), n,
-                                     nlist, E, _DT[x.dtype], sums.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_kmeans_segment_sum")
+    _call(dev, L.mm_kmeans_segment_sum, (x.data_ptr() if n else None, order.data_ptr() if n else None, list_begin.data_ptr(), n,
+                                         nlist, E, _DT[x.dtype], sums.data_ptr()),
+          L.mm_kmeans_segment_sum_workspace_bytes, (n, nlist, E), cached=True)
     return sums
 
 
@@ -1236,13 +1190,10 @@ def topk_merge(scores: torch.Tensor, ids: torch.Tensor, k: int):
     scores = scores.to(torch.float32).contiguous()
     ids = ids.to(torch.int64).contiguous()
     nq, n_in = scores.shape
-    out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
-    out_i = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    out_s, out_i = _topk_out(dev, nq, k)
     if nq:
-        with _on(dev):
-            rc = _lib.lib().mm_topk_merge(scores.data_ptr(), ids.data_ptr(), nq, n_in, k, out_s.data_ptr(),
-                                          out_i.data_ptr(), _stream(dev))
-        _lib.check(rc, "mm_topk_merge")
+        _call(dev, _lib.lib().mm_topk_merge, (scores.data_ptr(), ids.data_ptr(), nq, n_in, k, out_s.data_ptr(), out_i.data_ptr()),
+              stream_only=True)
     return out_s, out_i
 
 
@@ -1288,13 +1239,10 @@ def colbert_candidates(hit_rows: torch.Tensor, begin_sorted: torch.Tensor, end_s
     if nq == 0:
         return cand_doc, cand_begin, cand_end, count
     L = _lib.lib()
-    with _on(dev):
-        wsb = _ws_bytes(L.mm_colbert_candidates_workspace_bytes, nq, H)
-        ws = _workspace(dev, wsb)
-        rc = L.mm_colbert_candidates(hit_rows.data_ptr(), begin_sorted.data_ptr(), end_sorted.data_ptr(), doc_of_sorted.data_ptr(),
-                                     n_docs, int(T), nq, H, c_cap, cand_doc.data_ptr(), cand_begin.data_ptr(),
-                                     cand_end.data_ptr(), count.data_ptr(), ws.data_ptr(), wsb, _stream(dev))
-    _lib.check(rc, "mm_colbert_candidates")
+    _call(dev, L.mm_colbert_candidates, (hit_rows.data_ptr(), begin_sorted.data_ptr(), end_sorted.data_ptr(),
+                                         doc_of_sorted.data_ptr(), n_docs, int(T), nq, H, c_cap, cand_doc.data_ptr(),
+                                         cand_begin.data_ptr(), cand_end.data_ptr(), count.data_ptr()),
+          L.mm_colbert_candidates_workspace_bytes, (nq, H), cached=True)
     return cand_doc, cand_begin, cand_end, count
 
 

@@ -1,11 +1,13 @@
 """GPU test of the one thing ops._call could get wrong: the stream and the workspace an operator's native call gets.  Every
-scoring operator that goes through the helper is called on a side stream, at a tiny shape whose workspace is not empty and at
+scoring and retrieval operator that goes through the helper is called on a side stream, at a tiny shape whose workspace is not empty and at
 one whose workspace query exceeds the 65,536-byte floor of the cached buffers, and must return the bits of the same calls on
 the default stream.  Operators whose policy is a fresh workspace must leave the cache ops._WS alone; the cached ones must
 replace their first buffer when the second call needs a larger one.  The forwards whose entry points need no workspace
 (PACRR, CO-PACRR, DRMM) are held to the same bits and to leaving the cache alone; MatchPyramid's workspace is empty at the tiny
 shape by construction (a slot exists only for an activation plane that does not fit the LDS, so the smallest non-empty
-workspace is larger than the floor): it is called at the tiny shape without one and at a shape with one."""
+workspace is larger than the floor): it is called at the tiny shape without one and at a shape with one.  The flat top-k
+operators allocate fresh and exceed the floor already at the tiny shape (two candidate lists of 4,096 entries per query); the
+retrieval operators whose entry points end in the stream alone are held like the other forwards without a workspace."""
 import pytest
 import torch
 
@@ -173,7 +175,112 @@ def _matchpyramid_features(ops, L, K, dev, gen, B):
     return ops.mm_matchpyramid_workspace_bytes(B, Qm, Dm, 1, *layers), lambda: (ops.matchpyramid_features(q, d, w, b, pools),)
 
 
+# ---- retrieval: the tiny shape is 3 queries against 40 store rows in 4 lists, nprobe 2, E = 128, fp16, k = 2; the second one
+# 64 queries against 2,000 rows (the flat top-k: 5,000, past the 4,096 rows up to which every row is a candidate)
+RK = 2
+
+
+def _store(dev, gen, B, n_big=2000):
+    """(queries [nq, 128], rows [n, 128], list_begin [5], probes [nq, 2] of distinct lists)"""
+    nq, n = (3, 40) if B == TINY else (64, n_big)
+    lb = torch.arange(5, dtype=torch.int64) * (n // 4)
+    probes = torch.stack([torch.randperm(4, generator=gen)[:2] for _ in range(nq)]).to(torch.int32)
+    return _emb(gen, dev, torch.float16, nq, 128), _emb(gen, dev, torch.float16, n, 128), lb.to(dev), probes.to(dev)
+
+
+def _dot_topk(ops, L, K, dev, gen, B):
+    q, x, _, _ = _store(dev, gen, B, 5000)
+    return L.mm_dot_topk_workspace_bytes(x.shape[0], q.shape[0], RK), lambda: ops.dot_topk(q, x, RK)
+
+
+def _dot_topk_fp8(ops, L, K, dev, gen, B):
+    q, x, _, _ = _store(dev, gen, B, 5000)
+    codes, scales = ops.fp8_quantize_rows(x)
+    return L.mm_dot_topk_fp8_workspace_bytes(x.shape[0], q.shape[0], RK), lambda: ops.dot_topk_fp8(q, codes, scales, RK)
+
+
+def _ivf_scan(ops, L, K, dev, gen, B):
+    q, x, lb, probes = _store(dev, gen, B)
+    return L.mm_ivf_scan_workspace_bytes(x.shape[0], 4, q.shape[0], 2, RK), lambda: ops.ivf_scan(q, x, lb, probes, RK)
+
+
+def _ivf_scan_fp8(ops, L, K, dev, gen, B):
+    q, x, lb, probes = _store(dev, gen, B)
+    codes, scales = ops.fp8_quantize_rows(x)
+    return L.mm_ivf_scan_fp8_workspace_bytes(x.shape[0], 4, q.shape[0], 2, RK), \
+        lambda: ops.ivf_scan_fp8(q, codes, scales, lb, probes, RK)
+
+
+def _codebook(dev, gen):
+    return _emb(gen, dev, torch.float16, 64, 16, 2)
+
+
+def _ah_scan(ops, L, K, dev, gen, B):
+    q, x, lb, probes = _store(dev, gen, B)
+    codes = torch.randint(0, 256, (x.shape[0], 32), generator=gen).to(torch.uint8).to(dev)
+    book, ps = _codebook(dev, gen), _emb(gen, dev, torch.float32, q.shape[0], 2)
+    return L.mm_ah_scan_workspace_bytes(x.shape[0], 4, q.shape[0], 2, RK), lambda: ops.ah_scan(q, codes, book, lb, probes, ps, RK)
+
+
+def _graph_search(ops, L, K, dev, gen, B):
+    # tiny: the visited table fits the LDS (a 256-byte workspace); second shape: one slice of global memory per query
+    nq, n, M, ef, width, n_entry, iters = (3, 40, 4, 8, 2, 2, 12) if B == TINY else (64, 20000, 32, 64, 4, 8, 64)
+    q, x = _emb(gen, dev, torch.float16, nq, 128), _emb(gen, dev, torch.float16, n, 128)
+    nbr = torch.randint(0, n, (n, M), generator=gen).to(torch.int32).to(dev)
+    entry = torch.randint(0, n, (nq, n_entry), generator=gen).to(torch.int32).to(dev)
+    return L.mm_graph_search_workspace_bytes(n, nq, M, ef, width, n_entry, iters), \
+        lambda: ops.graph_search(q, x, nbr, entry, ef, RK, width=width, max_iters=iters, return_stats=True)
+
+
+def _kmeans_segment_sum(ops, L, K, dev, gen, B):
+    n = 40 if B == TINY else 70000                             # 3 lists: 136 chunks of 512 rows at the second shape
+    x = _emb(gen, dev, torch.float16, n, 128)
+    order = torch.randperm(n, generator=gen).to(dev)
+    lb = torch.tensor([0, n // 3, 2 * n // 3, n], dtype=torch.int64, device=dev)
+    return L.mm_kmeans_segment_sum_workspace_bytes(n, 3, 128), lambda: (ops.kmeans_segment_sum(x, order, lb),)
+
+
+def _colbert_candidates(ops, L, K, dev, gen, B):
+    nq, H, n_docs, T = (3, 8, 5, 40) if B == TINY else (64, 512, 50, 2000)
+    hits = torch.randint(-1, T, (nq, H), generator=gen).to(dev)
+    begin = (torch.arange(n_docs, dtype=torch.int64) * (T // n_docs)).to(dev)
+    doc_of = torch.randperm(n_docs, generator=gen).to(torch.int32).to(dev)
+    return L.mm_colbert_candidates_workspace_bytes(nq, H), lambda: ops.colbert_candidates(hits, begin, begin + T // n_docs, doc_of, T)
+
+
+def _ah_encode(ops, L, K, dev, gen, B):
+    _, x, _, _ = _store(dev, gen, B)
+    lists = torch.randint(0, 4, (x.shape[0],), generator=gen).to(torch.int32).to(dev)
+    cent, book = _emb(gen, dev, torch.float16, 4, 128), _codebook(dev, gen)
+    return 0, lambda: (ops.ah_encode(x, lists, cent, book, 4.0),)
+
+
+def _gather_dot(ops, L, K, dev, gen, B):
+    q, x, _, _ = _store(dev, gen, B)
+    rows = torch.randint(-1, x.shape[0], (q.shape[0], 70), generator=gen).to(dev)      # two workgroups per query
+    return 0, lambda: (ops.gather_dot(q, x, rows),)
+
+
+def _kmeans_assign(ops, L, K, dev, gen, B):
+    _, x, _, _ = _store(dev, gen, B)
+    cent = _emb(gen, dev, torch.float16, 4, 128)
+    return 0, lambda: ops.kmeans_assign(x, cent)
+
+
+def _topk_merge(ops, L, K, dev, gen, B):
+    nq = 3 if B == TINY else 64
+    scores = _emb(gen, dev, torch.float32, nq, 6)
+    ids = torch.randint(-1, 1000, (nq, 6), generator=gen).to(dev)
+    return 0, lambda: ops.topk_merge(scores, ids, RK)
+
+
+def _fp8_quantize_rows(ops, L, K, dev, gen, B):
+    _, x, _, _ = _store(dev, gen, B)
+    return 0, lambda: ops.fp8_quantize_rows(x)
+
+
 CACHED, FRESH, FRESH_TINY_EMPTY, NO_WORKSPACE = "cached", "fresh", "fresh, empty at the tiny shape", "no workspace"
+FRESH_TINY_ABOVE_FLOOR = "fresh, above the floor already at the tiny shape"
 
 # operator -> (builder, pairs of the second shape (its workspace exceeds the floor where the operator has one), workspace policy)
 CASES = {
@@ -194,6 +301,20 @@ CASES = {
     "pacrr_kmax": (_pacrr_kmax, 600, NO_WORKSPACE),
     "co_pacrr_kmax": (_co_pacrr_kmax, 600, NO_WORKSPACE),
     "drmm_score": (_drmm_score, 600, NO_WORKSPACE),
+    # retrieval (the second number only says "not the tiny shape": the builders above choose the shapes)
+    "ivf_scan": (_ivf_scan, 64, CACHED),
+    "ivf_scan_fp8": (_ivf_scan_fp8, 64, CACHED),
+    "ah_scan": (_ah_scan, 64, CACHED),
+    "graph_search": (_graph_search, 64, CACHED),
+    "kmeans_segment_sum": (_kmeans_segment_sum, 70000, CACHED),
+    "colbert_candidates": (_colbert_candidates, 64, CACHED),
+    "dot_topk": (_dot_topk, 64, FRESH_TINY_ABOVE_FLOOR),
+    "dot_topk_fp8": (_dot_topk_fp8, 64, FRESH_TINY_ABOVE_FLOOR),
+    "ah_encode": (_ah_encode, 64, NO_WORKSPACE),
+    "gather_dot": (_gather_dot, 64, NO_WORKSPACE),
+    "kmeans_assign": (_kmeans_assign, 64, NO_WORKSPACE),
+    "topk_merge": (_topk_merge, 64, NO_WORKSPACE),
+    "fp8_quantize_rows": (_fp8_quantize_rows, 64, NO_WORKSPACE),
 }
 
 
@@ -212,6 +333,8 @@ def test_side_stream_calls_equal_the_default_stream_and_keep_the_workspace_polic
         assert wsb_tiny == 0 and wsb_big == 0
     elif policy == FRESH_TINY_EMPTY:
         assert wsb_tiny == 0 and FLOOR < wsb_big
+    elif policy == FRESH_TINY_ABOVE_FLOOR:
+        assert FLOOR < wsb_tiny <= wsb_big
     else:
         assert 0 < wsb_tiny <= FLOOR < wsb_big
     want = [run() for _, run in calls]                         # default stream
