@@ -913,6 +913,50 @@ int mm_ivf_scan_fp8_fwd(const void* queries, const uint8_t* codes, const float* 
                         float* out_scores, int64_t* out_rows,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * ColBERT store writer: a batch of encoder output -> its token rows appended to a resident store (additive:
+ * MM_ABI_VERSION unchanged).
+ *
+ * Replaces: the host half of the encode loop, matchmaker/dense_retrieval.py:232-265 — the copy of the padded batch to the
+ *           CPU (:232), the per-document removal of all-zero rows (:244), the copy into the memmap (:259-261) and
+ *           doc_infos[seq_id] = (file, start, end) (:264) — for a store that stays on the device.
+ *
+ *   x [n_docs, D, E] of `dtype` (MM_F32 / MM_F16 / MM_BF16), contiguous, 16-byte aligned.
+ *   Row (b, j) is KEPT iff one of its elements has a non-zero magnitude (bits & ~sign != 0: -0.0 counts as zero).  For
+ *   finite input that is the reference's `abs().sum(-1) > 0` in the store's dtype.  Non-finite input is the caller's error,
+ *   as for mm_fp8_quantize_rows (a row holding NaN is dropped by the reference and kept here).
+ *   flags & MM_STORE_KEEP_ZERO_ROWS keeps every row: the reference's one-vector-per-document case (dim_count == 1,
+ *   :243-246), called with D = 1.
+ *   Kept rows are written back to back in document order, then token order, from store row fill[0] on:
+ *     doc_begin[b] = fill_in + (kept rows of the documents < b),  doc_end[b] = doc_begin[b] + kept(b)
+ *   (an empty range for a document without a kept row), and fill[0] becomes fill_in + the batch's kept rows.
+ *   rows_out [capacity, E] of out_dtype (or NULL): out_dtype == dtype copies the bits; MM_F32 -> MM_F16 / MM_BF16 rounds to
+ *     nearest even with overflow to +-inf (numpy's and torch's cast); MM_F16 / MM_BF16 -> MM_F32 widens exactly;
+ *     MM_F16 <-> MM_BF16 returns MM_EUNSUPPORTED.
+ *   codes_out [capacity, E] + scales_out [capacity] (or both NULL): exactly mm_fp8_quantize_rows of the kept rows in `dtype`
+ *     (one copy of the device code serves both).  Either output or both may be given; neither returns MM_EINVAL.
+ *   Capacity is all or nothing per batch: if fill_in + kept > capacity the call writes no row and no doc_begin / doc_end,
+ *   leaves fill[0] unchanged and sets status[0] = 1.  status is sticky: when it is non-zero on entry the call does nothing.
+ *   No store uses a row index >= capacity, no load reads outside x.
+ *   fill [1] int64, status [1] int32, doc_begin / doc_end [n_docs] int64 are DEVICE memory: appends chain through fill with
+ *   no read-back.  Three launches on `stream` (row flags by wavefront ballot; a one-workgroup scan with the capacity test;
+ *   scatter), no allocation, no host synchronisation, no atomics and no workgroup waiting on another: graph-capturable as a
+ *   single chain, and two runs give the same bits.
+ *   Limits: E * sizeof(dtype) % 16 != 0, or an fp8 output with E % 16 != 0, returns MM_EUNSUPPORTED; n_docs * D < 2^31 (the
+ *   kernels have no separate limit for D or n_docs; the scan is one workgroup, so its time grows with n_docs * D / 64);
+ *   n_docs = 0 succeeds and changes nothing.
+ *   workspace: mm_store_append_workspace_bytes(n_docs, D) bytes (12 bytes per 64 rows of the batch); one byte less returns
+ *   MM_EWORKSPACE with nothing written.
+ */
+#define MM_STORE_KEEP_ZERO_ROWS 1
+
+size_t mm_store_append_workspace_bytes(int n_docs, int D);
+
+int mm_store_append(const void* x, int n_docs, int D, int E, int dtype, int flags,
+                    void* rows_out, int out_dtype, uint8_t* codes_out, float* scales_out, int64_t capacity,
+                    int64_t* fill, int64_t* doc_begin, int64_t* doc_end, int32_t* status,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ from ._lib import NativeError, LIB_PATH  # noqa: F401
 from . import ops  # noqa: F401
 
 __all__ = ["ops", "NativeError", "LIB_PATH", "FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer",
-           "TokenStore", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8"]
+           "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8"]
 
 
 def __getattr__(name):          # the indexers, imported on first use (retrieval pulls in torch.distributed)
@@ -15,6 +15,12 @@ def __getattr__(name):          # the indexers, imported on first use (retrieval
     if name == "TokenStore":    # the ColBERT token store (16-bit, or fp8: TokenStore.quantize_fp8 / load(..., fp8=True))
         from .token_store import TokenStore
         return TokenStore
+    if name == "TokenStoreWriter":   # the device-side writer of that store (encoder output -> TokenStore)
+        from .token_store import TokenStoreWriter
+        return TokenStoreWriter
+    if name == "encode_collection":
+        from .encode import encode_collection
+        return encode_collection
     if name in ("fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8"):   # the fp8 store's operators
         return getattr(ops, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

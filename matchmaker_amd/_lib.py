@@ -13,6 +13,7 @@ MM_F32, MM_F16, MM_BF16 = 0, 1, 2
 MASK_NONE, MASK_LEN_I32, MASK_U8, MASK_I64, MASK_F32 = 0, 1, 2, 3, 4
 TKL_SAT_EMBEDDING, TKL_SAT_LOG = 0, 1
 SIM_ROUND, SUM_ROUND = 1, 2          # MM_SIM_ROUND / MM_SUM_ROUND
+STORE_KEEP_ZERO_ROWS = 1             # MM_STORE_KEEP_ZERO_ROWS
 ABI_VERSION = 4
 MM_OK, MM_EINVAL, MM_EUNSUPPORTED, MM_EWORKSPACE, MM_ELAUNCH = 0, -1, -2, -3, -4
 
@@ -99,6 +100,8 @@ SIGNATURES = {
     "mm_dot_topk_fp8_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _c.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
     "mm_ivf_scan_fp8_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
     "mm_ivf_scan_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "mm_store_append_workspace_bytes": (_sz, [_i, _i]),
+    "mm_store_append": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-// Device helpers of the fp8 token store kernels (maxsim_fp8.hip, dot_topk_fp8.hip): code conversion and the LDS-DMA ring slot
-// of one-byte elements.  gfx950 only.
+// Device helpers of the fp8 token store kernels (maxsim_fp8.hip, dot_topk_fp8.hip, store_writer.hip): code conversion, the
+// row quantiser and the LDS-DMA ring slot of one-byte elements.  gfx950 only.
 #pragma once
 #include "mm_internal.h"
 
@@ -26,6 +26,83 @@ __device__ __forceinline__ short8 cvt8(u32x2 c) {
     o[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(c[1], 1.0f, true));
   }
   return __builtin_bit_cast(short8, o);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Row quantiser (the store format of include/mm_native.h), shared by fp8_quantize_rows_kernel (maxsim_fp8.hip) and the store
+// writer's scatter kernel (store_writer.hip).  One 16-lane group per row: a lane owns the 8-element units l, l + 16, ... of
+// its row (one 16-byte load of 16-bit input, one 8-byte store of codes), so a dim-128 row is exactly one unit per lane and
+// is read once; wider rows re-read the units after the first from L1/L2 in the second pass.
+// ---------------------------------------------------------------------------------------------
+template <int DT>
+__device__ __forceinline__ void load8(const void* row, int u, float (&v)[8]) {
+  if constexpr (DT == MM_F32) {
+    const f32x4 a = *(const f32x4*)((const char*)row + u * 32), b = *(const f32x4*)((const char*)row + u * 32 + 16);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = a[j];
+      v[4 + j] = b[j];
+    }
+  } else if constexpr (DT == MM_F16) {
+    const f16x8 s = *(const f16x8*)((const char*)row + u * 16);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = (float)s[j];
+  } else {
+    const u32x4 s = *(const u32x4*)((const char*)row + u * 16);     // bf16 pairs: the low half is the even element
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[2 * j] = __uint_as_float(s[j] << 16);
+      v[2 * j + 1] = __uint_as_float(s[j] & 0xffff0000u);
+    }
+  }
+}
+
+__device__ __forceinline__ u32x2 quant8(const float (&v)[8], float inv) {
+  // x * inv is exact (inv is a power of two) unless it underflows fp32, far below half of e4m3's smallest subnormal
+  int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
+  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w0, true);
+  int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
+  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, w1, true);
+  return u32x2{(uint32_t)w0, (uint32_t)w1};
+}
+
+// Lane l (0..15) of the group that owns the row at xr [E] of type DT: the row's codes to cr [E], its scale to *scale.
+// The whole 16-lane group must call it together (the maximum is reduced with shuffles inside the group).
+template <int DT>
+__device__ __forceinline__ void fp8_quantize_row(const char* xr, int E, int l, uint8_t* cr, float* scale) {
+  const int nu = E >> 3;
+  float first[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) first[j] = 0.0f;
+  float a = 0.0f;
+  for (int u = l; u < nu; u += 16) {
+    float v[8];
+    load8<DT>(xr, u, v);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(v[j]));
+    if (u == l) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) first[j] = v[j];
+    }
+  }
+#pragma unroll
+  for (int o = 8; o >= 1; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
+  // s = 2^clamp(floor(log2 a) - 7, -126, 120), 1.0 for a zero row.  A subnormal a has exponent field 0 -> -127 - 7 clamps
+  // to -126 like its true logarithm would.
+  int k = (int)((__float_as_uint(a) >> 23) & 0xffu) - 127 - 7;
+  k = k < -126 ? -126 : (k > 120 ? 120 : k);
+  if (a == 0.0f) k = 0;
+  const float inv = __uint_as_float((uint32_t)(127 - k) << 23);
+  if (l == 0) *scale = __uint_as_float((uint32_t)(127 + k) << 23);
+  for (int u = l; u < nu; u += 16) {
+    if (u == l) {
+      *(u32x2*)(cr + u * 8) = quant8(first, inv);
+    } else {
+      float v[8];
+      load8<DT>(xr, u, v);
+      *(u32x2*)(cr + u * 8) = quant8(v, inv);
+    }
+  }
 }
 
 // A ring slot holds ROWS token rows x one 128-code slice, and behind them the rows' scales (a 256-byte tail).

@@ -35,84 +35,17 @@ struct Fp8Args {
 };
 
 // ---------------------------------------------------------------------------------------------
-// Quantiser.  One 16-lane group per row (four rows per wavefront, 16 per workgroup): a lane owns the 8-element units
-// l, l + 16, ... of its row (one 16-byte load of 16-bit input, one 8-byte store of codes), so a dim-128 row is exactly
-// one unit per lane and is read once; wider rows re-read the units after the first from L1/L2 in the second pass.
+// Quantiser.  One 16-lane group per row (four rows per wavefront, 16 per workgroup); the per-row code is fp8_quantize_row
+// (fp8_device.h), which the store writer's scatter kernel runs as well.
 // No atomics, every output byte written once, no dependence on launch geometry: two calls give the same bits.
 // ---------------------------------------------------------------------------------------------
-template <int DT>
-__device__ __forceinline__ void load8(const void* row, int u, float (&v)[8]) {
-  if constexpr (DT == MM_F32) {
-    const f32x4 a = *(const f32x4*)((const char*)row + u * 32), b = *(const f32x4*)((const char*)row + u * 32 + 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = a[j];
-      v[4 + j] = b[j];
-    }
-  } else if constexpr (DT == MM_F16) {
-    const f16x8 s = *(const f16x8*)((const char*)row + u * 16);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = (float)s[j];
-  } else {
-    const u32x4 s = *(const u32x4*)((const char*)row + u * 16);     // bf16 pairs: the low half is the even element
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(s[j] << 16);
-      v[2 * j + 1] = __uint_as_float(s[j] & 0xffff0000u);
-    }
-  }
-}
-
-__device__ __forceinline__ u32x2 quant8(const float (&v)[8], float inv) {
-  // x * inv is exact (inv is a power of two) unless it underflows fp32, far below half of e4m3's smallest subnormal
-  int w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
-  w0 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, w0, true);
-  int w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[4] * inv, v[5] * inv, 0, false);
-  w1 = __builtin_amdgcn_cvt_pk_fp8_f32(v[6] * inv, v[7] * inv, w1, true);
-  return u32x2{(uint32_t)w0, (uint32_t)w1};
-}
-
 template <int DT>
 __global__ void __launch_bounds__(256) fp8_quantize_rows_kernel(const void* x, int64_t n_rows, int E, uint8_t* codes, float* scales) {
   const int l = threadIdx.x & 15;
   const int64_t row = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
-  if (row >= n_rows) return;                       // (a whole 16-lane group leaves; the shuffles below stay inside a group)
+  if (row >= n_rows) return;                       // (a whole 16-lane group leaves; the shuffles stay inside a group)
   constexpr int ES = DT == MM_F32 ? 4 : 2;
-  const char* xr = (const char*)x + row * (int64_t)E * ES;
-  const int nu = E >> 3;
-  float first[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) first[j] = 0.0f;
-  float a = 0.0f;
-  for (int u = l; u < nu; u += 16) {
-    float v[8];
-    load8<DT>(xr, u, v);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) a = fmaxf(a, fabsf(v[j]));
-    if (u == l) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) first[j] = v[j];
-    }
-  }
-#pragma unroll
-  for (int o = 8; o >= 1; o >>= 1) a = fmaxf(a, __shfl_xor(a, o, 64));
-  // s = 2^clamp(floor(log2 a) - 7, -126, 120), 1.0 for a zero row.  A subnormal a has exponent field 0 -> -127 - 7 clamps
-  // to -126 like its true logarithm would.
-  int k = (int)((__float_as_uint(a) >> 23) & 0xffu) - 127 - 7;
-  k = k < -126 ? -126 : (k > 120 ? 120 : k);
-  if (a == 0.0f) k = 0;
-  const float inv = __uint_as_float((uint32_t)(127 - k) << 23);
-  if (l == 0) scales[row] = __uint_as_float((uint32_t)(127 + k) << 23);
-  uint8_t* cr = codes + row * (int64_t)E;
-  for (int u = l; u < nu; u += 16) {
-    if (u == l) {
-      *(u32x2*)(cr + u * 8) = quant8(first, inv);
-    } else {
-      float v[8];
-      load8<DT>(xr, u, v);
-      *(u32x2*)(cr + u * 8) = quant8(v, inv);
-    }
-  }
+  fp8_quantize_row<DT>((const char*)x + row * (int64_t)E * ES, E, l, codes + row * (int64_t)E, scales + row);
 }
 
 // ---------------------------------------------------------------------------------------------

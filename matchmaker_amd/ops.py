@@ -1246,6 +1246,69 @@ def colbert_candidates(hit_rows: torch.Tensor, begin_sorted: torch.Tensor, end_s
     return cand_doc, cand_begin, cand_end, count
 
 
+def store_append(x: torch.Tensor, rows_out: Optional[torch.Tensor], codes_out: Optional[torch.Tensor],
+                 scales_out: Optional[torch.Tensor], capacity: int, fill: torch.Tensor, doc_begin: torch.Tensor,
+                 doc_end: torch.Tensor, status: torch.Tensor, keep_zero_rows: bool = False) -> None:
+    """A batch of encoder output -> its non-zero token rows appended to a resident store (the host half of the encode loop,
+    matchmaker/dense_retrieval.py:232-265; native mm_store_append, include/mm_native.h).
+
+    x [n_docs, D, E] fp16 / bf16 / fp32.  A row is kept iff it has an element of non-zero magnitude (keep_zero_rows: every
+    row); the kept rows go back to back, document by document, to store rows fill[0] .. of
+      rows_out [>= capacity, E] (x's dtype: the bits; fp32 -> fp16 / bf16 rounded to nearest even; fp16 / bf16 -> fp32), and / or
+      codes_out [>= capacity, E] uint8 + scales_out [>= capacity] float32 = fp8_quantize_rows of the kept rows;
+    doc_begin / doc_end [n_docs] int64 receive the documents' row ranges, fill [1] int64 advances, status [1] int32 is set to
+    1 (and stays: later calls do nothing) when a batch does not fit below `capacity` — such a batch writes nothing at all.
+    The five buffers are written in place, so they must be contiguous tensors (or contiguous slices) of the device.  Three
+    launches on the current stream, no read-back: appends chain through `fill` and can be captured into a graph."""
+    dev = _dev_check(x, rows_out, codes_out, scales_out, fill, doc_begin, doc_end, status)
+    if x.dim() != 3 or x.dtype not in _DT:
+        raise NativeError(f"store_append: x: expected [n_docs, D, E] fp16 / bf16 / fp32, got {tuple(x.shape)} {x.dtype}")
+    n_docs, D, E = x.shape
+    capacity = int(capacity)
+    if rows_out is None and codes_out is None and scales_out is None:
+        raise NativeError("store_append: neither rows_out nor codes_out / scales_out given", _lib.MM_EINVAL)
+    if (codes_out is None) != (scales_out is None):
+        raise NativeError("store_append: codes_out and scales_out go together", _lib.MM_EINVAL)
+    if D < 1 or E < 1 or capacity < 0:
+        raise NativeError(f"store_append: bad shape {tuple(x.shape)} / capacity {capacity}", _lib.MM_EINVAL)
+    if rows_out is not None:
+        if rows_out.dtype not in _DT or rows_out.dim() != 2 or rows_out.shape[1] != E or rows_out.shape[0] < capacity:
+            raise NativeError(f"store_append: rows_out: expected [>= {capacity}, {E}] fp16 / bf16 / fp32, got "
+                              f"{tuple(rows_out.shape)} {rows_out.dtype}")
+        if rows_out.dtype != x.dtype and torch.float32 not in (rows_out.dtype, x.dtype):
+            raise NativeError(f"store_append: {x.dtype} -> {rows_out.dtype} is not a conversion the store makes (convert the batch)",
+                              _lib.MM_EUNSUPPORTED)
+    if codes_out is not None:
+        if (codes_out.dtype != torch.uint8 or codes_out.dim() != 2 or codes_out.shape[1] != E or codes_out.shape[0] < capacity
+                or scales_out.dtype != torch.float32 or scales_out.dim() != 1 or scales_out.shape[0] < capacity):
+            raise NativeError(f"store_append: codes_out / scales_out: expected [>= {capacity}, {E}] uint8 and [>= {capacity}] float32, got "
+                              f"{tuple(codes_out.shape)} {codes_out.dtype} / {tuple(scales_out.shape)} {scales_out.dtype}")
+    if (E * x.element_size()) % 16:
+        raise NativeError(f"store_append: a row of E={E} {x.dtype} elements is not a multiple of 16 bytes", _lib.MM_EUNSUPPORTED)
+    if codes_out is not None and E % 16:
+        raise NativeError(f"store_append: an fp8 store needs E % 16 == 0, got E={E}", _lib.MM_EUNSUPPORTED)
+    if n_docs * D >= 2 ** 31:
+        raise NativeError(f"store_append: n_docs * D = {n_docs * D} rows in one batch, the limit is 2^31 - 1", _lib.MM_EUNSUPPORTED)
+    if (fill.dtype != torch.int64 or fill.numel() != 1 or status.dtype != torch.int32 or status.numel() != 1
+            or doc_begin.dtype != torch.int64 or doc_end.dtype != torch.int64 or tuple(doc_begin.shape) != (n_docs,)
+            or tuple(doc_end.shape) != (n_docs,)):
+        raise NativeError(f"store_append: fill [1] int64, status [1] int32 and doc_begin / doc_end [{n_docs}] int64 needed")
+    for name, t in (("rows_out", rows_out), ("codes_out", codes_out), ("scales_out", scales_out), ("fill", fill),
+                    ("doc_begin", doc_begin), ("doc_end", doc_end), ("status", status)):
+        if t is not None and not t.is_contiguous():
+            raise NativeError(f"store_append: {name} is written in place and must be contiguous")
+    if n_docs == 0:
+        return
+    x = x.contiguous()
+    p = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+    L = _lib.lib()
+    _call(dev, L.mm_store_append, (x.data_ptr(), n_docs, D, E, _DT[x.dtype], _lib.STORE_KEEP_ZERO_ROWS if keep_zero_rows else 0,
+                                   p(rows_out), _DT[rows_out.dtype] if rows_out is not None else _DT[x.dtype], p(codes_out),
+                                   p(scales_out), capacity, fill.data_ptr(), doc_begin.data_ptr(), doc_end.data_ptr(),
+                                   status.data_ptr()),
+          L.mm_store_append_workspace_bytes, (n_docs, D), cached=True)
+
+
 def _pacrr_params(weights, biases, C: int, dev):
     """Packs the conv weights ([C, 1, n, n] or [C, n, n], widths 2 .. N in order) and biases ([C] each) into the two float
     buffers of mm_pacrr_fwd: C * (4 + .. + N^2) weights, (N - 1) * C biases.  Returns (w, b) or (None, None) for N = 1."""

@@ -28,6 +28,10 @@ the rows kept with `keep_tokens=True`.
 `row_shard=` runs a flat token search (16-bit or fp8) over consecutive shards of that many rows and merges the per-shard
 lists (ops.topk_merge): the one-call search places its sampled threshold only up to about 1.3 M rows at k' = 128
 (DESIGN §3.12); `row_shard = 2**20` is the recommended setting for stores beyond that.
+
+`TokenStoreWriter` builds a store on the device straight from encoder output: `append(seq_ids, vecs)` per batch
+(ops.store_append: the zero-row removal and doc_infos of dense_retrieval.py:232-265 as a stream compaction, 16-bit rows and / or
+fp8 codes + scales), `finish()` for the TokenStore; `TokenStore.save_reference` writes a store back in the reference's layout.
 """
 import glob
 import os
@@ -200,6 +204,66 @@ class TokenStore:
         ids[:] = list(self.seq_ids)
         np.savez(os.path.join(folder, "docs.npz"), seq_ids=ids, begin=self._begin, end=self._end,
                  source_dtype=np.array(str(self._source_dtype).replace("torch.", "")))
+
+    def save_reference(self, folder: str, token_block_size: int, token_dtype: Optional[str] = None) -> None:
+        """Writes a 16-bit or fp32 store in the reference's layout (dense_retrieval.py:205-206, 246-279): raw memmaps
+        `token_reps_<n>.npy` of token_block_size rows, the documents in seq_ids order, no document straddling a file, and
+        `doc_infos.npz` — byte for byte what write_reference_store writes for the same documents, so the reference's
+        skip-encoding branch (:291-302) and TokenStore.load read it.  token_dtype: numpy's name of the files' dtype (default:
+        the store's own; the rows are cast with torch when it differs).  Runs of documents that are neighbours in the store
+        and in a file cross to the host in one copy."""
+        if self._tokens is None:
+            raise ops.NativeError("TokenStore.save_reference: an fp8-only store holds no rows the reference's layout can take — "
+                              "save_fp8() writes it")
+        name = token_dtype or str(self._tokens.dtype).replace("torch.", "")
+        if name not in ("float16", "float32"):
+            raise ops.NativeError(f"TokenStore.save_reference: token_dtype={name!r}: numpy memmaps hold float16 or float32 (pass one)")
+        np_dt, t_dt = np.dtype(name), getattr(torch, name)
+        token_block_size = int(token_block_size)
+        lens = self._end - self._begin
+        if lens.size and int(lens.max()) > token_block_size:
+            raise ops.NativeError(f"TokenStore.save_reference: a document of {int(lens.max())} rows does not fit a file of "
+                              f"token_block_size={token_block_size}")
+        os.makedirs(folder, exist_ok=True)
+        E = int(self._tokens.shape[1])
+
+        def new_file(n):
+            return np.memmap(os.path.join(folder, f"token_reps_{n}.npy"), dtype=np_dt, mode="w+", shape=(token_block_size, E))
+
+        n, ins = 0, 0
+        base = new_file(0)
+        doc_infos, filled = {}, []
+        run = None                                       # [store row from, store row to, file row]: one pending copy
+
+        def flush_run():
+            if run is not None:
+                a, b, at = run
+                base[at: at + (b - a)] = self._tokens[a:b].to(t_dt).cpu().numpy()
+
+        for i, sid in enumerate(self.seq_ids):
+            k, a = int(lens[i]), int(self._begin[i])
+            if ins + k > token_block_size:               # :248-256 start the next file
+                flush_run()
+                run = None
+                filled.append(ins)
+                base.flush()
+                n, ins = n + 1, 0
+                base = new_file(n)
+            if k:
+                if run is not None and run[1] == a:
+                    run[1] = a + k
+                else:
+                    flush_run()
+                    run = [a, a + k, ins]
+            doc_infos[sid] = (n, ins, ins + k)
+            ins += k
+        flush_run()
+        filled.append(ins)
+        base.flush()
+        ids = np.empty(len(self.seq_ids), dtype=object)
+        ids[:] = list(self.seq_ids)
+        np.savez(os.path.join(folder, "doc_infos.npz"), doc_infos=np.array(doc_infos, dtype=object), seq_ids=ids,
+                 storage_filled_to_index=np.array(filled), id_mapping=np.array([], dtype=object))
 
     @classmethod
     def load_fp8(cls, folder: str, device, **fns) -> "TokenStore":
@@ -445,6 +509,121 @@ class TokenStore:
         s, d = s.cpu().numpy(), d.cpu().numpy()
         ids = self.seq_ids
         return [[(ids[j], float(x)) for x, j in zip(s[i], d[i]) if j >= 0] for i in range(s.shape[0])]
+
+
+class TokenStoreWriter:
+    """Builds a TokenStore on the device from encoder output, batch by batch: the host half of the reference's encode loop
+    (dense_retrieval.py:232-265 — the copy of the padded batch to the CPU, the per-document removal of zero rows, the copy
+    into a memmap, doc_infos) as one native call per batch (ops.store_append).
+
+        w = TokenStoreWriter(capacity_rows, token_dim, dtype=torch.float16, device="cuda", fp8=False)
+        w.append(seq_ids, vecs)        # vecs [B, D, E]: all-zero rows are padding and dropped; [B, E]: one row each, all kept
+        store = w.finish()             # -> TokenStore
+
+    The writer owns the store's buffers — rows [capacity_rows, token_dim] of `dtype`, or codes + scales with fp8=True, or both
+    with keep_tokens=True — a growing device table of the documents' row ranges, and the device-side fill / status the
+    appends chain through.  append() does not synchronise while the running sum of B * D stays within the capacity; see there.
+    append_fn: what append() runs (default ops.store_append; the CPU test-suite injects a stand-in, as for the indexers);
+    fns: TokenStore's *_fn arguments, handed to the store finish() builds."""
+
+    def __init__(self, capacity_rows: int, token_dim: int, dtype: torch.dtype = torch.float16, device="cuda", fp8: bool = False,
+                 keep_tokens: bool = False, append_fn=None, **fns):
+        if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+            raise ops.NativeError(f"TokenStoreWriter: dtype {dtype} (float16, bfloat16 or float32)")
+        self.capacity, self.token_dim, self.dtype = int(capacity_rows), int(token_dim), dtype
+        if self.capacity < 0 or self.token_dim < 1:
+            raise ops.NativeError(f"TokenStoreWriter: capacity_rows={capacity_rows}, token_dim={token_dim}")
+        self._device = torch.device(device)
+        self._fp8 = bool(fp8)
+        self._append = append_fn if append_fn is not None else ops.store_append
+        self._fns = fns
+        dev, T, E = self._device, self.capacity, self.token_dim
+        self._tokens = torch.empty((T, E), dtype=dtype, device=dev) if (not fp8 or keep_tokens) else None
+        self._codes = torch.empty((T, E), dtype=torch.uint8, device=dev) if fp8 else None
+        self._scales = torch.empty((T,), dtype=torch.float32, device=dev) if fp8 else None
+        self._fill = torch.zeros(1, dtype=torch.int64, device=dev)
+        self._status = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._table = torch.full((2, 1024), -1, dtype=torch.int64, device=dev)   # begin / end per document; -1 = never written
+        self.seq_ids: List = []
+        self._seen = set()
+        self.rows_upper_bound = 0                        # >= the device-side fill, without reading it
+        self._finished = False
+
+    def _grow_table(self, n: int):
+        cap = self._table.shape[1]
+        if n <= cap:
+            return
+        while cap < n:
+            cap *= 2
+        table = torch.full((2, cap), -1, dtype=torch.int64, device=self._device)
+        table[:, : len(self.seq_ids)] = self._table[:, : len(self.seq_ids)]
+        self._table = table
+
+    def append(self, seq_ids: Sequence, vecs: torch.Tensor) -> None:
+        """vecs [B, D, E]: document i's token rows, all-zero rows being padding (the model multiplies by its mask,
+        colbert.py:95-96) — they are dropped, wherever in the document they are.  vecs [B, E]: one vector per document, kept
+        even if zero (the reference's dim_count == 1 case).  Rows are converted to the store's dtype.
+        Nothing synchronises while rows_upper_bound (the running sum of B * D) stays within the capacity.  When it would pass
+        it, the device-side fill is read back once and takes the bound's place; if even that true fill cannot take B * D more
+        rows, NativeError is raised before anything is launched.  Otherwise the batch is launched and the device decides: a
+        batch that does not fit writes nothing and sets the sticky status finish() reports."""
+        if self._finished:
+            raise ops.NativeError("TokenStoreWriter.append: finish() was called — the buffers belong to the store now")
+        seq_ids = list(seq_ids)
+        keep_all = vecs.dim() == 2
+        if keep_all:
+            vecs = vecs.unsqueeze(1)
+        if vecs.dim() != 3 or vecs.shape[0] != len(seq_ids) or vecs.shape[2] != self.token_dim:
+            raise ops.NativeError(f"TokenStoreWriter.append: {len(seq_ids)} seq_ids and vectors {tuple(vecs.shape)}: expected "
+                                  f"[B, D, {self.token_dim}] or [B, {self.token_dim}]")
+        new = set()
+        for s in seq_ids:
+            if s in self._seen or s in new:
+                raise ops.NativeError(f"TokenStoreWriter.append: seq_id {s!r} was appended before")
+            new.add(s)
+        B, D = int(vecs.shape[0]), int(vecs.shape[1])
+        if B == 0:
+            return
+        n = B * D
+        if self.rows_upper_bound + n > self.capacity:
+            true = int(self._fill.item())                # the one read-back
+            if true + n > self.capacity:
+                raise ops.NativeError(f"TokenStoreWriter.append: the store holds {true} of {self.capacity} rows and cannot take a "
+                                      f"batch of {B} x {D} = {n} rows (document {seq_ids[0]!r} on)", ops._lib.MM_EUNSUPPORTED)
+            self.rows_upper_bound = true
+        vecs = vecs.to(self._device)
+        # the kernel converts fp32 <-> 16-bit on the way; an fp8 store is quantised from the values of the store's dtype, as
+        # from_reference_parts(fp8=True) quantises the stored rows
+        if vecs.dtype != self.dtype and (self._fp8 or torch.float32 not in (vecs.dtype, self.dtype)):
+            vecs = vecs.to(self.dtype)
+        n0 = len(self.seq_ids)
+        self._grow_table(n0 + B)
+        self._append(vecs, self._tokens, self._codes, self._scales, self.capacity, self._fill, self._table[0, n0: n0 + B],
+                     self._table[1, n0: n0 + B], self._status, keep_zero_rows=keep_all)
+        self.rows_upper_bound += n
+        self.seq_ids.extend(seq_ids)
+        self._seen |= new
+
+    def finish(self, compact: bool = False) -> "TokenStore":
+        """Reads fill, status and the document table back (once each) and returns the TokenStore over the filled part of the
+        buffers — views; compact=True clones them to their exact size, so the unused capacity can be freed.  Raises
+        NativeError naming the first document that did not fit when an append was refused on the device."""
+        fill, status = int(self._fill.item()), int(self._status.item())
+        n = len(self.seq_ids)
+        table = self._table[:, :n].cpu().numpy()
+        if status != 0:
+            first = int(np.argmax(table[0] < 0)) if n else 0
+            raise ops.NativeError(f"TokenStoreWriter.finish: the store's {self.capacity} rows were full at {fill}: the batch of "
+                                  f"document {self.seq_ids[first]!r} (number {first}) did not fit and nothing after it was "
+                                  "written — build a writer with a larger capacity_rows", ops._lib.MM_EUNSUPPORTED)
+        self._finished = True
+        cut = (lambda t: None if t is None else (t[:fill].clone() if compact else t[:fill]))
+        tokens, codes, scales = cut(self._tokens), cut(self._codes), cut(self._scales)
+        self._tokens = self._codes = self._scales = None
+        if self._fp8:
+            return TokenStore(tokens, self.seq_ids, table[0], table[1], codes=codes, scales=scales, source_dtype=self.dtype,
+                              **self._fns)
+        return TokenStore(tokens, self.seq_ids, table[0], table[1], **self._fns)
 
 
 def write_reference_store(folder: str, docs: Sequence[np.ndarray], seq_ids: Sequence, token_block_size: int,
