@@ -36,18 +36,13 @@ const EnvCfg& env() {
     c.kp_generic = env_int("MM_KP_GENERIC", 0);
     c.kp_f32mfma = env_int("MM_KP_F32MFMA", 0);
     c.dot_prof = env_int("MM_DOT_PROF", 0);
-    c.tkl_pairsums = env_int("MM_TKL_PAIRSUMS", 0);
     c.mp_generic = env_int("MM_MP_GENERIC", 0);
-    c.tkl_fold_regions = env_int("MM_TKL_FOLD_REGIONS", 0);
     c.tkl_bwd_nosplit = env_int("MM_TKL_BWD_NOSPLIT", 0);
     c.kp128_occ = env_int("MM_KP128_OCC", 0);
     c.kp_multi_2d = env_int("MM_KP_MULTI_2D", 0);
-    c.kp_multi_wg = env_int("MM_KP_MULTI_WG", 0);
     c.kp_bwd_untiled = env_int("MM_KP_BWD_UNTILED", 0);
     c.kp_bwd_f32 = env_int("MM_KP_BWD_F32", 0);
     c.kp_bwd_nsplit = env_int("MM_KP_BWD_NSPLIT", 0);
-    c.tkl_stage1_slices = env_int("MM_TKL_STAGE1_SLICES", 0);
-    c.tkl_stage1_ksplit = env_int("MM_TKL_STAGE1_KSPLIT", 0);
     c.kp_multi_loop = env_int("MM_KP_MULTI_LOOP", -1);
     c.kp_bwd_threads = env_int("MM_KP_BWD_THREADS", 1024);
     return c;

@@ -22,7 +22,7 @@
 
 // VALU instructions scheduled behind each MFMA of the split kernels' K steps (sched_group_barrier).  Measured on one box,
 // round-robin: 3: 2.82-2.84 ms | 4: 2.79-2.83 | 5: 2.78-2.79 | 6: 2.79 | 7: 2.81-2.83 | 8: 2.83-2.87 | 10: 2.83-2.85 for TK
-// (profiles/r03_experiments/tk_schedule_ab.txt); TKL's stage 1 does not care (0.135-0.138 ms for 3 .. 12).
+// (profiles/r03_experiments/tk_schedule_ab.txt).
 constexpr int kShadowValu = 5;
 
 // The split-bf16 dot product of the TK pooling kernel is  hi.hi + lo.hi + hi.lo  (three MFMAs per K step): the fourth
@@ -34,10 +34,6 @@ constexpr int kShadowValu = 5;
 // the four-product kernel for A/B runs.
 #ifndef MM_KP_LOLO
 #define MM_KP_LOLO 0
-#endif
-#ifndef MM_TKL_LOLO      // the same switch for TKL's stage 1 (tkl_stage1_run_kernel): parity-neutral there too (window error 2.5e-5 either
-                         // way, 256 / 256 rank positions), -1 us of 138 — the kernel is not power-limited, so it buys little
-#define MM_TKL_LOLO 0
 #endif
 
 namespace mm {
@@ -407,10 +403,9 @@ __device__ __forceinline__ void wait_q_slices(f32x4 (&raw)[NS][13]) {
 // wavefronts per pair — wavefront w of the 128-thread workgroup streams the pair's blocks w, w + 2, ... through its own
 // ring, the kernel sums of the two meet in LDS once per pair and wavefront 0 pools.  A 200-token document is 4 + 3
 // blocks instead of 7 in a row on one wavefront while half of the chip's wavefront slots idle.
-template <int NS, int K, int NBUF, bool NT, bool TKL, bool W = false, int WPP = 1>
+template <int NS, int K, int NBUF, bool NT, bool W = false, int WPP = 1>
 __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArgs a_in) {
-  static_assert(!(TKL && W), "the gate is a TK-Sparse feature");
-  static_assert(WPP == 1 || (WPP == 2 && !TKL && !W), "two wavefronts per pair: plain TK pooling only");
+  static_assert(WPP == 1 || (WPP == 2 && !W), "two wavefronts per pair: plain TK pooling only");
   const KpArgs a = kp_block_args(a_in);
   static_assert(NS >= 1 && NS <= 4, "parked-chunk step holds at most 4 chunks");
   extern __shared__ __attribute__((aligned(16))) char smem_all[];
@@ -508,14 +503,11 @@ __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArg
   int qn = Q, np = 2;  // effective query length; lanes sharing one query token in the epilogue (2 = the MFMA layout)
   int rrows = 0, rtk = 0, rsub = 0;  // redistributed epilogue: rows per lane (0 = MFMA layout), this lane's token and row group
   int64_t cur_q = -1;
-  int64_t qi = TKL ? 0 : p0 / a.ppq;
-  int64_t q_left = TKL ? 0 : a.ppq - (p0 - qi * a.ppq);
+  int64_t qi = p0 / a.ppq;
+  int64_t q_left = a.ppq - (p0 - qi * a.ppq);
 
   for (int64_t pair = p0; pair < p1; ++pair) {
-    if (TKL) {
-      qi = (int64_t)((int)sload_u32(a.chunk_slot, pair) / a.C);
-      tkl_publish_slot(a, pair, (doc_len(pair) + 31) >> 5, lane);
-    } else if (a.pair_q) {
+    if (a.pair_q) {
       qi = (int64_t)(int)sload_u32(a.pair_q, pair);
     } else {
       if (q_left == 0) {
@@ -560,7 +552,7 @@ __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArg
       // queries of <= 21 real tokens: share each query token's epilogue between np = ceil(32 / rows) lanes (see
       // rbf_redistributed): 3 lanes x 11 rows at qn = 20 instead of 2 x 16 with 24 of the 64 lanes idle
       qn = qlen < Q ? (qlen < 0 ? 0 : qlen) : Q;
-      rrows = TKL ? 0 : redist_rows(qn);
+      rrows = redist_rows(qn);
       np = rrows ? (32 + rrows - 1) / rrows : 2;
       rtk = lane / np;
       rsub = lane - rtk * np;
@@ -673,9 +665,7 @@ __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArg
       } else if (a.dm.bits) {
         va = sload_u32(a.dm.bits, pair * nblk_tot + t) & ex;
       }
-      if constexpr (TKL) {
-        tkl_block<K>(a.ps_out + pair * (20 * (int64_t)Q * (K + 1)), Q, t, r, h, acc, rdr, rq, va >> (4 * h), rbf);
-      } else if (np > 2) {
+      if (np > 2) {
         // transpose the scaled tile through the ring slot just consumed (free until the next top_up()):
         // T[query token][32 rows]; then np lanes per token evaluate 32 / np rows each
         float* T = (float*)(smem + (cbuf == 0 ? NBUF - 1 : cbuf - 1) * kSliceBytes);
@@ -716,7 +706,7 @@ __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArg
       }
       asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // comb may be rewritten for the next pair
     }
-    if (!TKL && wv == 0) {
+    if (wv == 0) {
       float pk[kMaxK];
       if (np > 2) {  // np consecutive lanes hold the partial sums of one query token
         pk_get<K>(pk, pk2, rbf);
@@ -730,376 +720,6 @@ __global__ void __launch_bounds__(64 * WPP) kernel_pool_split_kernel(const KpArg
         finish_pool<K>(a, pair, pk, qvalid && lane < 32, lane, rbf, lane < 32 ? lane : -1);
       }
     }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// TKL stage 1, grouped (the default TKL path for E == 100*NS, Q <= 32).
-//
-// A chunk contributes its 40 centre rows = one full 32-row MFMA block + an 8-row remainder that costs
-// a full block of split / MFMA / LDS-DMA work.  Up to four consecutive packed chunks of the SAME
-// document (same query) are therefore treated as one virtual document of 40n rows: n = 4 gives exactly
-// five full blocks instead of eight.  LDS-DMA sources are per-lane addresses anyway, so virtual row i
-// simply maps to row 5 + i % 40 of chunk p + i / 40; position pairs never straddle a chunk (40 is even).
-// Every pair of every chunk of the run is written (zeros where the mask says padding), so stage 2 needs
-// no per-chunk block count.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void sload4_u32(const void* base, int64_t idx, uint32_t (&v)[4]) {
-  const uint32_t* p = (const uint32_t*)base + idx;
-  asm volatile(
-      "s_load_dword %0, %4, 0x0\n\t"
-      "s_load_dword %1, %4, 0x4\n\t"
-      "s_load_dword %2, %4, 0x8\n\t"
-      "s_load_dword %3, %4, 0xc\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&s"(v[0]), "=&s"(v[1]), "=&s"(v[2]), "=&s"(v[3])
-      : "s"(p));
-}
-
-// Epilogue of block t of a run: pairs of virtual rows (i0, i0 + 1), i0 = 32t + rowof(2ip) + 4h, belong
-// to chunk i0 / 40, pair (i0 % 40) / 2.  rows_blk = rows of this block that exist (multiple of 8).
-//
-// The pair sums leave through LDS.  A lane owns one query token, so writing them straight from the registers is
-// 24 store instructions per block whose 40 active lanes each put 16 B at a 48-B stride (measured by removal on
-// config 3: 49 of stage 1's 189 us).  The 16 pair rows of a block are ONE contiguous region of the pair buffer
-// ((chunk * 20 + pair) * Q * 12 floats is linear in the run's pair index), so each half of the block (8 pair rows,
-// <= 12 KiB) is staged in the ring slot the block just freed and written out as one contiguous run of qlim * 48 B per
-// store instruction: 16 stores per block, every one a full-width burst.  (Measured: 189 -> 184 us — the cost is the
-// write traffic in the read stream and the stores sitting in the in-order vmcnt queue, not the shape of the stores.)
-template <int K>
-__device__ __forceinline__ void tkl_block_run(float* ps_run, float* stage, int lane, int Q, int qlim, int t, int rows_blk, int r,
-                                              int h, const f32x16& acc, const float (&rdr)[16], float rq, uint32_t vbits,
-                                              const Rbf& rbf) {
-  constexpr int KC = K + 1;
-  constexpr int KP = (K + 1) / 2;
-  static_assert(KC == 12 && K % 2 == 1, "K kernels + the count channel fill three float4s");
-  f32x4* stage4 = (f32x4*)stage;                                  // [8 pair rows][Q][3]
-  f32x4* out4 = (f32x4*)ps_run + (int64_t)16 * t * (3 * Q);       // pair row g of the run at g * Q * 12 floats
-#pragma unroll
-  for (int hf = 0; hf < 2; ++hf) {
-    if (16 * hf >= rows_blk) break;                               // wave-uniform
-#pragma unroll
-    for (int iq = 0; iq < 4; ++iq) {
-      const int ip = 4 * hf + iq;
-      if (rowof(2 * ip) < rows_blk) {  // wave-uniform (rows_blk is a multiple of 8, rowof(2ip) + 4h + 1 < its 8-row group end)
-        f32x2 o2[KP];
-#pragma unroll
-        for (int k = 0; k < KP; ++k) o2[k] = f32x2{0.0f, 0.0f};
-        float cnt = 0.0f;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-          const int i = 2 * ip + half;
-          float c = (acc[i] * rq) * rdr[i];
-          c = ((vbits >> rowof(i)) & 1u) ? c : 1.0e5f;  // masked: every kernel underflows to exactly 0 (:194)
-          const f32x2 cc = {c, c};
-          f32x2 any2 = {0.0f, 0.0f};
-#pragma unroll
-          for (int kp = 0; kp < KP; ++kp) {
-            const f32x2 sv = cc * rbf.sq2[kp] - rbf.msq2[kp];
-            const f32x2 av = -(sv * sv);
-            const f32x2 e = {__builtin_amdgcn_exp2f(av[0]), __builtin_amdgcn_exp2f(av[1])};
-            o2[kp] += e;
-            any2 += e;
-          }
-          cnt += (any2[0] + any2[1]) != 0.0f ? 1.0f : 0.0f;  // (:210)
-        }
-        const int j8 = ((rowof(2 * ip) + 4 * h) >> 1) - 8 * hf;   // pair row inside this half (0..7)
-        if (r < qlim) {  // query tokens past the query's effective length are masked in stage 2 (:248): never written, never read
-          f32x4* dst = stage4 + (j8 * Q + r) * 3;
-          dst[0] = f32x4{o2[0][0], o2[0][1], o2[1][0], o2[1][1]};
-          dst[1] = f32x4{o2[2][0], o2[2][1], o2[3][0], o2[3][1]};
-          dst[2] = f32x4{o2[KP - 2][0], o2[KP - 2][1], o2[KP - 1][0], cnt};
-        }
-      }
-    }
-    // the half's pair rows that exist: rows_blk / 2 - 8 hf of them (a multiple of 4), one contiguous store each
-    const int npr = rows_blk / 2 - 8 * hf < 8 ? rows_blk / 2 - 8 * hf : 8;
-    for (int l = lane; l < 3 * qlim; l += 64) {                  // (one pass for queries of <= 21 tokens)
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (j < npr) out4[(int64_t)(8 * hf + j) * (3 * Q) + l] = stage4[j * (3 * Q) + l];
-    }
-  }
-}
-
-template <int NS, int K, int NBUF, bool NT, bool COS>
-__global__ void __launch_bounds__(64) tkl_stage1_run_kernel(const KpArgs a) {
-  static_assert(NS >= 1 && NS <= 4, "parked-chunk step holds at most 4 chunks");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x;
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t p0 = (int64_t)blockIdx.x * a.pairs_per_wave;
-  const int64_t p1 = (p0 + a.pairs_per_wave < a.n_pairs) ? p0 + a.pairs_per_wave : a.n_pairs;
-  if (p0 >= p1) return;
-  constexpr int E = 100 * NS;
-  constexpr int RB = E * 4;  // row bytes
-  const int Q = a.Q;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
-  float* rdbuf = (float*)(smem + NBUF * kSliceBytes);
-
-  // slice image: slot s = 64n + lane -> (row, 16-B column) of the 32-row x 25-chunk slice
-  int srow[kSliceInstr];
-  uint32_t scol[kSliceInstr];
-#pragma unroll
-  for (int n = 0; n < kSliceInstr; ++n) {
-    int s = 64 * n + lane;
-    if (s > 32 * kSC - 1) s = 32 * kSC - 1;
-    srow[n] = s / kSC;
-    scol[n] = (uint32_t)((s - srow[n] * kSC) * 16);
-  }
-  const uint32_t a_off = (uint32_t)(r * (kSC * 16) + h * 32);
-  const uint32_t l_off = (uint32_t)(r * (kSC * 16) + 24 * 16);
-
-  Rbf rbf;
-  if constexpr (!COS) load_rbf<K, false>(a.mu, a.sigma, nullptr, nullptr, rbf);   // (the cosine hand-off evaluates no kernels here)
-
-  const char* dbase = (const char*)a.d;
-  // run of up to 4 consecutive packed chunks of one document starting at chunk p (inside [p, p1))
-  auto run_len = [&](int64_t p) -> int {
-    if (p + 4 <= a.n_pairs) {
-      uint32_t sl[4];
-      sload4_u32(a.chunk_slot, p, sl);
-      const int b0 = (int)sl[0] / a.C;
-      int n = 1;
-      while (n < 4 && p + n < p1 && (int)sl[n] / a.C == b0 && (!COS || (int)sl[n] == (int)sl[0] + n)) ++n;
-      return n;
-    }
-    const int s0 = (int)sload_u32(a.chunk_slot, p), b0 = s0 / a.C;
-    int n = 1;
-    while (n < 4 && p + n < p1) {
-      const int sn = (int)sload_u32(a.chunk_slot, p + n);
-      if (sn / a.C != b0 || (COS && sn != s0 + n)) break;
-      ++n;
-    }
-    return n;
-  };
-
-  // ---- producer cursor over (run, block, slice) ------------------------------------------------
-  int64_t pp = p0;
-  int prun = run_len(pp), pn = (40 * prun + 31) >> 5, pt = 0, ps = 0;
-  uint32_t vrun[kSliceInstr];
-  int pbuf = 0, cbuf = 0, inflight = 0;
-  // The epilogue's global stores share the in-order vmcnt queue with the LDS-DMA slices.  Counting only slices made
-  // the first wait of every block (queue: [slice a][slice b][16 stores][slice c], wait for a with vmcnt(2 x 13))
-  // also wait for slice b — one slice of prefetch depth lost per block.  `pre` = slices in the queue older than the
-  // last store burst, `nst` = stores of that burst: the count of operations younger than the oldest slice is
-  // 13 (inflight - 1) + nst while pre > 0, and the burst has retired before any younger slice once pre == 0.
-  // (Counting too FEW younger operations only waits longer; counting too many would read a slice before it landed.)
-  int pre = 0, nst = 0;
-  auto top_up = [&]() {
-    while (pp < p1 && inflight < NBUF) {
-      if (ps == 0) {  // source offsets of block pt of the run: virtual row i -> chunk i / 40, row 5 + i % 40
-        const int last = 40 * prun - 1;
-#pragma unroll
-        for (int n = 0; n < kSliceInstr; ++n) {
-          int i = 32 * pt + srow[n];
-          i = i < last ? i : last;  // rows past the run re-read its last row (excluded by the masks)
-          const int ci = (i * 205) >> 13;
-          vrun[n] = (uint32_t)((ci * 50 + 5 + (i - 40 * ci)) * RB) + scol[n];
-        }
-      }
-      const char* g = dbase + pp * 50 * (int64_t)RB + ps * (kSC * 16);
-      issue_slice<NT>(g, vrun, 0u, false, lds0 + (uint32_t)pbuf * kSliceBytes);
-      pbuf = (pbuf + 1 == NBUF) ? 0 : pbuf + 1;
-      ++inflight;
-      if (++ps == NS) {
-        ps = 0;
-        if (++pt == pn) {
-          pt = 0;
-          pp += prun;
-          if (pp < p1) {
-            prun = run_len(pp);
-            pn = (40 * prun + 31) >> 5;
-          }
-        }
-      }
-    }
-  };
-  top_up();
-
-  bf16x8 qhi[NS][kSplitSteps], qlo[NS][kSplitSteps], qhiL, qloL;
-  float rq = 0.0f;
-  int64_t cur_q = -1;
-  int qlim = Q;  // effective length of the current query (a.qm.len, when the caller resolved the query mask)
-
-  for (int64_t pair = p0; pair < p1;) {
-    const int crun = run_len(pair);
-    const int nb = (40 * crun + 31) >> 5;
-    for (int k = 0; k < crun; ++k) tkl_publish_slot(a, pair + k, 2, lane);  // every pair row of every chunk is written
-    const int slot0 = (int)sload_u32(a.chunk_slot, pair);
-    const int64_t qi = (int64_t)(slot0 / a.C);
-    if (qi != cur_q) {
-      cur_q = qi;
-      const int qr = r < Q ? r : Q - 1;
-      const char* qrow = (const char*)a.q + (qi * Q + qr) * RB;
-      float ss = 0.0f;
-      f32x4 park[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
-      // all 13 NS loads of the tile are in flight together: one memory round trip per query, not NS
-      f32x4 raw[NS][13];
-#pragma unroll
-      for (int s = 0; s < NS; ++s)
-        load_q_slice_split<false>(qrow + s * (kSC * 16) + h * 32, qrow + s * (kSC * 16) + 24 * 16, raw[s]);
-      wait_q_slices<NS>(raw);
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-#pragma unroll
-        for (int p = 0; p < kSplitSteps; ++p) {
-          split8(raw[s][2 * p], raw[s][2 * p + 1], qhi[s][p], qlo[s][p]);
-          qhi[s][p] = to_agpr(qhi[s][p]);
-          qlo[s][p] = to_agpr(qlo[s][p]);
-          ss += sumsq4(raw[s][2 * p]) + sumsq4(raw[s][2 * p + 1]);
-        }
-        if (h == 0) ss += sumsq4(raw[s][12]);
-        if (h == (s >> 1)) park[s & 1] = raw[s][12];
-      }
-      split8(park[0], park[1], qhiL, qloL);
-      qhiL = to_agpr(qhiL);
-      qloL = to_agpr(qloL);
-      ss += __shfl_xor(ss, 32, 64);
-      rq = 1.0f / (sqrtf(ss) + 1e-13f);
-      if (a.qm.len) {
-        const int ql = (int)sload_u32(a.qm.len, qi);
-        qlim = ql < 0 ? 0 : (ql > Q ? Q : ql);
-      }
-    }
-    float* ps_run = a.ps_out + pair * (20 * (int64_t)Q * (K + 1));
-
-    for (int t = 0; t < nb; ++t) {
-      f32x16 acc_hh = {0}, acc_lh = {0}, acc_xl = {0};
-      f32x4 park[2] = {f32x4{0, 0, 0, 0}, f32x4{0, 0, 0, 0}};
-      f32x2 ss2 = {0.0f, 0.0f};
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        top_up();
-        if (pre > 0) {
-          wait_vm(kSliceInstr * (inflight - 1) + nst);
-          --pre;
-        } else {
-          nst = 0;
-          wait_slices(inflight - 1);
-        }
-        const char* buf = smem + cbuf * kSliceBytes;
-        f32x4 x[13];
-#pragma unroll
-        for (int p = 0; p < kSplitSteps; ++p) {
-          x[2 * p] = *(const f32x4*)(buf + a_off + p * 64);
-          x[2 * p + 1] = *(const f32x4*)(buf + a_off + p * 64 + 16);
-        }
-        x[12] = *(const f32x4*)(buf + l_off);
-        __builtin_amdgcn_sched_barrier(0);
-        // as in kernel_pool_split_kernel: the slot goes back before the split / MFMA work — after EVERY slice with the cosine
-        // hand-off, whose epilogue needs no scratch (three slices in flight throughout: 159.8 -> 149.3 us with two of three
-        // slices released early, config 3's full documents)
-        const bool early = COS || s + 1 < NS;
-        if (early) {
-          cbuf = (cbuf + 1 == NBUF) ? 0 : cbuf + 1;
-          --inflight;
-          top_up();
-        }
-        bf16x8 ah, al;
-        split8(x[0], x[1], ah, al);
-#pragma unroll
-        for (int p = 0; p < kSplitSteps; ++p) {
-          bf16x8 nh = ah, nl = al;
-          if (p + 1 < kSplitSteps) split8(x[2 * p + 2], x[2 * p + 3], nh, nl);
-          acc_hh = mfma_bf16(ah, qhi[s][p], acc_hh);
-          acc_lh = mfma_bf16(al, qhi[s][p], acc_lh);
-          acc_xl = mfma_bf16(ah, qlo[s][p], acc_xl);
-          if (MM_TKL_LOLO) acc_xl = mfma_bf16(al, qlo[s][p], acc_xl);
-          {
-            const f32x2 a0 = {x[2 * p][0], x[2 * p][1]}, a1 = {x[2 * p][2], x[2 * p][3]};
-            const f32x2 b0 = {x[2 * p + 1][0], x[2 * p + 1][1]}, b1 = {x[2 * p + 1][2], x[2 * p + 1][3]};
-            ss2 += a0 * a0;
-            ss2 += a1 * a1;
-            ss2 += b0 * b0;
-            ss2 += b1 * b1;
-          }
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, kShadowValu, 0);
-          }
-          ah = nh;
-          al = nl;
-        }
-        const f32x4 xl = x[12];
-        if (h == 0) ss2 += f32x2{xl[0] * xl[0] + xl[1] * xl[1], xl[2] * xl[2] + xl[3] * xl[3]};
-        if (h == (s >> 1)) park[s & 1] = xl;
-        if (!early) {
-          cbuf = (cbuf + 1 == NBUF) ? 0 : cbuf + 1;
-          --inflight;
-        }
-      }
-      {
-        bf16x8 ah, al;
-        split8(park[0], park[1], ah, al);
-        acc_hh = mfma_bf16(ah, qhiL, acc_hh);
-        acc_lh = mfma_bf16(al, qhiL, acc_lh);
-        acc_xl = mfma_bf16(ah, qloL, acc_xl);
-        if (MM_TKL_LOLO) acc_xl = mfma_bf16(al, qloL, acc_xl);
-      }
-      float ss = ss2[0] + ss2[1];
-      f32x16 acc;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[i] = acc_hh[i] + (acc_lh[i] + acc_xl[i]);
-      ss += __shfl_xor(ss, 32, 64);
-      if (h == 0) rdbuf[r] = 1.0f / (sqrtf(ss) + 1e-13f);
-      float rdr[16];
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 v = *(const f32x4*)(rdbuf + 8 * g + 4 * h);
-        rdr[4 * g + 0] = v[0]; rdr[4 * g + 1] = v[1]; rdr[4 * g + 2] = v[2]; rdr[4 * g + 3] = v[3];
-      }
-      // validity bits of virtual rows 32t .. 32t+31: they span at most two chunks of the run
-      const int i0 = 32 * t;
-      const int c0 = (i0 * 205) >> 13, r0 = i0 - 40 * c0;
-      uint32_t va;
-      {
-        const uint32_t w0 = sload_u32(a.dm.bits, (pair + c0) * 2), w1 = sload_u32(a.dm.bits, (pair + c0) * 2 + 1);
-        const unsigned long long b0 = ((unsigned long long)(w1 & 0xffu) << 32) | w0;
-        va = (uint32_t)(b0 >> r0);
-        const int n0 = 40 - r0;  // rows of this block that come from chunk c0 (when < 32)
-        if (n0 < 32 && c0 + 1 < crun) va |= sload_u32(a.dm.bits, (pair + c0 + 1) * 2) << n0;
-      }
-      const int rows_blk = 40 * crun - i0 < 32 ? 40 * crun - i0 : 32;
-      if (rows_blk < 32) va &= (1u << rows_blk) - 1u;
-      if constexpr (COS) {
-        // Cosine rows are indexed by document and position: document b owns cos_out[b * C * 40 * Q ...], and inside it the
-        // row of position n = c * 40 + p (chunk c, centre token p) starts at n * ql with ql = the query's effective
-        // length — only the ql real tokens are stored.  The chunks of a run sit in consecutive slots, so virtual row iv of
-        // the run is position (slot0 % C) * 40 + iv of its document.  Lane (token r, half h) stores its 16 rows directly:
-        // 16 store instructions of <= 2 x ql x 4 B per block.  Measured by removal the stores cost ~20 us of stage 1's 160
-        // on config 3's full documents WHATEVER their shape or cache policy — transposed through LDS into 3 full-width
-        // 16-B stores per block: 160.6 vs 160.5 us; ordinary / nt / sc0 sc1: 257.7 / 259.0 / 260.4 us per call — it is the
-        // write traffic inside the read stream, so fewer bytes is what helps (no columns past ql: 24.5 MB, not 42.6),
-        // and the direct form leaves the ring slot free for an early hand-back.
-        if (r < qlim) {
-          float* dst = a.cos_out + qi * ((int64_t)a.C * 40 * Q) + ((int64_t)(slot0 - (int)qi * a.C) * 40 + 32 * t + 4 * h) * qlim + r;
-          const uint32_t vbits = va >> (4 * h);
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            if (rowof(i) < rows_blk) {  // wave-uniform: rows_blk is a multiple of 8 and rowof(i) + 4h stays in rowof(i)'s group of 8
-              const float c = (acc[i] * rq) * rdr[i];
-              dst[rowof(i) * qlim] = ((vbits >> rowof(i)) & 1u) ? c : 1.0e5f;   // masked: every kernel underflows to exactly 0
-            }
-          }
-        }
-        if (qlim > 0) {
-          nst = rows_blk / 2;
-          pre = inflight;
-        }
-      } else {
-        // staging area: the ring slot this block's last slice just left (free until the next top_up())
-        float* stage = (float*)(smem + (cbuf == 0 ? NBUF - 1 : cbuf - 1) * kSliceBytes);
-        tkl_block_run<K>(ps_run, stage, lane, Q, qlim, t, rows_blk, r, h, acc, rdr, rq, va >> (4 * h), rbf);
-        if (qlim > 0) {
-          const int burst = ((3 * qlim + 63) >> 6) * (rows_blk / 2);      // tkl_block_run: one store per pair row and 64-lane pass
-          nst = burst;
-          pre = inflight;
-        }
-      }
-    }
-    pair += crun;
   }
 }
 
@@ -1248,21 +868,8 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
   }
   // No non-temporal hint on these K-sliced streams: the 400-B row pieces of neighbouring slices share cache
   // lines, and with `nt` the shared lines came from HBM twice (FETCH_SIZE 1.22 x the padded bytes, 1.08 x without).
-  if constexpr (TKL) {  // grouped runs of chunks (tkl_stage1_run_kernel)
-    // the cosine hand-off streams whole rows since round 6 (tkl_stage1_rows.hip).  A/B: MM_TKL_STAGE1_KSPLIT=1 = two K-splitting wavefronts per
-    // workgroup (tkl_stage1_ksplit.hip: correct, not faster), MM_TKL_STAGE1_SLICES=1 = the K-sliced ring of rounds 2-5 below
-    if (a.cos_out && env().tkl_stage1_ksplit && tkl_stage1_ksplit_supported(a.Q, a.E)) return tkl_stage1_ksplit_launch(a, stream);
-    if (a.cos_out && !env().tkl_stage1_slices && tkl_stage1_rows_supported(a.Q, a.E)) return tkl_stage1_rows_launch(a, stream);
-    if (a.cos_out) {
-      return with_ns(a.E, [&](auto ns) {
-        hipLaunchKernelGGL((tkl_stage1_run_kernel<MM_V(ns), K, NBUF, false, true>), grid, block, lds, stream, a);
-        return check_launch("tkl_stage1_run_kernel<cos>");
-      });
-    }
-    return with_ns(a.E, [&](auto ns) {
-      hipLaunchKernelGGL((tkl_stage1_run_kernel<MM_V(ns), K, NBUF, false, false>), grid, block, lds, stream, a);
-      return check_launch("tkl_stage1_run_kernel");
-    });
+  if constexpr (TKL) {  // tkl_stage1_stream comes here for the exact-f32 kernel above only
+    return set_error(MM_ELAUNCH, "tkl: the streaming pair-sum stage 1 is the exact-f32 kernel (MM_KP_F32MFMA=1) only (internal)");
   } else {
     if constexpr (!W) {
       // fewer pairs than half the wavefront slots (eval.py-sized calls): two wavefronts per pair
@@ -1272,15 +879,15 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
         const int lds2 = 2 * (NBUF * kSliceBytes + 128);
         const dim3 grid2((unsigned)a.n_pairs), block2(128);
         return with_ns(a.E, [&](auto ns) {
-          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-          hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, false, 2>), grid2, block2, lds2, stream, b);
+          (void)hipFuncSetAttribute((const void*)kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
+          hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, 2>), grid2, block2, lds2, stream, b);
           return check_launch("kernel_pool_split_kernel<2 wavefronts per pair>");
         });
       }
     }
     if (a.fdm) return set_error(MM_ELAUNCH, "kernel_pool: float masks were left to a kernel that does not read them (internal)");
     return with_ns(a.E, [&](auto ns) {
-      hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, false, W>), grid, block, lds, stream, a);
+      hipLaunchKernelGGL((kernel_pool_split_kernel<MM_V(ns), K, NBUF, false, W>), grid, block, lds, stream, a);
       return check_launch("kernel_pool_split_kernel");
     });
   }
@@ -1288,8 +895,8 @@ static int launch_stream(const KpArgs& a0, hipStream_t stream) {
 
 bool kp_stream_supported(int Q, int E) { return Q <= 32 && kp_stream_width(E); }
 
-// the cosine hand-off exists on the grouped-run kernel only (the exact-f32 A/B kernel and the generic kernel emit pair sums)
-bool tkl_cos_supported(int Q, int E) { return !env().kp_generic && !env().kp_f32mfma && !env().tkl_pairsums && kp_stream_supported(Q, E); }
+// the cosine hand-off exists on the row-streaming kernel only (the exact-f32 A/B kernel and the generic kernel emit pair sums)
+bool tkl_cos_supported(int Q, int E) { return !env().kp_generic && !env().kp_f32mfma && kp_stream_supported(Q, E); }
 
 // TKL stage 1 entry (called from tkl.hip): chunks [P,50,E] -> ps_out [P,20,Q,12]
 int tkl_stage1_stream(const float* q_ctx, const float* chunks, PackedMask dm, const int32_t* q_len,
@@ -1302,7 +909,11 @@ int tkl_stage1_stream(const float* q_ctx, const float* chunks, PackedMask dm, co
   a.n_pairs = P; a.ppq = 1; a.Q = Q; a.D = 40; a.E = E; a.K = 11;
   a.d_doc_rows = 50; a.d_row0 = 5; a.chunk_slot = chunk_slot; a.C = C; a.ps_out = ps_out;
   a.slot2p = slot2p; a.n_slots = n_slots;
-  if (!env().kp_generic && kp_stream_supported(Q, E)) return launch_stream<11, true>(a, stream);
+  if (!env().kp_generic && kp_stream_supported(Q, E)) {
+    // the cosine hand-off streams whole rows (tkl_stage1_rows.hip); pair sums come from the exact-f32 kernel or the generic one
+    if (cos_out && tkl_stage1_rows_supported(Q, E)) return tkl_stage1_rows_launch(a, stream);
+    if (env().kp_f32mfma) return launch_stream<11, true>(a, stream);
+  }
   if (P > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "tkl: too many chunks for one launch");
   hipLaunchKernelGGL((kernel_pool_generic_kernel<11, true>), dim3((unsigned)P), dim3(64), 0, stream, a);
   return check_launch("kernel_pool_generic_kernel<TKL>");

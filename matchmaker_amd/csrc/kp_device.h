@@ -39,7 +39,7 @@ struct KpArgs {
   // (entries of dropped chunks were set to -1 by the preparation launch, earlier in the stream)
   int32_t* slot2p;
   int64_t n_slots;
-  // TKL, cosine hand-off (tkl_stage1_run_kernel<COS>): instead of the pair sums stage 1 stores the scaled, masked
+  // TKL, cosine hand-off (tkl_stage1_rows.hip): instead of the pair sums stage 1 stores the scaled, masked
   // cosines themselves, cos_out[b * C * 40 * Q + (c * 40 + position) * ql + query token] (ql = the query's effective
   // length: only real tokens are stored; masked position: 1e5, which underflows every
   // kernel to exactly 0), and the window kernel evaluates the RBF kernels while it stages its tile — 4 bytes per
@@ -73,29 +73,17 @@ struct KpArgs {
   // (workgroup b runs on XCD b % 8: observed, used for speed only), dispatched together — so the second and third reader of a
   // block find it in that XCD's L2 (a follower cannot overtake the leader without taking over its misses: the three stay
   // together).  m_ranges = pair ranges per combination (the 2-D grid's x extent); block_x = this workgroup's range.
-  // m_flat = 2 (round 5, MM_KP_MULTI_WG=1, A/B only): ONE workgroup per (pair range, document tensor) whose n_mq wavefronts
-  // are the query tensors — each with its own ring and query tile, no shared state — and meet at an s_barrier once per
-  // 32-token block: a rate limiter that keeps the n_mq readers of a block within one block of each other (in the flat order
-  // the three drift apart: FETCH_SIZE 46.9 GB per launch against the 2-D grid's 49.9, 22.9 with the barrier).  Bit-equal, and SLOWER than the flat order (9.19 vs 8.40 ms):
-  // workgroups of three wavefronts fill six of a CU's eight two-per-SIMD slots, and the launch is bound by the RBF
-  // evaluations, not by the bytes the barrier saves.
   int m_flat;
   int m_ranges;
   int block_x;
 };
 
-// wq: this wavefront's index in a workgroup of the m_flat = 2 form (0 otherwise)
-__device__ __forceinline__ KpArgs kp_block_args(const KpArgs& a, int wq = 0) {
+__device__ __forceinline__ KpArgs kp_block_args(const KpArgs& a) {
   KpArgs b = a;
   b.block_x = (int)blockIdx.x;
   if (a.n_md > 0) {
     int y = blockIdx.y;
-    if (a.m_flat == 2) {
-      const int fr = (int)blockIdx.x;                                // flat (pair range, document tensor)
-      const int x = fr / a.n_md, t = fr - x * a.n_md;
-      y = __builtin_amdgcn_readfirstlane(wq * a.n_md + t);
-      b.block_x = __builtin_amdgcn_readfirstlane(x);
-    } else if (a.m_flat) {
+    if (a.m_flat) {
       const int n_mq = a.n_mblk / a.n_md, period = 8 * n_mq;
       const int g = (int)blockIdx.x, blk = g / period, r = g - blk * period;
       const int64_t fr = (int64_t)blk * 8 + (r & 7);                 // flat (pair range, document tensor)
@@ -645,9 +633,6 @@ __device__ __forceinline__ void tkl_publish_slot(const KpArgs& a, int64_t p, int
 // tkl_stage1_rows.hip: TKL stage 1 with the cosine hand-off, whole chunk rows streamed (E = 100 / 200 / 300, Q <= 32)
 bool tkl_stage1_rows_supported(int Q, int E);
 int tkl_stage1_rows_launch(const KpArgs& a, hipStream_t stream);
-// tkl_stage1_ksplit.hip: the same with two wavefronts per workgroup sharing every tile along K (two wavefronts per SIMD)
-bool tkl_stage1_ksplit_supported(int Q, int E);
-int tkl_stage1_ksplit_launch(const KpArgs& a, hipStream_t stream);
 
 // kernel_pool128.hip: streaming kernels for E = 64n <= 384 (Q <= 32)
 bool kp128_supported(int Q, int D, int E, bool gated);

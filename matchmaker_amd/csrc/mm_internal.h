@@ -38,24 +38,16 @@ struct EnvCfg {
   int kp_f32mfma = 0;       // MM_KP_F32MFMA: exact-f32 MFMA pooling kernel instead of split-bf16
   int dot_prof = 0;         // MM_DOT_PROF: in-kernel phase counters of the dot top-k kernel
   int kp_bwd_threads = 1024; // MM_KP_BWD_THREADS: 1024 (when its LDS fits) | 512 threads per pair in kernel_pool_bwd_tiled_kernel (A/B runs)
-  int tkl_stage1_ksplit = 0;  // MM_TKL_STAGE1_KSPLIT=1: TKL stage 1 on the two-wavefront K-split kernel (tkl_stage1_ksplit.hip) instead of the row-streaming one (A/B runs)
-  int tkl_stage1_slices = 0;  // MM_TKL_STAGE1_SLICES=1: TKL stage 1 (cosine hand-off) on the K-sliced ring of rounds 2-5 instead of the row-streaming kernel (A/B runs)
   int kp_bwd_nsplit = 0;    // MM_KP_BWD_NSPLIT=n: workgroups per pair of the split backward (0: by batch size — 4 up to 128 pairs, else 1)
   int kp_bwd_f32 = 0;       // MM_KP_BWD_F32=1: pooling backward on the exact-f32 tiled kernel of rounds 4-5 instead of the split-bf16 streaming kernel (parity twin, A/B runs)
   int kp_bwd_untiled = 0;   // MM_KP_BWD_UNTILED: pooling backward on the per-element kernel of rounds 1-3 (A/B runs)
-  int kp_multi_wg = 0;        // MM_KP_MULTI_WG=1: the multi launch as one workgroup per (pair range, document tensor) with a wavefront per query
-                              // tensor and a rate barrier per block, instead of independent workgroups in flat XCD-grouped order (A/B runs:
-                              // measured SLOWER, 9.19 vs 8.40 ms for Conv-KNRM 3 x 3 — six wavefronts per CU instead of eight)
   int kp_multi_loop = -1;     // MM_KP_MULTI_LOOP: Conv-KNRM's multi launch as one wavefront per (pair range, document tensor) looping over the query
                               // tensors (kernel_pool_multi128_kernel: every document block crosses HBM once, 22.5 GB fetched instead of 47.3).
                               // -1 = by launch size (>= 2,048 pairs), 0 / 1 = never / always (A/B runs)
   int kp_multi_2d = 0;        // MM_KP_MULTI_2D=1: Conv-KNRM's multi launch on the 2-D grid of rounds 1-4 instead of the flat XCD-grouped order (A/B runs)
   int kp128_occ = 0;          // MM_KP128_OCC: 0 = choose by shape, 1 / 2 = wavefronts per SIMD of the 64n-wide pooling kernel (A/B runs)
   int tkl_bwd_nosplit = 0;    // MM_TKL_BWD_NOSPLIT=1: TKL's backward with one workgroup per document at every batch size (A/B runs)
-  int tkl_fold_regions = 0;   // MM_TKL_FOLD_REGIONS=1: TKL's region top-k in the last window workgroup of each document (round 4's default) instead of
-                              // its own launch (A/B runs: the hand-off written to the memory model costs +50 us per 256-document call, see tkl.hip)
   int mp_generic = 0;       // MM_MP_GENERIC=1: MatchPyramid on the generic kernel also at the reference config (bit-equal twin, A/B runs)
-  int tkl_pairsums = 0;     // MM_TKL_PAIRSUMS: TKL stage 1 emits pair sums (round-2 data path) instead of cosines (A/B runs)
 };
 const EnvCfg& env();
 

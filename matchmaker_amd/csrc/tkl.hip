@@ -25,13 +25,7 @@ constexpr int kWThreads = 256;
 #define MM_TKL_TOK_GROUP 10     // -D overrides for A/B builds only (profiles/r06_experiments/tkl_window_token_groups.txt)
 #endif
 constexpr int kTokGroup = MM_TKL_TOK_GROUP;  // query tokens per window workgroup (see tkl_window_kernel)
-#ifndef MM_TKL_EPILOGUE_ORDER
-#define MM_TKL_EPILOGUE_ORDER 1   // 0: round 4 (relaxed counter + s_waitcnt), 1: acq_rel counter by thread 0, 2: fences in every thread
-#endif
 constexpr int kRThreads = 256;  // region kernel (1,024 threads, one window each, measured slower: 11.3 vs 9.8-10.5 us)
-
-__device__ __forceinline__ void region_topk(float* orig, float* work, float* rv, int* ri, int Wp, const float* __restrict__ prm,
-                                            float* __restrict__ out, int32_t* __restrict__ peaks, int tid);   // (defined below the window kernel)
 
 
 // Preparation in ONE launch (round 1: memset + emb + two mask packs + slot map = five, ~25 us of a 0.3 ms call) —
@@ -53,19 +47,15 @@ __global__ void __launch_bounds__(256) tkl_prep_kernel(int32_t* __restrict__ slo
                                                        int32_t* __restrict__ qlen_out, uint32_t* __restrict__ qbits_out,
                                                        const float* __restrict__ chunk_mask, int64_t P,
                                                        int32_t* __restrict__ clen_out, uint32_t* __restrict__ cbits_out,
-                                                       const int32_t* __restrict__ chunk_slot, int C, int32_t* __restrict__ ntile,
-                                                       int32_t* __restrict__ done_cnt) {
+                                                       const int32_t* __restrict__ chunk_slot, int C, int32_t* __restrict__ ntile) {
   const int lane = threadIdx.x & 63;
   int blk = blockIdx.x;
   if (blk < n_fill) {
     const int64_t i = (int64_t)blk * 256 + threadIdx.x;
     if (i < BC) slot2p[i] = -1;
-    // Per document (the first B threads of this role): the arrival counter of the window kernel's last-workgroup epilogue; the
-    // live window tiles come from the chunk role below (without packed chunks: 0 for every document, here).
-    if (i < B) {
-      done_cnt[i] = 0;
-      if (P == 0) ntile[i] = 0;
-    }
+    // Per document (the first B threads of this role): the live window tiles come from the chunk role below (without packed
+    // chunks: 0 for every document, here).
+    if (i < B && P == 0) ntile[i] = 0;
     return;
   }
   blk -= n_fill;
@@ -242,7 +232,7 @@ constexpr int kWindowLds = MM_WIN_LDS;     // four workgroups per CU (a 64-windo
 // fits the workgroup's LDS at the document's effective query length.
 // COS: `ps` holds stage 1's scaled, masked cosines (KpArgs::cos_out: per document, rows of ql real tokens) and the pair
 // rows of the tile are EVALUATED here while they are staged (RBF kernels of the two positions of a pair + the
-// non-zero count, the arithmetic of kernel_pool.hip's tkl_block_run), instead of being read back from a 6x larger
+// non-zero count, the arithmetic of kernel_pool.hip's tkl_block), instead of being read back from a 6x larger
 // pair-sum buffer.
 template <int SAT, bool COS>
 __global__ void __launch_bounds__(kWThreads, 4) tkl_window_kernel(const float* __restrict__ ps, const int32_t* __restrict__ slot2p,
@@ -250,98 +240,15 @@ __global__ void __launch_bounds__(kWThreads, 4) tkl_window_kernel(const float* _
                                                          const float* __restrict__ q_mask,
                                                          const int32_t* __restrict__ q_len,
                                                          const float* __restrict__ prm, float* win,
-                                                         int C, int Q, int W, int lds_bytes, const int32_t* __restrict__ ntile,
-                                                         int n_planes, float* win_final, float* __restrict__ out,
-                                                         int32_t* __restrict__ done_cnt, int32_t* __restrict__ peaks) {
+                                                         int C, int Q, int W, int lds_bytes, const int32_t* __restrict__ ntile) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  __shared__ float rv[kRThreads / 64];
-  __shared__ int ri[kRThreads / 64];
-  __shared__ int last_flag;
   const int b = blockIdx.y;
   const int w0 = blockIdx.x * kWT;
   const int tid = threadIdx.x;
-  // ---- last-workgroup epilogue (MM_TKL_FOLD_REGIONS=1 only; round 4's default: the region top-k of :254-286 without its own launch) ----
-  // The "last block" reduction pattern, written to the HIP memory model (round 5; round 4 relied on gfx950's sc1 write-through
-  // behaviour alone).  Every workgroup that scores a live tile of document b
-  //   1. publishes its 64 partial window scores (agent-scope atomic stores: sc1 write-through),
-  //   2. meets at the workgroup barrier (workgroup-scope release / acquire between its threads),
-  //   3. thread 0 arrives on done_cnt[b] with an ACQ_REL agent-scope fetch_add: the release half (buffer_wbl2 sc1 + s_waitcnt)
-  //      covers the whole workgroup's scores through the barrier (happens-before is transitive across scopes).
-  // The workgroup whose arrival completes the document (old + 1 == expected) has, through thread 0's acquire half
-  // (buffer_inv sc1) and the second barrier, every other workgroup's scores ordered before its own loads (which are agent-scope
-  // atomic loads besides: no stale line of another XCD's L2), sums the planes and runs the region search in the LDS its tile
-  // just left.  (A release fence in EVERY thread, round 5's first form, cost +0.19 ms per 256-document call — a buffer_wbl2
-  // from every wavefront; MM_TKL_EPILOGUE_ORDER=2 keeps it for A/B.)  expected = live tiles x live token groups
-  // of the document — dead tiles (past the last kept chunk, tkl_prep_kernel) and groups without a real token neither write
-  // nor arrive.  out == nullptr (the DEFAULT since round 5, see mm_tkl_fwd_peaks): the standalone tkl_region_kernel follows and this kernel only
-  // publishes.  win / win_final are NOT __restrict__: with one token group (Q <= 10) they are the same buffer (each thread
-  // reads and writes only its own windows there).
-  const float* const part = win;
-  const int64_t plane_stride = (int64_t)gridDim.y * W;
+  // This kernel only publishes its (plane of) window scores; the region top-k of :254-286 is the launch behind it
+  // (tkl_region_kernel, see mm_tkl_fwd_peaks for the in-launch form that was retired).  Dead tiles (past the document's last
+  // kept chunk, tkl_prep_kernel) and token groups without a real token write nothing.
   const int nt_live = ntile[b] < (int)gridDim.x ? ntile[b] : (int)gridDim.x;
-  int np_live = n_planes;
-  {
-    int qa = q_len ? q_len[b] : Q;
-    qa = qa < 0 ? 0 : (qa > Q ? Q : qa);
-    const int npq = (qa + kTokGroup - 1) / kTokGroup;
-    np_live = npq < n_planes ? npq : n_planes;
-  }
-  const int expected = nt_live * np_live;
-  auto finalize = [&]() {
-    const int Wp = W < 3 ? 3 : W;
-    float* orig = (float*)smem;
-    float* work = orig + Wp;
-    const int live_w = nt_live * kWT;
-    for (int w = tid; w < Wp; w += kWThreads) {
-      float s = 0.0f;
-      if (w < W) {
-        if (w < live_w)
-          for (int g = 0; g < np_live; ++g)
-            s += __hip_atomic_load(part + g * plane_stride + (int64_t)b * W + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        win_final[(int64_t)b * W + w] = s;
-      }
-      if (s == 0.0f) s = -9900.0f;                                     // :257
-      orig[w] = s;
-      work[w] = s;
-    }
-    __syncthreads();
-    region_topk(orig, work, rv, ri, Wp, prm, out + b, peaks ? peaks + 3 * (int64_t)b : nullptr, tid);
-  };
-  auto arrive = [&]() {
-    if (!out) return;
-#if MM_TKL_EPILOGUE_ORDER == 2
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");                 // (A/B: a release fence in EVERY thread: +0.19 ms at 256 documents)
-#elif MM_TKL_EPILOGUE_ORDER == 0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                   // (A/B: round 4's hardware-level ordering, not the memory model's)
-#endif
-    __syncthreads();   // workgroup-scope release / acquire: every thread's published scores happen-before thread 0's RMW below
-    if (tid == 0) {
-#if MM_TKL_EPILOGUE_ORDER == 0
-      const int old = __hip_atomic_fetch_add(done_cnt + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-      // ACQ_REL at agent scope: release = the workgroup's scores (cumulative over the barrier) are visible device-wide before
-      // the count; acquire = the finalizer sees the scores of every workgroup that counted before it
-      const int old = __hip_atomic_fetch_add(done_cnt + b, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-      last_flag = old + 1 == expected;
-    }
-    __syncthreads();   // ... and thread 0's acquire happens-before every thread's loads in finalize()
-    if (last_flag) {
-#if MM_TKL_EPILOGUE_ORDER == 2
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-#endif
-      finalize();
-    }
-  };
-  if (out && expected == 0) {            // no live tile or no real query token: every window is empty, the score is 0 (:257, :282)
-    if (blockIdx.x == 0 && blockIdx.z == 0) {
-      for (int w = tid; w < W; w += kWThreads) win_final[(int64_t)b * W + w] = 0.0f;
-      if (tid == 0) out[b] = 0.0f;
-      // every window is -9900: the arg-max rounds pick 0, then the first index outside +-15 of it, and so on (:268-273)
-      if (peaks && tid < 3) { const int Wp = W < 3 ? 3 : W; peaks[3 * (int64_t)b + tid] = 15 * tid < Wp ? 15 * tid : 0; }
-    }
-    return;
-  }
   // Token groups: workgroup z evaluates query tokens [kTokGroup z, kTokGroup (z + 1)) of its 64 windows and writes a partial
   // window score (summed over ITS tokens) to plane z of `win`; the region kernel adds the planes in order.  A tile of
   // 10 tokens is 37 KiB of LDS instead of 75: FOUR independent 256-thread workgroups per CU instead of two of 512 —
@@ -413,7 +320,6 @@ __global__ void __launch_bounds__(kWThreads, 4) tkl_window_kernel(const float* _
     if (!live) {                                       // (a hole: below the last kept chunk, so it is counted as a live tile)
       if (tid < kWT && w0 + tid < W)
         __hip_atomic_store(win + (int64_t)b * W + w0 + tid, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      arrive();
       return;
     }
   }
@@ -555,7 +461,6 @@ __global__ void __launch_bounds__(kWThreads, 4) tkl_window_kernel(const float* _
     }
     // the next pass overwrites `tile` (last read before the barrier above) and, after its own barrier, `red`
   }
-  arrive();
 }
 
 // Region top-k over the window scores of ONE document (:254-286) by the 256 threads of a workgroup: orig / work [Wp] in LDS
@@ -614,8 +519,8 @@ __device__ __forceinline__ void region_topk(float* orig, float* work, float* rv,
   }
 }
 
-// One 256-thread workgroup per document: the default form (round 4 let the LAST window workgroup of a document do this itself,
-// see tkl_window_kernel: MM_TKL_FOLD_REGIONS=1 for A/B runs).  (One wavefront per document spent 16 us on sixteen
+// One 256-thread workgroup per document (round 4 let the LAST window workgroup of a document do this itself: retired, see
+// mm_tkl_fwd_peaks).  (One wavefront per document spent 16 us on sixteen
 // dependent 4-byte loads per lane; four wavefronts load the ~1,000 scores of a 2,048-token document in four rounds.)
 __global__ void __launch_bounds__(kRThreads) tkl_region_kernel(const float* part, int n_planes, int64_t plane,
                                                          const int32_t* __restrict__ q_len, float* win,
@@ -690,8 +595,7 @@ extern "C" size_t mm_tkl_workspace_bytes(int64_t B, int64_t P, int C, int Q, int
          packed_mask_bytes(MM_MASK_F32, P, 40) + align256((size_t)B * W * 4) + align256((size_t)B * Q * 4) +
          packed_mask_bytes(MM_MASK_F32, B, Q) +  // + the packed query mask (effective lengths)
          align256((size_t)((Q + kTokGroup - 1) / kTokGroup) * B * W * 4) +  // + the token groups' partial window scores
-         align256((size_t)B * 4) +                                         // + live window tiles per document
-         align256((size_t)B * 4);                                          // + arrival counters of the last-workgroup epilogue
+         align256((size_t)B * 4);                                          // + live window tiles per document
 }
 
 extern "C" int mm_tkl_fwd(const void* q_ctx, const void* chunks, const float* chunk_mask, const int32_t* chunk_slot,
@@ -737,9 +641,7 @@ extern "C" int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const flo
   PackedMask qmk, dm;
   float* planes = nullptr;                              // [n_planes][B][W] partial window scores of the token groups
   int32_t* ntile = nullptr;                             // [B] live window tiles per document (tkl_prep_kernel)
-  int32_t* done_cnt = nullptr;                          // [B] window workgroups of the document that have published their scores
   const int n_planes = (Q + kTokGroup - 1) / kTokGroup;
-  bool fold_regions = false;
   {
     if (P >= (1LL << 29)) return set_error(MM_EUNSUPPORTED, "tkl: too many packed chunks for one launch");
     const size_t need_dm = packed_mask_bytes(MM_MASK_F32, P, 40);
@@ -749,7 +651,6 @@ extern "C" int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const flo
     char* qws = (char*)emb + align256((size_t)B * Q * 4);
     planes = (float*)(qws + packed_mask_bytes(MM_MASK_F32, B, Q));
     ntile = (int32_t*)((char*)planes + align256((size_t)n_planes * B * W * 4));
-    done_cnt = (int32_t*)((char*)ntile + align256((size_t)B * 4));
     int32_t* qlen = (int32_t*)qws;
     uint32_t* qbits = (uint32_t*)(qws + (size_t)B * 4);
     const int n_fill = (int)((B * (int64_t)C + 255) / 256);
@@ -758,7 +659,7 @@ extern "C" int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const flo
     const int n_chunk = (int)((P + 3) / 4);
     hipLaunchKernelGGL(tkl_prep_kernel, dim3((unsigned)(n_fill + n_emb + n_q + n_chunk)), dim3(256), 0, stream, slot2p,
                        B * (int64_t)C, n_fill, (const float*)q_ctx, params, emb, B * (int64_t)Q, E, n_emb, q_mask, B, Q, n_q,
-                       qlen, qbits, chunk_mask, P, clen, cbits, chunk_slot, C, ntile, done_cnt);
+                       qlen, qbits, chunk_mask, P, clen, cbits, chunk_slot, C, ntile);
     if (int e = check_launch("tkl_prep_kernel")) return e;
     qmk.len = qlen;
     qmk.bits = qbits;
@@ -784,22 +685,20 @@ extern "C" int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const flo
     if (n_planes > 65535 || B > 65535) return set_error(MM_EUNSUPPORTED, "tkl: grid limits (B=%lld, Q=%d)", (long long)B, Q);
     const dim3 grid2((unsigned)((W + kWT - 1) / kWT), (unsigned)B, (unsigned)n_planes);
     float* wdst = n_planes > 1 ? planes : win;                         // one group: its plane IS the window-score output
-    // The region top-k is its own launch (tkl_region_kernel) again since round 5.  Round 4 folded it into the last window
-    // workgroup of each document (MM_TKL_FOLD_REGIONS=1 still does, when the tile's LDS holds the two score rows).  Measured on
-    // one box, 256 documents, round-robin (profiles/r05_experiments/tkl_epilogue_orderings.txt):
+    // The region top-k is its own launch (tkl_region_kernel).  Round 4 folded it into the last window workgroup of each
+    // document (arrival counter + last-workgroup finalizer; retired, last present in 51a08f0).  Measured on one box,
+    // 256 documents, round-robin (profiles/r05_experiments/tkl_epilogue_orderings.txt):
     //     standalone launch                                   0.1388 / 0.1396 ms
     //     folded, round 4's relaxed counter + s_waitcnt       0.1413 / 0.1418     (correct on gfx950's sc1 path, not by the HIP model)
-    //     folded, acq_rel arrival by thread 0 (the default of the folded form: correct by the model)   0.1927 / 0.1914
+    //     folded, acq_rel arrival by thread 0 (correct by the model)   0.1927 / 0.1914
     //     folded, release / acquire fences in every thread    0.3367 / 0.3359
     // A kernel boundary is the cheapest agent-scope release there is: the buffer_wbl2 an in-launch release needs costs more per
     // workgroup (~1.7 us, MI355X_MICROARCH.md) than the 9.7 us launch it was meant to save, and even the unordered form was not
     // faster than the launch.
-    fold_regions = env().tkl_fold_regions && (size_t)(W < 3 ? 3 : W) * 8 <= lds2;
     auto launch = [&](auto kern) {
       if (lds2 > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
       hipLaunchKernelGGL(kern, grid2, dim3(kWThreads), lds2, stream, (const float*)ps, (const int32_t*)slot2p, (const float*)emb, q_mask,
-                         (const int32_t*)qmk.len, params, wdst, C, Q, W, (int)lds2, (const int32_t*)ntile, n_planes, win,
-                         fold_regions ? out : (float*)nullptr, done_cnt, top_idx);
+                         (const int32_t*)qmk.len, params, wdst, C, Q, W, (int)lds2, (const int32_t*)ntile);
     };
     if (saturation == MM_TKL_SAT_EMBEDDING) {
       if (use_cos) launch(tkl_window_kernel<MM_TKL_SAT_EMBEDDING, true>);
@@ -810,7 +709,6 @@ extern "C" int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const flo
     }
     if (int e = check_launch("tkl_window_kernel")) return e;
   }
-  if (fold_regions) return MM_OK;
   const int Wp = W < 3 ? 3 : W;
   hipLaunchKernelGGL(tkl_region_kernel, dim3((unsigned)B), dim3(kRThreads), (size_t)Wp * 8, stream,
                      (const float*)(n_planes > 1 ? planes : win), n_planes, (int64_t)B * W, (const int32_t*)qmk.len, win, params, out, W,

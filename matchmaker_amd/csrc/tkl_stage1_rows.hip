@@ -1,9 +1,10 @@
 // TKL stage 1, row-streaming form (round 6): the cosine match of sigir20_tkl.py:184-194 for the cosine hand-off to the window
-// kernel (KpArgs::cos_out, tkl.hip) — what tkl_stage1_run_kernel<COS> of kernel_pool.hip computes, with another HBM stream.
+// kernel (KpArgs::cos_out, tkl.hip) — what the K-sliced ring kernel of rounds 2-5 (retired; last present in 51a08f0) computed, with
+// another HBM stream.
 //
-// tkl_stage1_run_kernel cuts the 1,200-byte rows of a chunk (E = 300) into three 400-byte K-slices so that a ring slot can go
-// back to its producer after a third of a block: every LDS-DMA instruction then gathers 2.56 row PIECES (13 cache lines for
-// 1,024 bytes, neighbouring slices sharing lines), the three pieces of a row are requested a slice period apart, and stage 1
+// That kernel cut the 1,200-byte rows of a chunk (E = 300) into three 400-byte K-slices so that a ring slot could go
+// back to its producer after a third of a block: every LDS-DMA instruction then gathered 2.56 row PIECES (13 cache lines for
+// 1,024 bytes, neighbouring slices sharing lines), the three pieces of a row were requested a slice period apart, and stage 1
 // streamed 4.7 TB/s.  Here the 40 centre rows of a chunk — ONE contiguous 48,000-byte run — are streamed as
 // such: five units of 8 rows (9,600 B = 9 full LDS-DMA instructions + one of 24 lanes), each a linear image of global memory in
 // its ring slot.  A row is whole in LDS when its unit lands, so the matrix products run over M = 16 document rows at full K

@@ -518,7 +518,7 @@ def test_shared_ring_all_pairs_work_map_covers_every_pair_once(Bq, Bd, NQT):
 
 
 def test_store_burst_accounting_never_overcounts():
-    """Model of the vmcnt bookkeeping of tkl_stage1_run_kernel / maxsim_allpairs_wg_kernel: a wavefront's loads (slices of
+    """Model of the vmcnt bookkeeping of maxsim_allpairs_wg_kernel: a wavefront's loads (slices of
     `per` instructions) and its bursts of stores retire in issue order; the wait for the oldest slice is
     vmcnt(per * (inflight - 1) + nst) while `pre` > 0, else vmcnt(per * (inflight - 1)).  The value must never EXCEED the
     true number of younger operations (that would read a slice before it landed) and should equal it whenever at most one

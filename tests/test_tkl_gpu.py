@@ -70,7 +70,9 @@ def test_tkl_matches_reference_golden(fname):
 
 @pytest.mark.parametrize("B,Q,D,E,sat", [(3, 20, 500, 300, "embedding"), (2, 30, 2048, 300, "log"),
                                           (4, 12, 130, 100, "embedding"), (2, 20, 90, 200, "embedding"),
-                                          (3, 7, 41, 64, "log"), (2, 40, 300, 32, "embedding")])
+                                          (3, 7, 41, 64, "log"), (2, 40, 300, 32, "embedding"),
+                                          # one token group at E = 300, log saturation at E = 200, short documents on the generic fallback
+                                          (2, 7, 700, 300, "embedding"), (2, 20, 500, 200, "log"), (3, 20, 90, 128, "embedding")])
 def test_tkl_random_vs_oracle(B, Q, D, E, sat):
     dev = util.require_gpu()
     gen = torch.Generator().manual_seed(B * 1000 + D)
@@ -155,6 +157,13 @@ def test_tkl_config3_scale_properties():
     # region-tied document: asserting 1e-3 on every score, as rounds 1-4 did, is a coin with a 1-in-20 red side)
     util.tkl_check_documents(s1.cpu().numpy(), w1.cpu().numpy(), p1.cpu().numpy(), np.concatenate(sc), np.concatenate(wn),
                              m.chunk_scoring.detach().cpu().numpy().reshape(-1), label="config 3")
+    # config 3 at 1,024 documents: every score finite, and the first two region peaks of every document differ
+    del q, d, chunks
+    torch.cuda.empty_cache()
+    q_ctx, chunks, cmask, slot, qm, params, B, C, sat = _epilogue_inputs(dev, 1024, 20, 2048, 300, "embedding", 11)
+    s, _, pk = ops.tkl_score(q_ctx, chunks, cmask, slot, qm, params, B, C, 11, sat, return_windows=True, return_peaks=True)
+    assert s.shape == (1024,) and torch.isfinite(s).all()
+    assert (pk[:, 0] != pk[:, 1]).all()
 
 
 
@@ -507,22 +516,6 @@ print("ACCEPTED")
     assert "ACCEPTED" not in r.stdout
 
 
-# ---- the region search: standalone launch (default since round 5) vs the folded epilogue (MM_TKL_FOLD_REGIONS=1: the last window
-# workgroup of a document runs it).  The folded form is a cross-workgroup, cross-XCD hand-off through HBM: publish (agent-scope
-# stores) -> workgroup barrier -> acq_rel arrival counter by thread 0 -> barrier -> sum the planes.  A missing ordering or a stale
-# cached line would show as a score / window / peak that differs from the standalone tkl_region_kernel (a kernel boundary instead
-# of the hand-off), that changes between repeated calls, or that carries a value left in the workspace by the previous call.
-
-def _epilogue_cases(dev):
-    """(label, B, Q, D, E, sat, seed): config 3 at 1,024 documents; Q <= 10 (ONE token group: the window output buffer is
-    also the plane the finalizer reads — win == win_final inside the kernel); Q = 30 (three groups); short documents; E = 100 / 200."""
-    return [("config3_1024", 1024, 20, 2048, 300, "embedding", 11), ("one_group_q7", 96, 7, 2048, 300, "embedding", 12),
-            ("one_group_q10_log", 64, 10, 700, 64, "log", 13), ("three_groups_q30", 64, 30, 2048, 300, "embedding", 14),
-            ("short_docs", 200, 20, 90, 128, "embedding", 15),
-            # the other two widths of the streaming stage-1 kernels (4 and 7 k-steps of 32; uneven K halves in the K-split twin)
-            ("e100_q12", 40, 12, 700, 100, "embedding", 16), ("e200_q20_log", 32, 20, 500, 200, "log", 17)]
-
-
 def _epilogue_inputs(dev, B, Q, D, E, sat, seed):
     from matchmaker_amd.tkl import chunk_documents
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -536,68 +529,6 @@ def _epilogue_inputs(dev, B, Q, D, E, sat, seed):
     q_ctx = q * qm.unsqueeze(-1)
     chunks, cmask, slot, C = chunk_documents(d * dm.unsqueeze(-1), dm)
     return q_ctx, chunks, cmask, slot, qm, m.pack_params(), B, C, sat
-
-
-def _epilogue_run_all(path=None):
-    """scores / windows / peaks of every case; `path`: save them (the child process under MM_TKL_FOLD_REGIONS=1)."""
-    from matchmaker_amd import ops
-    dev = util.require_gpu()
-    out = {}
-    for label, B, Q, D, E, sat, seed in _epilogue_cases(dev):
-        q_ctx, chunks, cmask, slot, qm, params, B, C, sat = _epilogue_inputs(dev, B, Q, D, E, sat, seed)
-        s, w, p = ops.tkl_score(q_ctx, chunks, cmask, slot, qm, params, B, C, 11, sat, return_windows=True, return_peaks=True)
-        out[label + ".score"], out[label + ".win"], out[label + ".peaks"] = s.cpu().numpy(), w.cpu().numpy(), p.cpu().numpy()
-        del q_ctx, chunks
-        torch.cuda.empty_cache()
-    if path:
-        np.savez(path, **out)
-    return out
-
-
-def test_folded_region_epilogue_is_bit_equal_to_the_standalone_region_kernel(tmp_path):
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "standalone.npz")
-    r = subprocess.run([sys.executable, "-c", f"from tests.test_tkl_gpu import _epilogue_run_all; _epilogue_run_all({path!r})"], cwd=root,
-                       env=dict(os.environ, MM_TKL_FOLD_REGIONS="1"), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert not os.environ.get("MM_TKL_FOLD_REGIONS"), "this process must run the default (standalone region kernel) path"
-    folded = np.load(path)
-    alone = _epilogue_run_all()
-    assert set(folded.files) == set(alone)
-    for k in sorted(alone):
-        assert folded[k].shape == alone[k].shape and folded[k].tobytes() == alone[k].tobytes(), f"{k}: folded epilogue != standalone region kernel"
-    assert alone["config3_1024.score"].shape == (1024,) and np.isfinite(alone["config3_1024.score"]).all()
-    assert (alone["config3_1024.peaks"][:, 0] != alone["config3_1024.peaks"][:, 1]).all()
-
-
-@pytest.mark.parametrize("switch", ["MM_TKL_STAGE1_SLICES", "MM_TKL_STAGE1_KSPLIT"])
-def test_stage1_kernels_agree_with_the_row_streaming_default(tmp_path, switch):
-    """Stage 1 ships as tkl_stage1_rows.hip (whole chunk rows through the LDS ring, round 6).  Its two A/B twins — the K-sliced ring
-    of rounds 2-5 (MM_TKL_STAGE1_SLICES=1) and the two-wavefront K-split kernel (MM_TKL_STAGE1_KSPLIT=1) — compute the same split-bf16
-    cosines in another summation order: every window of the five epilogue cases (config 3 at 1,024 documents, one / three token
-    groups, log saturation at E = 64 -> generic fallback, short documents) within 4e-5 of the default's, the document scores
-    within 1e-3 except where a region arg-max sits on a tie (at most 1 %; tests/util.py states the tie policy)."""
-    import os, subprocess, sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    path = str(tmp_path / "twin.npz")
-    r = subprocess.run([sys.executable, "-c", f"from tests.test_tkl_gpu import _epilogue_run_all; _epilogue_run_all({path!r})"], cwd=root,
-                       env=dict(os.environ, **{switch: "1"}), capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-3000:]
-    assert not os.environ.get(switch), "this process must run the default stage 1"
-    twin = np.load(path)
-    ours = _epilogue_run_all()
-    assert set(twin.files) == set(ours)
-    for k in sorted(ours):
-        if k.endswith(".win"):
-            a, b = ours[k].astype(np.float64), twin[k].astype(np.float64)
-            assert np.isfinite(a).all() and np.isfinite(b).all()
-            err = np.abs(a - b) / np.maximum(1.0, np.abs(a))
-            assert err.max() <= 4e-5, f"{k}: windows differ by {err.max():.2e}"
-        elif k.endswith(".score"):
-            a, b = ours[k].astype(np.float64), twin[k].astype(np.float64)
-            off = np.abs(a - b) > 1e-3 * np.maximum(1.0, np.abs(a))
-            assert off.mean() <= 0.01, f"{k}: {int(off.sum())} of {off.size} document scores differ (region ties are rarer than that)"
 
 
 def test_scores_do_not_depend_on_the_batch_and_wavefronts_with_more_than_64_chunks_reload_their_metadata():
@@ -675,15 +606,8 @@ def _stability_run():
 
 
 def test_tkl_forward_is_stable_under_repetition_concurrency_and_a_poisoned_workspace():
-    """Run for the default path (standalone region kernel) in this process and for the folded epilogue (MM_TKL_FOLD_REGIONS=1: the
-    cross-workgroup hand-off, where a missing ordering would show exactly here) in a child process.
-    200 calls of mm_tkl_fwd_peaks on ONE input through the C ABI with a caller-owned workspace that is filled with NaN
-    bit patterns (0xFF) before every call — a plane, counter or slot-map entry read before this call wrote it shows up as a
+    """200 calls of mm_tkl_fwd_peaks on ONE input through the C ABI with a caller-owned workspace that is filled with NaN
+    bit patterns (0xFF) before every call — a plane or slot-map entry read before this call wrote it shows up as a
     NaN or a changed bit — while a second stream keeps the headline MaxSim kernel running on all CUs (the window workgroups'
     placement over the XCDs and their arrival order change from call to call)."""
-    import os, subprocess, sys
     assert _stability_run()
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", "from tests.test_tkl_gpu import _stability_run; print('STABLE', _stability_run())"], cwd=root,
-                       env=dict(os.environ, MM_TKL_FOLD_REGIONS="1"), capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "STABLE True" in r.stdout, (r.stdout[-500:], r.stderr[-3000:])

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Same-box A/B of per-kernel times (rocprofv3 --kernel-trace --stats), round-robin, two passes:
 #   bash tools/ab_kernels.sh <kernel grep> <leg> <tag>:<ENV=V,...> [<tag>:<...> ...]     (environment switches; "lib=<path>" selects MM_NATIVE_LIB)
-#   e.g. bash tools/ab_kernels.sh stage1 tkl rows: slices:MM_TKL_STAGE1_SLICES=1
+#   e.g. bash tools/ab_kernels.sh stage1 tkl rows: parent:lib=variants/libmm_native_parent.so
 pat=$1; leg=$2; shift 2
 for rnd in 1 2; do
   for spec in "$@"; do

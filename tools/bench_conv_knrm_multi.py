@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Conv-KNRM's 3 x 3 multi launch alone (bench.py extra.variants' shape: 64 x 1000 pairs, Q30 / D200 / E128), for counter passes:
     rocprofv3 --pmc FETCH_SIZE --kernel-trace -d out -o c -- python tools/bench_conv_knrm_multi.py [steps]
-    MM_KP_MULTI_2D=1 MM_KP128_OCC=1 ... (rounds 1-4's 2-D grid)   |   MM_KP_MULTI_WG=1 ... (wavefront per query tensor)"""
+    MM_KP_MULTI_2D=1 MM_KP128_OCC=1 ... (rounds 1-4's 2-D grid)   |   MM_KP_MULTI_LOOP=0 ... (flat XCD-grouped order)"""
 import os
 import sys
 
