@@ -958,6 +958,77 @@ int mm_store_append(const void* x, int n_docs, int D, int E, int dtype, int flag
                     int64_t* fill, int64_t* doc_begin, int64_t* doc_end, int32_t* status,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ranking and IR metrics: scores on the device -> rank order -> the per-query quantities of the reference's metric
+ * dicts (additive: MM_ABI_VERSION unchanged).  None of the three entries needs a workspace, so there is no size query.
+ * All run on `stream` with no allocation, no read-back and no atomics: graph-capturable, two calls give the same bits.
+ *
+ * Segments: seg_begin [nq + 1] int64, ascending, DEVICE memory; query s owns rows [seg_begin[s], seg_begin[s + 1]).
+ * Every bound is clamped into [0, n_rows] on the device, so no load or store uses a row outside [0, n_rows) whatever
+ * seg_begin (or, for the metric entries, `order`) holds.  Empty segments are legal anywhere.  n_rows < 2^31.
+ *
+ * mm_segment_rank_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/utils/core_metrics.py:502-511 (unrolled_to_ranked_result: `sorted(..., key=score, reverse=True)`
+ *           per query), as called from eval.py:264-320, 395-407 and dense_retrieval.py:447-448.
+ *   scores [n_rows] of `dtype` (MM_F32 / MM_F16 / MM_BF16; 16-bit scores are widened exactly to fp32 before comparison).
+ *   order [n_rows] int32: order[seg_begin[s] + r] = the global row with rank r + 1 in query s.
+ *   Rule: higher score first; equal scores keep arrival order (the sort is stable); -0.0 == +0.0.  STATED CHOICE: every
+ *   NaN ranks after everything else, -inf included, NaNs among themselves in arrival order (Python's sorted() gives an
+ *   order that depends on the arrival positions there; the reference never scores NaN on purpose).
+ *   max_len: the caller's upper bound on the segment lengths, 0 .. MM_RANK_MAX_LEN.  max_len > MM_RANK_MAX_LEN returns
+ *   MM_EUNSUPPORTED before any launch (8,192 rows: 64 KiB of 64-bit keys in LDS, two workgroups per CU beside it).  A
+ *   segment that is longer than max_len all the same is written in arrival order.
+ *   Segments of <= 64 rows take one wavefront each (four per workgroup), longer ones one workgroup each.
+ *   nq = 0 or n_rows = 0 succeeds and writes nothing.
+ */
+#define MM_RANK_MAX_LEN 8192
+#define MM_RANK_MAX_CUTOFFS 8
+#define MM_RANK_NOT_JUDGED (-2147483647 - 1)   /* grade of a row whose document is not in the query's qrels (INT32_MIN) */
+
+int mm_segment_rank_fwd(const void* scores, int dtype, const int64_t* seg_begin, int64_t n_rows, int nq, int max_len,
+                        int32_t* order, void* stream);
+
+/* mm_rank_metrics_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: the per-query body of calculate_metrics_plain (core_metrics.py:380-461; threshold = INT32_MAX, cand_pos =
+ *           NULL) and of calculate_metrics_single_candidate_threshold (:228-327; cand_pos + threshold).
+ *   Per row (DEVICE): order [n_rows] int32 (mm_segment_rank_fwd's); grade [n_rows] int32 = the qrels grade of the row's
+ *   document for its query, MM_RANK_NOT_JUDGED when it is not in the query's qrels; cand_pos [n_rows] int32 or NULL = the
+ *   1-based first-stage rank.  Rows with cand_pos > threshold are dropped and the rest renumbered 1, 2, ... (merged_ranks,
+ *   :252-254).  A row is binary-relevant when it is judged and grade >= binarization_point.
+ *   Cutoffs (HOST arrays, read before the launch): mrr_cutoffs [n_mrr], ndcg_cutoffs [n_ndcg], each 0 .. 8 entries >= 1;
+ *   map_cutoff >= 1.
+ *   Per query (DEVICE, computed from the qrels alone): binary_num_relevant [nq] int32; idcg [nq, n_ndcg] float64 = the
+ *   reference's `idcg.sum()` (:447 / :318 / :164); log2_table [n_log2] float64, log2_table[r] = numpy's log2(1 + r), n_log2 >
+ *   every nDCG cutoff (so the divisors are the reference's bits and the device evaluates no logarithm).
+ *   Outputs per query (DEVICE): first_rank [nq] int32 = the rank of the first surviving binary-relevant row, 0 without one;
+ *   hits [nq, n_mrr] int32 = surviving binary-relevant rows with rank <= cutoff; ap [nq] float64 (:405-407 / :271-273;
+ *   0 when no row of the list is binary-relevant); ndcg [nq, n_ndcg] float64 (:444-461; 0 when no row of the list is
+ *   judged, NaN exactly where the reference divides 0 by 0: a list with a judged row for a query whose judged documents
+ *   all have grade 0).  RR, recall and the rank at a cutoff follow from first_rank, hits and binary_num_relevant.
+ *   One wavefront per query; float64 sums of correctly rounded terms, added in rank order.
+ */
+int mm_rank_metrics_fwd(const int32_t* order, const int64_t* seg_begin, const int32_t* grade, const int32_t* cand_pos,
+                        int64_t n_rows, int nq, int threshold, double binarization_point,
+                        const int32_t* mrr_cutoffs, int n_mrr, const int32_t* ndcg_cutoffs, int n_ndcg, int map_cutoff,
+                        const int32_t* binary_num_relevant, const double* idcg, const double* log2_table, int n_log2,
+                        int32_t* first_rank, int32_t* hits, double* ap, double* ndcg, void* stream);
+
+/* mm_rank_metrics_depth_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: the per-query body of calculate_metrics_along_candidate_depth (core_metrics.py:42-173) for every candidate
+ *           threshold t = 1 .. hi at once, without its [hi, hi] mask (:40, :88-92).
+ *   Inputs as mm_rank_metrics_fwd, cand_pos required; 1 <= hi <= MM_RANK_MAX_LEN (more returns MM_EUNSUPPORTED before any
+ *   launch).  Outputs first_rank [nq, hi] int32, hits [nq, hi, n_mrr] int32, ap [nq, hi] float64, ndcg [nq, hi, n_ndcg]
+ *   float64: entry t - 1 is what mm_rank_metrics_fwd gives with threshold = t (sums in rank order).
+ *   A list shorter than hi behaves as padded (:58-85).  The reference refuses a list longer than hi (a broadcast error) and
+ *   so must the caller: the kernel reads the first hi rows of such a list only.
+ *   One lane per (query, threshold) walks the query's (cand_pos, grade) pairs, staged in LDS in rank order.
+ */
+int mm_rank_metrics_depth_fwd(const int32_t* order, const int64_t* seg_begin, const int32_t* grade, const int32_t* cand_pos,
+                              int64_t n_rows, int nq, int hi, double binarization_point,
+                              const int32_t* mrr_cutoffs, int n_mrr, const int32_t* ndcg_cutoffs, int n_ndcg, int map_cutoff,
+                              const int32_t* binary_num_relevant, const double* idcg, const double* log2_table, int n_log2,
+                              int32_t* first_rank, int32_t* hits, double* ap, double* ndcg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

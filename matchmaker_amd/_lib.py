@@ -102,7 +102,13 @@ SIGNATURES = {
     "mm_ivf_scan_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "mm_store_append_workspace_bytes": (_sz, [_i, _i]),
     "mm_store_append": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "mm_segment_rank_fwd": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _vp]),
+    "mm_rank_metrics_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _c.c_double, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
+                                 _vp, _vp, _vp, _vp, _vp]),
+    "mm_rank_metrics_depth_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _c.c_double, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
+                                       _vp, _vp, _vp, _vp, _vp]),
 }
+RANK_MAX_LEN, RANK_MAX_CUTOFFS, RANK_NOT_JUDGED = 8192, 8, -2 ** 31      # MM_RANK_MAX_LEN / _MAX_CUTOFFS / _NOT_JUDGED
 
 _lib = None
 

@@ -16,6 +16,7 @@
 //      (the indices are distinct, so the slots are) and writes the document's range there.
 // Every output element is written once, by one lane; no atomics, nothing read back: graph-capturable, bit-reproducible.
 #include "mm_internal.h"
+#include "bitonic_device.h"
 
 namespace mm {
 
@@ -44,23 +45,6 @@ static int cand_pow2_ge(int v) {
   int p = 1;
   while (p < v) p <<= 1;
   return p;
-}
-
-// Ascending bitonic network over key[0, n) (n a power of two), all threads of the workgroup.
-__device__ __forceinline__ void bitonic_asc_i32(int32_t* key, int n, int tid, int nt) {
-  for (int size = 2; size <= n; size <<= 1) {
-    for (int strd = size >> 1; strd > 0; strd >>= 1) {
-      __syncthreads();
-      for (int idx = tid; idx < (n >> 1); idx += nt) {
-        const int lo = 2 * idx - (idx & (strd - 1));
-        const int hi = lo + strd;
-        const bool asc = (lo & size) == 0;
-        const int32_t a = key[lo], b = key[hi];
-        if ((a > b) == asc) { key[lo] = b; key[hi] = a; }
-      }
-    }
-  }
-  __syncthreads();
 }
 
 // Owner of `row`: the last j with dbeg[j] <= row owns it when row < dend[j] (zero-length documents sort in front of a
@@ -121,7 +105,7 @@ __global__ void __launch_bounds__(kCandThreads, 8) colbert_candidates_kernel(Can
         if (h < a.n2) key[h] = k4[u];
       }
     }
-    bitonic_asc_i32(key, a.n2, tid, nt);
+    bitonic_asc(key, a.n2, tid, nt);
 
     // ---- first occurrences -> exclusive prefix sum -> compaction in place
     const int first = tid * per;
@@ -171,7 +155,7 @@ __global__ void __launch_bounds__(kCandThreads, 8) colbert_candidates_kernel(Can
       }
       key[i] = d;
     }
-    bitonic_asc_i32(key, c2, tid, nt);
+    bitonic_asc(key, c2, tid, nt);
 
     // ---- 3. outputs
     int32_t* o_doc = a.cand_doc + (int64_t)q * a.C_cap;

@@ -1698,3 +1698,122 @@ def matchpyramid_bwd(q: torch.Tensor, d: torch.Tensor, weights, biases, pool_siz
         wo += t.numel()
         bo += int(t.shape[0])
     return gq, gd, grad_w, grad_b
+
+
+# ---- ranking and IR metrics (rank_metrics.hip) --------------------------------------------------------------------------
+RANK_MAX_LEN = _lib.RANK_MAX_LEN            # rows per segment of segment_rank, thresholds of rank_metrics_depth
+RANK_NOT_JUDGED = _lib.RANK_NOT_JUDGED      # grade of a row whose document is not in its query's qrels
+
+
+def _seg_begin_check(op: str, seg_begin: torch.Tensor):
+    if seg_begin.dim() != 1 or seg_begin.dtype != torch.int64 or seg_begin.shape[0] < 1:
+        raise NativeError(f"{op}: seg_begin must be int64 [nq + 1], got {seg_begin.dtype} {tuple(seg_begin.shape)}")
+
+
+def segment_rank(scores: torch.Tensor, seg_begin: torch.Tensor, max_len: int) -> torch.Tensor:
+    """Per-query rank order of flat scores (utils/core_metrics.py:502-511; native mm_segment_rank_fwd).
+
+    scores [N] float32 / float16 / bfloat16 in arrival order; seg_begin [nq + 1] int64, ascending: query s owns rows
+    [seg_begin[s], seg_begin[s + 1]); max_len >= every segment length, at most RANK_MAX_LEN (more is refused: the caller
+    takes another route).  Returns order [N] int32: order[seg_begin[s] + r] is the row with rank r + 1 in query s — higher
+    score first, equal scores in arrival order, -0.0 == +0.0, NaN after everything else.  One or two launches on the current
+    stream, no workspace, no read-back: graph-capturable."""
+    dev = _dev_check(scores, seg_begin)
+    if scores.dim() != 1 or scores.dtype not in _DT:
+        raise NativeError(f"segment_rank: scores must be float32 / float16 / bfloat16 [N], got {scores.dtype} {tuple(scores.shape)}")
+    _seg_begin_check("segment_rank", seg_begin)
+    max_len = int(max_len)
+    if not 0 <= max_len <= RANK_MAX_LEN:
+        raise NativeError(f"segment_rank: max_len={max_len} outside 0 .. {RANK_MAX_LEN} rows per segment", _lib.MM_EUNSUPPORTED)
+    n, nq = scores.shape[0], seg_begin.shape[0] - 1
+    if n >= 1 << 31:
+        raise NativeError(f"segment_rank: n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
+    scores, seg_begin = scores.contiguous(), seg_begin.contiguous()
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0 or nq == 0:
+        return order
+    _call(dev, _lib.lib().mm_segment_rank_fwd, (scores.data_ptr(), _DT[scores.dtype], seg_begin.data_ptr(), n, nq, max_len,
+                                                order.data_ptr()), stream_only=True)
+    return order
+
+
+def _cutoffs(op: str, name: str, cutoffs):
+    cutoffs = [int(c) for c in cutoffs]
+    if len(cutoffs) > _lib.RANK_MAX_CUTOFFS or any(c < 1 for c in cutoffs):
+        raise NativeError(f"{op}: {name}={cutoffs}: at most {_lib.RANK_MAX_CUTOFFS} cutoffs, each >= 1", _lib.MM_EUNSUPPORTED)
+    return cutoffs, (ctypes.c_int32 * max(len(cutoffs), 1))(*cutoffs)
+
+
+def _rank_metrics(op, fn, per_query, order, seg_begin, grade, cand_pos, scalar, binarization_point, mrr_cutoffs, ndcg_cutoffs,
+                  map_cutoff, binary_num_relevant, idcg, log2_table):
+    """The checks and the call rank_metrics and rank_metrics_depth share; per_query = output entries per query (1 / hi)."""
+    dev = _dev_check(order, seg_begin, grade, cand_pos, binary_num_relevant, idcg, log2_table)
+    _seg_begin_check(op, seg_begin)
+    n, nq = order.shape[0], seg_begin.shape[0] - 1
+    rows = [("order", order), ("grade", grade)] + ([("cand_pos", cand_pos)] if cand_pos is not None else [])
+    for name, t in rows:
+        if t.dim() != 1 or t.dtype != torch.int32 or t.shape[0] != n:
+            raise NativeError(f"{op}: {name} must be int32 [{n}], got {t.dtype} {tuple(t.shape)}")
+    rc, rc_c = _cutoffs(op, "mrr_cutoffs", mrr_cutoffs)
+    nc, nc_c = _cutoffs(op, "ndcg_cutoffs", ndcg_cutoffs)
+    if int(map_cutoff) < 1:
+        raise NativeError(f"{op}: map_cutoff={map_cutoff} below 1")
+    if binary_num_relevant.dtype != torch.int32 or tuple(binary_num_relevant.shape) != (nq,):
+        raise NativeError(f"{op}: binary_num_relevant must be int32 [{nq}], got {binary_num_relevant.dtype} "
+                          f"{tuple(binary_num_relevant.shape)}")
+    if idcg.dtype != torch.float64 or tuple(idcg.shape) != (nq, len(nc)):
+        raise NativeError(f"{op}: idcg must be float64 [{nq}, {len(nc)}], got {idcg.dtype} {tuple(idcg.shape)}")
+    if log2_table.dtype != torch.float64 or log2_table.dim() != 1 or log2_table.shape[0] <= max(nc, default=0):
+        raise NativeError(f"{op}: log2_table must be float64 [> {max(nc, default=0)}] (log2(1 + r) up to the largest nDCG cutoff), "
+                          f"got {log2_table.dtype} {tuple(log2_table.shape)}")
+    if n >= 1 << 31:
+        raise NativeError(f"{op}: n={n} >= 2^31", _lib.MM_EUNSUPPORTED)
+    order, seg_begin, grade = order.contiguous(), seg_begin.contiguous(), grade.contiguous()
+    cand_pos = cand_pos.contiguous() if cand_pos is not None else None
+    binary_num_relevant, idcg, log2_table = binary_num_relevant.contiguous(), idcg.contiguous(), log2_table.contiguous()
+    shape = (nq,) if per_query is None else (nq, per_query)
+    first_rank = torch.empty(shape, dtype=torch.int32, device=dev)
+    hits = torch.empty(shape + (len(rc),), dtype=torch.int32, device=dev)
+    ap = torch.empty(shape, dtype=torch.float64, device=dev)
+    ndcg = torch.empty(shape + (len(nc),), dtype=torch.float64, device=dev)
+    if nq:
+        _call(dev, fn, (order.data_ptr() if n else None, seg_begin.data_ptr(), grade.data_ptr() if n else None,
+                        cand_pos.data_ptr() if cand_pos is not None and n else None, n, nq, int(scalar), float(binarization_point),
+                        ctypes.addressof(rc_c), len(rc), ctypes.addressof(nc_c), len(nc), int(map_cutoff),
+                        binary_num_relevant.data_ptr(), idcg.data_ptr(), log2_table.data_ptr(), log2_table.shape[0],
+                        first_rank.data_ptr(), hits.data_ptr() if rc else None, ap.data_ptr(), ndcg.data_ptr() if nc else None),
+              stream_only=True)
+    return first_rank, hits, ap, ndcg
+
+
+def rank_metrics(order: torch.Tensor, seg_begin: torch.Tensor, grade: torch.Tensor, cand_pos: Optional[torch.Tensor],
+                 threshold: int, binarization_point: float, mrr_cutoffs, ndcg_cutoffs, map_cutoff: int,
+                 binary_num_relevant: torch.Tensor, idcg: torch.Tensor, log2_table: torch.Tensor):
+    """Per-query metric quantities at one candidate threshold (the per-query bodies of calculate_metrics_plain,
+    utils/core_metrics.py:380-461, and calculate_metrics_single_candidate_threshold, :228-327; native mm_rank_metrics_fwd).
+
+    order [N] int32 (segment_rank's), grade [N] int32 (RANK_NOT_JUDGED = not in the query's qrels), cand_pos [N] int32 or
+    None; rows with cand_pos > threshold are dropped and the rest renumbered (threshold = 2^31-1 with cand_pos None is the
+    plain form).  binary_num_relevant [nq] int32, idcg [nq, len(ndcg_cutoffs)] float64, log2_table float64 = log2(1 + r).
+    Returns (first_rank [nq] int32, hits [nq, len(mrr_cutoffs)] int32, ap [nq] float64, ndcg [nq, len(ndcg_cutoffs)]
+    float64).  One launch on the current stream, no workspace, no atomics: graph-capturable, bit-equal run to run."""
+    if not -2 ** 31 <= int(threshold) < 2 ** 31:
+        raise NativeError(f"rank_metrics: threshold={threshold} is not an int32")
+    return _rank_metrics("rank_metrics", _lib.lib().mm_rank_metrics_fwd, None, order, seg_begin, grade, cand_pos, threshold,
+                         binarization_point, mrr_cutoffs, ndcg_cutoffs, map_cutoff, binary_num_relevant, idcg, log2_table)
+
+
+def rank_metrics_depth(order: torch.Tensor, seg_begin: torch.Tensor, grade: torch.Tensor, cand_pos: torch.Tensor, hi: int,
+                       binarization_point: float, mrr_cutoffs, ndcg_cutoffs, map_cutoff: int,
+                       binary_num_relevant: torch.Tensor, idcg: torch.Tensor, log2_table: torch.Tensor):
+    """rank_metrics at every candidate threshold t = 1 .. hi in one launch (calculate_metrics_along_candidate_depth,
+    utils/core_metrics.py:42-173, without its [hi, hi] mask; native mm_rank_metrics_depth_fwd).  hi <= RANK_MAX_LEN; every
+    segment must be at most hi rows long (the caller checks: the reference raises there).  Returns (first_rank [nq, hi],
+    hits [nq, hi, nR], ap [nq, hi], ndcg [nq, hi, nN]); entry t - 1 is rank_metrics(threshold=t)."""
+    hi = int(hi)
+    if cand_pos is None:
+        raise NativeError("rank_metrics_depth: cand_pos is needed (the sweep is over first-stage ranks)")
+    if not 1 <= hi <= RANK_MAX_LEN:
+        raise NativeError(f"rank_metrics_depth: hi={hi} outside 1 .. {RANK_MAX_LEN} thresholds", _lib.MM_EUNSUPPORTED)
+    return _rank_metrics("rank_metrics_depth", _lib.lib().mm_rank_metrics_depth_fwd, hi, order, seg_begin, grade, cand_pos, hi,
+                         binarization_point, mrr_cutoffs, ndcg_cutoffs, map_cutoff, binary_num_relevant, idcg, log2_table)

@@ -160,3 +160,47 @@ def unrolled_to_ranked_result(unrolled: Dict[str, List[Tuple[str, float]]]) -> D
     """utils/core_metrics.py:502-511: per query, `sorted(..., key=score, reverse=True)` — stable, so ties
     keep arrival order."""
     return {qid: [doc for doc, _ in sorted(rows, key=lambda x: x[1], reverse=True)] for qid, rows in unrolled.items()}
+
+
+def evaluate_to_metrics(model, batches: Iterable[dict], eval_set, use_fp16: bool = True, device=None,
+                        output_secondary_output: bool = False, graph: bool = False, candidate_threshold=None,
+                        check_ids: bool = True):
+    """evaluate_batches + unrolled_to_ranked_result + calculate_metrics_plain (eval.py:264-320) with the scores kept on the
+    device: same batch protocol and same forward calls as evaluate_batches, but every batch's scores are appended to one flat
+    device tensor in arrival order (no `.cpu()` per batch), and the pass ends in ONE ranking call and ONE metrics call on
+    `eval_set` (matchmaker_amd.metrics.EvalSet, built once from the candidate file's (query_id, doc_id) pairs in the order the
+    batches deliver them, and moved to the device).  candidate_threshold: calculate_metrics_single_candidate_threshold instead
+    of the plain form.  Returns (ranked_result {query_id: [doc ids]}, metrics dict).
+    check_ids: the batches' ids are compared with the set's as they arrive (a host-side list comparison)."""
+    if device is None:
+        import itertools
+        t = next(itertools.chain(model.parameters(), model.buffers()), None)
+        if t is None:
+            raise ValueError("evaluate_to_metrics: the model has no parameters or buffers; pass device=")
+        device = t.device
+    graphed = _GraphedForward(model, use_fp16, output_secondary_output, torch.device(device)) if graph else None
+    pieces, seen = [], 0
+    want_q, want_d = eval_set.arrival_ids
+    with torch.no_grad():
+        for batch_orig in batches:
+            n = len(batch_orig["query_id"])
+            if check_ids and (list(batch_orig["query_id"]) != want_q[seen:seen + n] or list(batch_orig["doc_id"]) != want_d[seen:seen + n]):
+                raise ValueError(f"evaluate_to_metrics: the batch at row {seen} does not deliver the (query_id, doc_id) pairs the "
+                                 "EvalSet was built from")
+            seen += n
+            if graphed is not None:
+                pieces.append(graphed(batch_orig).float().reshape(-1).clone())      # the graph's output buffer is reused
+                continue
+            with torch.autocast("cuda", dtype=torch.float16, enabled=use_fp16):          # eval.py:83
+                batch = _to_device({k: batch_orig[k] for k in ("query_tokens", "doc_tokens")}, device)   # :89
+                output = model.forward(batch["query_tokens"], batch["doc_tokens"],
+                                       output_secondary_output=output_secondary_output, use_fp16=use_fp16)   # :108
+                if output_secondary_output:
+                    output, _ = output                                                   # :136
+            pieces.append(output.float().reshape(-1))
+    if seen != eval_set.n_rows:
+        raise ValueError(f"evaluate_to_metrics: the batches delivered {seen} pairs, the EvalSet holds {eval_set.n_rows}")
+    scores = torch.cat(pieces) if pieces else torch.zeros(0, device=device)
+    order = eval_set.rank(scores)
+    per_query = eval_set.per_query(scores, candidate_threshold, order=order)
+    return eval_set.ranked_result(scores, order=order), eval_set.metrics_from_per_query(*per_query)

@@ -15,6 +15,7 @@ Importing this module defines
     torch.ops.mm_native.fp8_quantize_rows(x)                                        -> (codes [T, E] uint8, scales [T])
     torch.ops.mm_native.maxsim_ragged_fp8(q, codes, scales, doc_begin, doc_end, q_mask=None, pairs_per_query=1,
                                           check_ranges=True, sim_round=False, sum_round=False) -> [n_pairs]
+    torch.ops.mm_native.segment_rank(scores, seg_begin, max_len)                    -> order [N] int32
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
@@ -511,3 +512,16 @@ def _(queries, vectors, neighbors, entry_rows, ef, k, width=4, max_iters=None):
     nq = queries.shape[0]
     return (queries.new_empty((nq, k), dtype=torch.float32), queries.new_empty((nq, k), dtype=torch.int64),
             queries.new_empty((nq, 2), dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- ranking
+@torch.library.custom_op(_NS + "::segment_rank", mutates_args=(), device_types="cuda")
+def segment_rank(scores: Tensor, seg_begin: Tensor, max_len: int) -> Tensor:
+    """order [N] int32: per-query rank order of flat scores (ops.segment_rank; utils/core_metrics.py:502-511).  A
+    permutation, not a differentiable function: no autograd formula."""
+    return ops.segment_rank(scores, seg_begin, max_len)
+
+
+@segment_rank.register_fake
+def _(scores, seg_begin, max_len):
+    return scores.new_empty((scores.shape[0],), dtype=torch.int32)
