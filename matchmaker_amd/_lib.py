@@ -1,116 +1,16 @@
-"""ctypes binding of libmm_native.so (C ABI declared in include/mm_native.h).
+"""ctypes binding of libmm_native.so.  include/mm_native.h is the one description of the C ABI: the table of prototypes and the
+constants below are read from it at import, nothing is restated here.
 
 There is NO fallback: if the library is missing or a call fails, an exception is raised.
 """
 import ctypes
 import os
+import re
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 # MM_NATIVE_LIB: another build of the same library for ONE process (A/B variants, tools/build_variant.sh)
 LIB_PATH = os.environ.get("MM_NATIVE_LIB") or os.path.join(HERE, "csrc", "libmm_native.so")
-
-MM_F32, MM_F16, MM_BF16 = 0, 1, 2
-MASK_NONE, MASK_LEN_I32, MASK_U8, MASK_I64, MASK_F32 = 0, 1, 2, 3, 4
-TKL_SAT_EMBEDDING, TKL_SAT_LOG = 0, 1
-SIM_ROUND, SUM_ROUND = 1, 2          # MM_SIM_ROUND / MM_SUM_ROUND
-STORE_KEEP_ZERO_ROWS = 1             # MM_STORE_KEEP_ZERO_ROWS
-ABI_VERSION = 4
-MM_OK, MM_EINVAL, MM_EUNSUPPORTED, MM_EWORKSPACE, MM_ELAUNCH = 0, -1, -2, -3, -4
-
-_c = ctypes
-_vp, _i64, _i, _sz = _c.c_void_p, _c.c_int64, _c.c_int, _c.c_size_t
-
-# symbol -> (restype, argtypes): must list every function declared in include/mm_native.h
-SIGNATURES = {
-    "mm_abi_version": (_i, []),
-    "mm_last_error": (_c.c_char_p, []),
-    "mm_maxsim_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i]),
-    "mm_maxsim_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_maxsim_fwd_batched": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "mm_maxsim_inbatch_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i]),
-    "mm_maxsim_inbatch_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_maxsim_ragged_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
-    "mm_maxsim_ragged_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_hbm_stream_probe": (_i, [_vp, _i64, _i, _vp]),
-    "mm_maxsim_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_maxsim_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_maxsim_inbatch_bwd_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i, _i]),
-    "mm_maxsim_inbatch_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i]),
-    "mm_kernel_pool_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64,
-                                _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_ex_fwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_float, _vp, _vp, _i64, _i64,
-                                   _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_ex_fwd2": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _c.c_float, _vp, _vp, _vp, _i64, _i64,
-                                    _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_ex_bwd2": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _c.c_float, _vp, _vp, _vp, _vp, _vp,
-                                    _vp, _vp, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_ex_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _c.c_float, _vp, _vp, _vp, _vp,
-                                   _vp, _vp, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_tkl_bwd_workspace_bytes": (_sz, [_i64, _i]),
-    "mm_tkl_bwd_workspace_bytes2": (_sz, [_i64, _i, _i, _i]),
-    "mm_tkl_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_multi_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i, _i, _i, _i]),
-    "mm_kernel_pool_multi_fwd": (_i, [_vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _c.c_float, _vp, _i64, _i64,
-                                      _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_kernel_pool_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_kernel_pool_bwd_workspace_bytes2": (_sz, [_i64, _i, _i, _i, _i, _i]),
-    "mm_kernel_pool_bwd": (_i, [_vp, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
-                                _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_dot_topk_workspace_bytes": (_sz, [_i64, _i, _i]),
-    "mm_dot_topk_fwd": (_i, [_vp, _vp, _i64, _i, _i, _i, _i, _c.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mm_topk_merge": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
-    "mm_tkl_workspace_bytes": (_sz, [_i64, _i64, _i, _i, _i]),
-    "mm_tkl_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_tkl_fwd_peaks": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_ivf_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_ivf_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "mm_ah_encode": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _c.c_float, _i, _vp, _vp]),
-    "mm_ah_scan_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_ah_scan_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "mm_gather_dot": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _vp]),
-    "mm_graph_search_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
-    "mm_graph_search_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mm_kmeans_assign": (_i, [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
-    "mm_kmeans_segment_sum_workspace_bytes": (_sz, [_i64, _i, _i]),
-    "mm_kmeans_segment_sum": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "mm_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i]),
-    "mm_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_co_pacrr_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i, _i, _i]),
-    "mm_co_pacrr_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _sz,
-                             _vp]),
-    "mm_co_pacrr_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i,
-                             _vp, _sz, _vp]),
-    "mm_drmm_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_drmm_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_matchpyramid_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
-    "mm_matchpyramid_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "mm_matchpyramid_fwd_save_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
-    "mm_matchpyramid_fwd_save": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "mm_matchpyramid_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i, _vp]),
-    "mm_matchpyramid_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _vp, _sz,
-                                 _vp]),
-    "mm_colbert_candidates_workspace_bytes": (_sz, [_i, _i]),
-    "mm_colbert_candidates": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mm_fp8_quantize_rows": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
-    "mm_maxsim_ragged_fp8_workspace_bytes": (_sz, [_i64, _i64, _i, _i]),
-    "mm_maxsim_ragged_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i64, _i64, _i, _i, _i, _i, _vp, _sz, _vp]),
-    "mm_dot_topk_fp8_workspace_bytes": (_sz, [_i64, _i, _i]),
-    "mm_dot_topk_fp8_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _c.c_float, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mm_ivf_scan_fp8_workspace_bytes": (_sz, [_i64, _i, _i, _i, _i]),
-    "mm_ivf_scan_fp8_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "mm_store_append_workspace_bytes": (_sz, [_i, _i]),
-    "mm_store_append": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "mm_segment_rank_fwd": (_i, [_vp, _i, _vp, _i64, _i, _i, _vp, _vp]),
-    "mm_rank_metrics_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _c.c_double, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                 _vp, _vp, _vp, _vp, _vp]),
-    "mm_rank_metrics_depth_fwd": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _c.c_double, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i,
-                                       _vp, _vp, _vp, _vp, _vp]),
-}
-RANK_MAX_LEN, RANK_MAX_CUTOFFS, RANK_NOT_JUDGED = 8192, 8, -2 ** 31      # MM_RANK_MAX_LEN / _MAX_CUTOFFS / _NOT_JUDGED
-
-_lib = None
+HEADER_PATH = os.path.join(HERE, "..", "include", "mm_native.h")
 
 
 class NativeError(RuntimeError):
@@ -119,6 +19,52 @@ class NativeError(RuntimeError):
     def __init__(self, msg="", code=None):
         super().__init__(msg)
         self.code = code
+
+
+_RETURNS = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}
+
+
+def _read_header(text):
+    """The text of a C header -> ({symbol: (restype, [argtypes])} of every prototype `RET mm_name(ARGS);`,
+    {NAME: int} of every object-like #define with a value).  The header's vocabulary is small: three return types, five scalars,
+    and every declarator with a `*` is a pointer.  Anything outside it is a NativeError naming the symbol, never a guess."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(\w+)[ \t]+(\S[^\n]*)$", text, re.M):   # NAME( is a macro: no match
+        terms = re.sub(r"\s", "", value)                                     # a decimal integer or a sum of them: (-2147483647 - 1)
+        if not re.fullmatch(r"\(?[-+]?(0|[1-9]\d*)([-+](0|[1-9]\d*))*\)?", terms):
+            raise NativeError(f"#define {name}: cannot read the value {value.strip()!r}")
+        defines[name] = sum(int(t) for t in re.findall(r"[-+]?\d+", terms))
+    signatures = {}
+    text = re.sub(r"^[ \t]*#[^\n]*$", "", text, flags=re.M)      # macros go; a struct's members have no parentheses: no match below
+    for ret, name, args in re.findall(r"([^;{}()]*?)\b(mm_\w+)\s*\(([^()]*)\)\s*;", text):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise NativeError(f"{name}: cannot bind the return type {ret!r}")
+        argtypes = []
+        for arg in [a.strip() for a in args.split(",") if args.strip() not in ("", "void")]:
+            m = re.fullmatch(r"(?:const\s+)?(\w+)(?:\s+\w+)?", arg)
+            if "*" not in arg and not (m and m.group(1) in _SCALARS):
+                raise NativeError(f"{name}: cannot bind the argument {arg!r}")
+            argtypes.append(ctypes.c_void_p if "*" in arg else _SCALARS[m.group(1)])
+        signatures[name] = (_RETURNS[ret], argtypes)
+    return signatures, defines
+
+
+try:
+    with open(HEADER_PATH) as _f:
+        SIGNATURES, _DEFINES = _read_header(_f.read())
+except OSError as e:
+    raise NativeError(f"the C ABI is read from {os.path.normpath(HEADER_PATH)}, which cannot be opened: {e}") from e
+# the header's constants under the names this package uses: MM_<NAME>, most of them without the prefix
+for _name in ("MM_F32 MM_F16 MM_BF16 MASK_NONE MASK_LEN_I32 MASK_U8 MASK_I64 MASK_F32 TKL_SAT_EMBEDDING TKL_SAT_LOG SIM_ROUND SUM_ROUND "
+              "STORE_KEEP_ZERO_ROWS ABI_VERSION MM_OK MM_EINVAL MM_EUNSUPPORTED MM_EWORKSPACE MM_ELAUNCH "
+              "RANK_MAX_LEN RANK_MAX_CUTOFFS RANK_NOT_JUDGED").split():
+    globals()[_name] = _DEFINES[_name if _name in _DEFINES else "MM_" + _name]
+
+_lib = None
 
 
 def lib():

@@ -2,9 +2,6 @@
 where the reference tree exists, against live instances; the drop-in's from_config / state_dict parity; patch_matchmaker's
 rebinding; the fake (meta) implementation of torch.ops.mm_native.co_pacrr_kmax; the host and C ABI refusals (no device
 needed)."""
-import os
-import shutil
-import subprocess
 import sys
 import types
 
@@ -16,7 +13,6 @@ from oracle import ref_harness as R
 from tests import co_pacrr_reference as CP
 from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CFG = {"pacrr_unified_query_length": 30, "pacrr_unified_document_length": 200, "pacrr_max_conv_kernel_size": 3,
        "pacrr_conv_output_size": 32, "pacrr_kmax_pooling_size": 5}       # config/train/non-bert-defaults.yaml:54-58
 CASES = ["ref", "short", "mid", "long", "oddu", "padded", "qpad", "b1", "n1", "k1"]
@@ -237,12 +233,8 @@ def test_views_narrower_than_k_are_refused_as_the_reference_raises(monkeypatch):
 
 
 def test_c_client_gets_einval_and_eunsupported_without_a_gpu(tmp_path):
-    from matchmaker_amd import build
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "co_pacrr_client.c"
-    src.write_text(r"""
+    from tests import abi
+    out = abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -277,12 +269,5 @@ int main(void) {
   printf("co_pacrr c client ok: %s\n", mm_last_error());
   return 0;
 }
-""")
-    exe = tmp_path / "co_pacrr_client"
-    libdir = os.path.dirname(so)
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o",
-                        str(exe), "-L", libdir, "-l:libmm_native.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
-    assert "co_pacrr c client ok" in r.stdout
+""", name="co_pacrr_client")
+    assert "co_pacrr c client ok" in out

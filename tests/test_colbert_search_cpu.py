@@ -2,7 +2,6 @@
 view of the store, the C ABI declarations, the fake-tensor rule, and search() driven through stand-ins for its four native
 calls (token search, candidates, MaxSim, selection)."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -126,15 +125,12 @@ def test_overlapping_documents_are_refused_by_name():
 # ------------------------------------------------------------------------------------------ C ABI and the torch op
 def test_header_and_binding_declare_the_candidate_entry_points():
     from matchmaker_amd import _lib, build
+    from tests import abi
+    L = abi.assert_bound(("mm_colbert_candidates_workspace_bytes", "mm_colbert_candidates"))
     hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    assert "MM_ABI_VERSION 4" in hdr and _lib.ABI_VERSION == 4
-    m = re.search(r"int mm_colbert_candidates\(([^;]*)\);", hdr)
-    assert m and m.group(1).count(",") + 1 == len(_lib.SIGNATURES["mm_colbert_candidates"][1]) == 16
-    assert re.search(r"size_t mm_colbert_candidates_workspace_bytes\(int nq, int H\);", hdr)
+    assert _lib.ABI_VERSION == 4
     assert "dense_retrieval.py:391-412" in hdr and "colbert.py:100-112" in hdr
     assert "colbert_candidates.hip" in build.SOURCES
-    build.build()
-    L = _lib.lib()
     # host arithmetic and refusals: callable without a GPU, nothing is launched
     assert L.mm_colbert_candidates_workspace_bytes(3, 1000) >= 3 * 1000 * 4
     assert L.mm_colbert_candidates_workspace_bytes(3, 16385) == 0

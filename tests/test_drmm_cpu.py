@@ -7,9 +7,6 @@ planted case, with tol = 4 x max |c32 - c64| measured per case and at most 0.5 %
 1e-5: every term is gate x tanh(.), gates sum to 1 and tanh outputs lie in (-1, 1), so the fp32 head is within a few ulp
 of 1."""
 import importlib
-import os
-import shutil
-import subprocess
 import sys
 import types
 
@@ -21,7 +18,6 @@ from oracle import ref_harness as R
 from tests import drmm_reference as DR
 from tests import util
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ["ref", "padded", "oov", "qpad", "b1", "d77", "d300", "bins7", "planted", "elmo"]
 CAP = 0.005
 
@@ -240,12 +236,8 @@ def test_ops_reject_cpu_tensors_and_out_of_limit_shapes():
 
 
 def test_c_client_gets_einval_and_eunsupported_without_a_gpu(tmp_path):
-    from matchmaker_amd import build
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "drmm_client.c"
-    src.write_text(r"""
+    from tests import abi
+    out = abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -281,12 +273,5 @@ int main(void) {
   printf("drmm c client ok\n");
   return 0;
 }
-""")
-    exe = tmp_path / "drmm_client"
-    libdir = os.path.dirname(so)
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o",
-                        str(exe), "-L", libdir, "-l:libmm_native.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
-    assert "drmm c client ok" in r.stdout
+""", name="drmm_client")
+    assert "drmm c client ok" in out

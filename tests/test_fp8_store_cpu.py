@@ -2,7 +2,6 @@
 of the restated format (element bound, scaled maximum, no NaN code, idempotence), the score bound, and TokenStore's fp8 host
 logic driven through stand-ins for the native calls."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,18 +16,12 @@ DTYPES = [torch.float16, torch.bfloat16, torch.float32]
 # ------------------------------------------------------------------------------------------ C ABI, binding, torch ops
 def test_header_and_binding_declare_the_three_entry_points():
     from matchmaker_amd import _lib, build
+    from tests import abi
+    L = abi.assert_bound(("mm_fp8_quantize_rows", "mm_maxsim_ragged_fp8_workspace_bytes", "mm_maxsim_ragged_fp8_fwd"))
     hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    assert "MM_ABI_VERSION 4" in hdr and _lib.ABI_VERSION == 4
-    for name, n_args in (("int mm_fp8_quantize_rows", 7), ("size_t mm_maxsim_ragged_fp8_workspace_bytes", 4),
-                         ("int mm_maxsim_ragged_fp8_fwd", 17)):
-        m = re.search(re.escape(name) + r"\(([^;]*)\);", hdr)
-        assert m, name
-        assert m.group(1).count(",") + 1 == len(_lib.SIGNATURES[name.split()[-1]][1]) == n_args
     assert "e4m3fn" in hdr and "fnuz" in hdr
     assert "maxsim_fp8.hip" in build.SOURCES
-    build.build()
-    L = _lib.lib()                                                         # binds every listed symbol or raises
-    assert L.mm_abi_version() == 4
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     # host arithmetic and refusals: callable without a GPU, nothing is launched
     assert L.mm_maxsim_ragged_fp8_workspace_bytes(10, 1, 32, _lib.MASK_NONE) == 0
     assert L.mm_maxsim_ragged_fp8_workspace_bytes(10, 5, 32, _lib.MASK_U8) > 0

@@ -2,7 +2,6 @@
 raw binding (nothing is launched), the preconditions of the exact cases of tests/test_fp8_token_search_gpu.py from the
 restatement alone, and TokenStore's token_search= / row_shard= host logic driven through numpy stand-ins."""
 import os
-import re
 
 import numpy as np
 import pytest
@@ -18,17 +17,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ------------------------------------------------------------------------------------------ C ABI and binding
 def test_header_binding_and_exports_declare_the_entry():
     from matchmaker_amd import _lib, build, ops
+    from tests import abi
+    L = abi.assert_bound(("mm_dot_topk_fp8_workspace_bytes", "mm_dot_topk_fp8_fwd"))
     hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    assert "MM_ABI_VERSION 4" in hdr and _lib.ABI_VERSION == 4
-    for name, n_args in (("size_t mm_dot_topk_fp8_workspace_bytes", 3), ("int mm_dot_topk_fp8_fwd", 15)):
-        m = re.search(re.escape(name) + r"\(([^;]*)\);", hdr)
-        assert m, name
-        assert m.group(1).count(",") + 1 == len(_lib.SIGNATURES[name.split()[-1]][1]) == n_args
     assert "dense_retrieval.py:391" in hdr[hdr.index("fp8 token search"):] and "faiss_indices.py:22-36" in hdr[hdr.index("fp8 token search"):]
     assert "dot_topk_fp8.hip" in build.SOURCES
-    build.build()
-    L = _lib.lib()                                                         # binds every listed symbol or raises
-    assert L.mm_abi_version() == 4
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     assert callable(ops.dot_topk_fp8)
     from matchmaker_amd import torch_ops
     assert "dot_topk_fp8" not in open(torch_ops.__file__).read()           # like dot_topk: the loop reads status back

@@ -2,7 +2,6 @@
 the fake-tensor rule, the indexer's host logic with the numpy restatement (tests/graph_reference.py) standing in for the
 device operators, and the restatement's own recall."""
 import os
-import re
 import socket
 
 import numpy as np
@@ -13,7 +12,6 @@ import torch.multiprocessing as mp
 
 from tests import graph_reference as GR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("mm_graph_search_workspace_bytes", "mm_graph_search_fwd")
 
 
@@ -39,17 +37,10 @@ def _padded16(a, E_pad=128):
 
 def test_symbols_are_declared_bound_and_exported_and_the_abi_version_stays_4():
     from matchmaker_amd import build, _lib
-    header = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    for name in SYMBOLS:
-        assert re.search(r"\b" + name + r"\s*\(", header), name
-        assert name in _lib.SIGNATURES, name
-    assert re.search(r"#define MM_ABI_VERSION 4\b", header) and _lib.ABI_VERSION == 4
-    assert len(_lib.SIGNATURES["mm_graph_search_workspace_bytes"][1]) == 7
-    assert len(_lib.SIGNATURES["mm_graph_search_fwd"][1]) == 20
+    from tests import abi
+    L = abi.assert_bound(SYMBOLS)
     assert "graph_search.hip" in build.SOURCES
-    build.build()
-    L = _lib.lib()                                     # binds every symbol of SIGNATURES: AttributeError if one is missing
-    assert L.mm_abi_version() == 4
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     # the visited table fits LDS: a token workspace; it does not: one slice per workgroup, never more than 1024 of them
     assert L.mm_graph_search_workspace_bytes(3000, 37, 16, 64, 4, 16, 24) == 256
     big = L.mm_graph_search_workspace_bytes(3000, 37, 128, 128, 8, 16, 512)

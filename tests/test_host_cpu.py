@@ -1,6 +1,6 @@
 """CPU tests of the host-side logic (no GPU, no compute through the HIP library): chunking,
-positional features, drop-in constructors / state_dict keys vs the real reference classes, the C-ABI
-library loading with every declared symbol, and loud failure on CPU tensors."""
+positional features, drop-in constructors / state_dict keys vs the real reference classes, a C client of
+the library (the binding itself: tests/test_abi_cpu.py), and loud failure on CPU tensors."""
 import os
 import re
 
@@ -16,34 +16,12 @@ MU = [1.0, 0.9, 0.7, 0.5, 0.3, 0.1, -0.1, -0.3, -0.5, -0.7, -0.9]
 SIGMA = [0.1] * 11
 
 
-def test_library_builds_loads_and_exports_every_declared_symbol():
-    from matchmaker_amd import build, _lib
-    build.build()
-    L = _lib.lib()
-    hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    declared = set(re.findall(r"\b(mm_[a-z_0-9]+)\s*\(", hdr))
-    assert declared, "no declarations found"
-    assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
-    for name in declared:
-        assert hasattr(L, name), name
-    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
-    # size queries are pure host arithmetic: callable without a GPU
-    assert L.mm_maxsim_workspace_bytes(10, 1, 32, 180, _lib.MASK_NONE, _lib.MASK_LEN_I32) == 0
-    assert L.mm_maxsim_workspace_bytes(10, 1, 32, 180, _lib.MASK_I64, _lib.MASK_I64) > 0
-
-
 def test_header_is_plain_c_and_a_c_client_links_the_library(tmp_path):
     """The drop-in boundary is a C ABI: include/mm_native.h must compile as C (gcc -std=c99, no C++ / torch types) and
     a C program must link libmm_native.so and call it — here the entry points that need no GPU: the ABI version, the
     host-side workspace arithmetic, and an argument error reported through mm_last_error()."""
-    import shutil
-    import subprocess
-    from matchmaker_amd import build
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "client.c"
-    src.write_text(r"""
+    from tests import abi
+    out = abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -60,14 +38,7 @@ int main(void) {
   return 0;
 }
 """)
-    exe = tmp_path / "client"
-    libdir = os.path.dirname(so)
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                        "-L", libdir, "-l:libmm_native.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
-    assert "c client ok" in r.stdout
+    assert "c client ok" in out
 
 
 def test_ops_reject_cpu_tensors_loudly():

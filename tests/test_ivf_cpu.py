@@ -1,9 +1,7 @@
 """CPU tests of the IVF inner-product index (matchmaker_amd.retrieval.IVFFlatIPIndexer, mm_ivf_scan_fwd): the C ABI, and
 the indexer's host logic with the numpy restatement (tests/ivf_reference.py) standing in for the device operators."""
 import os
-import shutil
 import socket
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +10,6 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests import ivf_reference as IR
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _topk_fn(q, c, k):
@@ -47,12 +43,8 @@ def _data(n=600, E=40, clusters=12, seed=5):
 
 
 def test_header_compiles_as_c_and_the_library_exports_the_symbols(tmp_path):
-    from matchmaker_amd import build, _lib
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "ivf_client.c"
-    src.write_text(r"""
+    from tests import abi
+    abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -77,17 +69,8 @@ int main(void) {
   printf("ivf c client ok\n");
   return 0;
 }
-""")
-    exe = tmp_path / "ivf_client"
-    libdir = os.path.dirname(so)
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o",
-                        str(exe), "-L", libdir, "-l:libmm_native.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
-    assert "mm_ivf_scan_fwd" in _lib.SIGNATURES and "mm_ivf_scan_workspace_bytes" in _lib.SIGNATURES
-    L = _lib.lib()                                     # binds every symbol of SIGNATURES: AttributeError if one is missing
-    assert L.mm_ivf_scan_workspace_bytes(1000, 10, 7, 3, 10) > 0
+""", name="ivf_client")
+    assert abi.assert_bound(("mm_ivf_scan_fwd", "mm_ivf_scan_workspace_bytes")).mm_ivf_scan_workspace_bytes(1000, 10, 7, 3, 10) > 0
 
 
 def test_ops_ivf_scan_rejects_cpu_tensors_and_bad_arguments():

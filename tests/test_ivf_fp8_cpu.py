@@ -3,7 +3,6 @@ TokenStore.build_token_index): the C ABI declaration and binding, every refusal 
 launched), the operator's argument checks, the indexer's host logic with numpy stand-ins for the device operators, and the
 preconditions of tests/test_ivf_fp8_gpu.py from the restatements alone."""
 import os
-import re
 import socket
 
 import numpy as np
@@ -24,18 +23,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # ------------------------------------------------------------------------------------------ C ABI and binding
 def test_header_binding_and_sources_declare_the_entry():
     from matchmaker_amd import _lib, build, ops
+    from tests import abi
+    L = abi.assert_bound(("mm_ivf_scan_fp8_workspace_bytes", "mm_ivf_scan_fp8_fwd"))
     hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    assert "MM_ABI_VERSION 4" in hdr and _lib.ABI_VERSION == 4
-    for name, n_args in (("size_t mm_ivf_scan_fp8_workspace_bytes", 5), ("int mm_ivf_scan_fp8_fwd", 17)):
-        m = re.search(re.escape(name) + r"\(([^;]*)\);", hdr)
-        assert m, name
-        assert m.group(1).count(",") + 1 == len(_lib.SIGNATURES[name.split()[-1]][1]) == n_args
     section = hdr[hdr.index("fp8 IVF list scan"):]
     assert "faiss_indices.py:106-145" in section and hdr.index("fp8 IVF list scan") > hdr.index("fp8 token search")
     assert "ivf_scan_fp8.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "ivf_scan_fp8.hip"))
-    build.build()
-    L = _lib.lib()                                                         # binds every listed symbol or raises
-    assert L.mm_abi_version() == 4
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     assert callable(ops.ivf_scan_fp8)
 
 

@@ -2,9 +2,6 @@
 matchmaker_amd.retrieval.spherical_kmeans / DynamicIVFIndexer): the C ABI, and the host logic with the numpy restatement
 (tests/kmeans_reference.py) standing in for the device operators."""
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -38,27 +35,18 @@ def _pad(a, E_pad=128):
 
 def test_symbols_are_declared_bound_and_the_abi_version_stays_4():
     from matchmaker_amd import _lib
+    from tests import abi
+    L = abi.assert_bound(SYMBOLS)
     header = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    for sym in SYMBOLS:
-        assert re.search(r"\b%s\(" % sym, header), sym
-        assert sym in _lib.SIGNATURES, sym
-    assert re.search(r"#define\s+MM_ABI_VERSION\s+4\b", header)
     for cite in ("faiss_indices.py:323-352, 401-428", "query_clusterer.py:218-221"):
         assert cite in header
-    from matchmaker_amd import build
-    build.build()
-    L = _lib.lib()                                     # binds every symbol of SIGNATURES: AttributeError if one is missing
     assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     assert L.mm_kmeans_segment_sum_workspace_bytes(5000, 3, 128) >= (5000 // 512) * 128 * 4
 
 
 def test_c_client_is_refused_before_anything_touches_the_device(tmp_path):
-    from matchmaker_amd import build
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "kmeans_client.c"
-    src.write_text(r"""
+    from tests import abi
+    abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -94,14 +82,7 @@ int main(void) {
   printf("kmeans c client ok\n");
   return 0;
 }
-""")
-    exe = tmp_path / "kmeans_client"
-    libdir = os.path.dirname(so)
-    r = subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", "-I", os.path.join(ROOT, "include"), str(src), "-o",
-                        str(exe), "-L", libdir, "-l:libmm_native.so", f"-Wl,-rpath,{libdir}"], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, (r.returncode, r.stdout, r.stderr)
+""", name="kmeans_client")
 
 
 def test_ops_refuse_cpu_tensors_mixed_dtypes_and_wrong_shapes():

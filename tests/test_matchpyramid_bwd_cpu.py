@@ -5,7 +5,6 @@ each other: the given-arg-max form fed torch's own return_indices IS the module'
 inputs of the direct comparison are decided (every strict gap above twice the forward tolerance) before the GPU test uses
 them."""
 import ctypes
-import os
 
 import pytest
 import torch
@@ -13,7 +12,6 @@ import torch
 from tests import matchpyramid_bwd_reference as BR
 from tests import matchpyramid_reference as MR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mm_matchpyramid_fwd_save_workspace_bytes", "mm_matchpyramid_fwd_save", "mm_matchpyramid_bwd_workspace_bytes",
        "mm_matchpyramid_bwd")
 
@@ -25,12 +23,9 @@ def _arr(channels, kernels, pools):
 
 def test_new_symbols_are_declared_bound_and_exported_and_the_abi_version_stays():
     from matchmaker_amd import _lib
-    header = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    for sym in NEW:
-        assert sym + "(" in header and sym in _lib.SIGNATURES
-    assert "#define MM_ABI_VERSION 4" in header and _lib.ABI_VERSION == 4
-    L = _lib.lib()                               # resolves every symbol
-    assert L.mm_abi_version() == 4
+    from tests import abi
+    L = abi.assert_bound(NEW)
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     arr = _arr(*MR.DEFAULT)
     one = L.mm_matchpyramid_bwd_workspace_bytes(1, 30, 200, 5, arr)
     assert 0 < one < 4 << 20

@@ -5,8 +5,6 @@ refusals that come before any launch, and the fake rule of torch.ops.mm_native.s
 import importlib.util
 import os
 import re
-import shutil
-import subprocess
 import warnings
 
 import numpy as np
@@ -16,7 +14,7 @@ import torch
 from tests import rank_metrics_reference as RR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = {"mm_segment_rank_fwd": 8, "mm_rank_metrics_fwd": 22, "mm_rank_metrics_depth_fwd": 22}
+SYMBOLS = ("mm_segment_rank_fwd", "mm_rank_metrics_fwd", "mm_rank_metrics_depth_fwd")
 
 
 def _same(a, b):
@@ -196,14 +194,10 @@ def test_value_errors_segment_longer_than_hi_and_zero_evaluated_queries():
 # ---- header, binding, refusals -----------------------------------------------------------------------------------------------
 def test_symbols_are_declared_bound_and_exported_and_the_abi_version_stays_4():
     from matchmaker_amd import build, _lib
-    build.build()
-    L = _lib.lib()
+    from tests import abi
+    L = abi.assert_bound(SYMBOLS)
     hdr = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    for name, n_args in SYMBOLS.items():
-        m = re.search(r"\bint " + name + r"\(([^;]*?)\);", hdr, re.S)
-        assert m, name
-        assert m.group(1).count(",") + 1 == len(_lib.SIGNATURES[name][1]) == n_args, name
-        assert hasattr(L, name)
+    for name in SYMBOLS:
         assert re.search(name + r" \(additive: MM_ABI_VERSION unchanged\)\s+\* Replaces: .*core_metrics\.py:\d+", hdr), name
     assert L.mm_abi_version() == 4 == _lib.ABI_VERSION and "#define MM_ABI_VERSION 4" in hdr
     assert "rank_metrics.hip" in build.SOURCES and os.path.exists(os.path.join(build.CSRC, "rank_metrics.hip"))
@@ -214,12 +208,8 @@ def test_symbols_are_declared_bound_and_exported_and_the_abi_version_stays_4():
 
 
 def test_header_compiles_as_c_and_a_c_client_is_refused_before_any_launch(tmp_path):
-    from matchmaker_amd import build
-    so = build.build()
-    gcc = shutil.which("gcc")
-    assert gcc, "gcc is part of the image"
-    src = tmp_path / "client.c"
-    src.write_text(r"""
+    from tests import abi
+    abi.run_c_client(tmp_path, r"""
 #include <stdio.h>
 #include <string.h>
 #include "mm_native.h"
@@ -251,11 +241,6 @@ int main(void) {
   return 0;
 }
 """)
-    exe = tmp_path / "client"
-    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe),
-                    "-L", os.path.dirname(so), "-lmm_native", "-Wl,-rpath," + os.path.dirname(so)], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert out.returncode == 0, (out.returncode, out.stdout, out.stderr)
 
 
 def test_python_refusals_come_before_any_launch():

@@ -3,7 +3,6 @@ the C ABI and its binding, the argument checks, the nibble layout, the restateme
 float64 on the inputs tests/test_scann_gpu.py uses, and the indexer's host logic with the numpy restatement
 (tests/scann_reference.py) standing in for the device operators."""
 import os
-import re
 import socket
 
 import numpy as np
@@ -15,7 +14,6 @@ import torch.multiprocessing as mp
 from tests import ivf_reference as IR
 from tests import scann_reference as SR
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("mm_ah_encode", "mm_ah_scan_workspace_bytes", "mm_ah_scan_fwd", "mm_gather_dot")
 
 
@@ -42,17 +40,11 @@ def _padded16(a, E_pad=128):
 
 def test_symbols_are_declared_bound_and_exported_and_the_abi_version_stays_4():
     from matchmaker_amd import build, _lib
-    header = open(os.path.join(ROOT, "include", "mm_native.h")).read()
-    for name in SYMBOLS:
-        assert re.search(r"\b" + name + r"\s*\(", header), name
-        assert name in _lib.SIGNATURES, name
-    assert re.search(r"#define MM_ABI_VERSION 4\b", header) and _lib.ABI_VERSION == 4
-    assert [len(_lib.SIGNATURES[s][1]) for s in SYMBOLS] == [12, 5, 18, 10]
+    from tests import abi
+    L = abi.assert_bound(SYMBOLS)
     assert "ah_scan.hip" in build.SOURCES and "ah_encode.hip" in build.SOURCES
     assert any(h.endswith("ivf_device.h") for h in build.HEADERS)          # the shared scan scaffolding triggers rebuilds
-    build.build()
-    L = _lib.lib()                                     # binds every symbol of SIGNATURES: AttributeError if one is missing
-    assert L.mm_abi_version() == 4
+    assert L.mm_abi_version() == 4 == _lib.ABI_VERSION
     # the scan's workspace is the IVF scan's
     assert L.mm_ah_scan_workspace_bytes(1000, 10, 7, 3, 10) == L.mm_ivf_scan_workspace_bytes(1000, 10, 7, 3, 10) > 7000 * 4
     assert L.mm_ah_scan_workspace_bytes(1000, 0, 7, 3, 10) == 0
