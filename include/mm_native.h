@@ -527,7 +527,8 @@ int mm_kmeans_segment_sum(const void* x, const int64_t* order, const int64_t* li
  *   This is coordinate descent on L = sum_s |e_s|^2 + (eta - 1) (sum_s <e_s, xhat_s>)^2 with the other
  *   blocks' parallel error held fixed; eta = 1 or passes = 0 is plain nearest-codeword quantisation.
  *   eta finite and >= 0, 0 <= passes <= 64.  The result is a pure function of the inputs: no atomics,
- *   one launch on `stream`, no workspace: graph-capturable.  n = 0 succeeds without a launch.
+ *   one launch on `stream`, no workspace: graph-capturable.  n = 0 succeeds without a launch; n < 2^35 (one workgroup
+ *   per 16 rows; more returns MM_EUNSUPPORTED before any launch).
  *
  * mm_ah_scan_fwd                                            scann_index.py:44 (search_batched, AH stage)
  *   queries [nq, E]; codes stored list by list as the vectors of mm_ivf_scan_fwd are (list_begin
@@ -839,7 +840,9 @@ int mm_colbert_candidates(const int64_t* hit_rows, const int64_t* doc_begin_sort
  *
  * mm_fp8_quantize_rows: x [n_rows, E] of `dtype` (MM_F32 / MM_F16 / MM_BF16) -> codes, scales.  One 16-lane group per row:
  *   row maximum, then convert and store.  No atomics, every output byte is written, two calls give the same bits.
- *   E % 16 != 0 returns MM_EUNSUPPORTED; x and codes 16-byte aligned; n_rows = 0 succeeds.
+ *   E % 16 != 0 returns MM_EUNSUPPORTED; x and codes 16-byte aligned; n_rows = 0 succeeds.  n_rows <= 2^35 - 16 (one
+ *   workgroup per 16 rows, at most 2^31 - 1 of them; more returns MM_EUNSUPPORTED before any launch); every offset is
+ *   64-bit, so the input and the codes may cross 2^32 bytes.
  *
  * mm_maxsim_ragged_fp8_fwd: mm_maxsim_ragged_fwd over such a store,
  *     out[p] = sum_{i, q_mask} max_{t in [doc_begin[p], doc_end[p])} ( scales[t] * sum_k q[i,k] * deq(codes[t,k]) )

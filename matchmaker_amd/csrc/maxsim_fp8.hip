@@ -320,7 +320,7 @@ extern "C" int mm_fp8_quantize_rows(const void* x, int64_t n_rows, int E, int dt
   if ((((uintptr_t)x | (uintptr_t)codes) & 15) || ((uintptr_t)scales & 3))
     return set_error(MM_EINVAL, "fp8_quantize_rows: x / codes must be 16-byte aligned, scales 4-byte aligned");
   const int64_t blocks = (n_rows + 15) / 16;
-  if (blocks > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "fp8_quantize_rows: more than 2^35 rows in one launch");
+  if (blocks > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "fp8_quantize_rows: more than 2^35 - 16 rows in one launch");
   const dim3 grid((unsigned)blocks), block(256);
   if (dtype == MM_F32) hipLaunchKernelGGL(fp8_quantize_rows_kernel<MM_F32>, grid, block, 0, stream, x, n_rows, E, codes, scales);
   else if (dtype == MM_F16) hipLaunchKernelGGL(fp8_quantize_rows_kernel<MM_F16>, grid, block, 0, stream, x, n_rows, E, codes, scales);
