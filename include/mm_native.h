@@ -941,7 +941,8 @@ int mm_ivf_scan_fp8_fwd(const void* queries, const uint8_t* codes, const float* 
  *     (one copy of the device code serves both).  Either output or both may be given; neither returns MM_EINVAL.
  *   Capacity is all or nothing per batch: if fill_in + kept > capacity the call writes no row and no doc_begin / doc_end,
  *   leaves fill[0] unchanged and sets status[0] = 1.  status is sticky: when it is non-zero on entry the call does nothing.
- *   No store uses a row index >= capacity, no load reads outside x.
+ *   No store uses a row index >= capacity, no load reads outside x.  Store rows below fill_in and from the new fill[0] on are
+ *   left as they were (rows_out, codes_out and scales_out alike): the call owns rows fill_in .. fill_in + kept - 1 only.
  *   fill [1] int64, status [1] int32, doc_begin / doc_end [n_docs] int64 are DEVICE memory: appends chain through fill with
  *   no read-back.  Three launches on `stream` (row flags by wavefront ballot; a one-workgroup scan with the capacity test;
  *   scatter), no allocation, no host synchronisation, no atomics and no workgroup waiting on another: graph-capturable as a

@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256) kernel_pool_bwd_kernel(const KpBwdArgs a,
 // 1.12 ms for 2,048 pairs, 17 % VALU utilisation — every FMA needed its operands from LDS.)
 // Two forms: 1,024 threads (sixteen wavefronts, <= 128 registers: one column tile per wavefront, twice the wavefronts to
 // hide the phases' latencies; 0.79 ms for 2,048 pairs) when its 8 partial-tile slots fit the LDS, else 512 threads (0.85 ms).
-// The document is read from HBM/L2 twice and its gradient written once.  Q <= 32, E <= 384 (16-byte rows), K <= 16, LDS
+// The document is read from HBM/L2 twice and its gradient written once.  Q <= 32, E <= 512 (16-byte rows), K <= 16, LDS
 // permitting; everything else takes the kernel above.
 // ---------------------------------------------------------------------------------------------
 constexpr int kTK = 16;
@@ -711,7 +711,7 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
   if (n_pairs == 0) return MM_OK;
   if (n_pairs > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "kernel_pool_bwd: too many pairs for one launch");
   // The split-bf16 streaming kernel (kernel_pool_bwd_split.hip) for every shape the reference's configs train at (Q <= 32,
-  // 11 kernels, E <= 384); MM_KP_BWD_F32=1 keeps the exact-f32 tiled kernel below as its parity twin (A/B runs).
+  // 11 kernels, E <= 320: kp_bwd_split_supported); MM_KP_BWD_F32=1 keeps the exact-f32 tiled kernel below as its parity twin (A/B runs).
   if (kp_bwd_split_supported(Q, E, K) && !env().kp_bwd_f32 && !env().kp_bwd_untiled &&
       !(((uintptr_t)q | (uintptr_t)d | (uintptr_t)grad_q | (uintptr_t)grad_d) & 15)) {
     KpBwdArgs a{};

@@ -41,7 +41,7 @@ __device__ __forceinline__ bool mask_bit(const PackedMask& m, int64_t row, int w
 
 __device__ __forceinline__ constexpr int mrow(int i) { return (i & 3) + 8 * (i >> 2); }   // C/D layout of the 32x32 MFMA: acc[i] of lane l = row mrow(i) + 4 (l >> 5), column l & 31
 
-// kernel_pool_bwd_split.hip: Q <= 32, K = 11, E = 4n <= 384.  pkq_in: the forward's pooled kernel sums [n_pairs, Q, K]
+// kernel_pool_bwd_split.hip: Q <= 32, K = 11, E = 4n <= 320 (kp_bwd_split_supported).  pkq_in: the forward's pooled kernel sums [n_pairs, Q, K]
 // (NULL: a pooling pre-pass of the same kernel writes them to pkq_ws first — the document then crosses HBM twice).
 bool kp_bwd_split_supported(int Q, int E, int K);
 size_t kp_bwd_split_ws_bytes(int64_t n_pairs, int Q, int K);
