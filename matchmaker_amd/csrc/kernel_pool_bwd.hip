@@ -24,8 +24,10 @@
 // device without a [B,Q,D,K] tensor.  Pair-per-row layout (the one train.py feeds: neuralIR_encoder.py:86-87).
 #include "mm_internal.h"
 #include "kp_bwd.h"
+#include "bwd_tiled_device.h"
 
 namespace mm {
+using namespace bwd_tiled;
 
 // LDS: cosine + gradient tiles [Q][DT] (DT document positions at a time) + per-pair vectors.  Documents longer than
 // one tile (max_doc_length 2000 in tk.yaml-style training configs) take two sweeps over their tiles: the first pools
@@ -228,13 +230,8 @@ __global__ void __launch_bounds__(256) kernel_pool_bwd_kernel(const KpBwdArgs a,
 // one dependent load per FMA: 1.5-2 ms per PAIR (bench.py extra.train_step, round 4: 16.6 ms for 2,048 pairs, 2.4 x
 // slower than torch's eager ops on the same GPU).  Here: the normalised query tile [Q][E] and one 32-row document block
 // live in LDS, the cosines of the whole document stay in LDS between the two sweeps (pooled sums need every position
-// before any gradient can be formed).  Per 32-row block the eight wavefronts of the workgroup
-//   * cosines: split K = E between them (wavefront w takes the 32-byte chunk pairs w, w + 8, ...: A = document rows,
-//     B = query tokens, both read as 16 bytes per lane and four MFMA steps), the eight partial 32 x 32 tiles meet in LDS;
-//   * grad_d block [32 rows x E]: wavefront w owns the 32-column tiles w, w + 8 of E; K = query tokens (A = G[row][token],
-//     B = Qh[token][column]: consecutive lanes read consecutive floats);
-//   * grad_q [Q x E]: the same column tiles, K = the block's 32 rows (A = G[token][row] / (|d_row| + tiny), B = the raw
-//     document block), accumulated in registers across the blocks.
+// before any gradient can be formed).  The three products of a 32-row block, the staging of the block and the norms are the
+// phases of bwd_tiled_device.h (shared with TKL's backward, tkl_bwd.hip); the pooling, the log and G in between are this kernel's.
 // (The first version of this kernel ran the three products as register-blocked VALU FMAs out of the same LDS tiles:
 // 1.12 ms for 2,048 pairs, 17 % VALU utilisation — every FMA needed its operands from LDS.)
 // Two forms: 1,024 threads (sixteen wavefronts, <= 128 registers: one column tile per wavefront, twice the wavefronts to
@@ -245,37 +242,11 @@ __global__ void __launch_bounds__(256) kernel_pool_bwd_kernel(const KpBwdArgs a,
 constexpr int kTK = 16;
 constexpr int kTT = 512;   // threads of the tiled kernel's smaller form (eight wavefronts, two per SIMD, around ONE set of LDS tiles per CU); the default form has 1,024
 
-// Row stride of the [row][E] tiles in floats: an ODD number of 16-byte units, so that the sixteen lanes of a ds_read_b128
-// phase that read one column chunk of sixteen consecutive rows (the A / B operands of the cosine MFMAs) cover all 64 banks.
-// (E + 4 alone is even for E = 300: 304 floats = 48 banks apart, rows r and r + 4 on the same banks, 8-way conflicts.)
-__host__ __device__ inline int kp_bwd_row_stride(int E) { return ((E >> 2) & 1) ? E + 8 : E + 4; }
-
 __host__ __device__ inline size_t kp_bwd_tiled_lds_bytes(int Q, int E, int Dpad, int nthr = 512) {
-  const int ES = kp_bwd_row_stride(E), QS = (Q + 3) & ~3;
+  const int ES = row_stride(E), QS = (Q + 3) & ~3;
   return ((size_t)Q * ES + 32 * (size_t)ES + (size_t)Dpad * QS + 3 * 32 * (size_t)QS + 2 * (size_t)Q * kTK + 4 * (size_t)Dpad +
           5 * 32 + 4 * kTK + (nthr / 128) * 1024) * 4;
 }
-
-
-__device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
-// Phase clocks (tools/build_variant.sh phases kernel_pool_bwd -DMM_KP_BWD_PHASE_TIMES=1; tools/bench_kp_bwd_phases.py): thread 0
-// of every pair sums s_memtime deltas per phase and pair 0 overwrites its grad_w / grad_alpha rows with them.
-#ifndef MM_KP_BWD_PHASE_TIMES
-#define MM_KP_BWD_PHASE_TIMES 0
-#endif
-// KP_KEEP16(v): the sixteen values are computed HERE.  Without it the compiler sinks each value's LDS reads and arithmetic
-// into the lane-conditional block of the store that uses it: per store two dependent LDS round trips behind a branch.  (One
-// statement for all sixteen: a volatile asm per value orders them and serialises the reads just the same — both measured, 35 %
-// and 17 % of the kernel.)
-#define KP_KEEP16(v)                                                                                                          \
-  asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), \
-               "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]))
-#if MM_KP_BWD_PHASE_TIMES
-#define KP_PH(k) do { const long long t_ = clock64(); ph[k] += (float)(t_ - t_last); t_last = t_; } while (0)
-#else
-#define KP_PH(k) do { } while (0)
-#endif
 
 template <bool GATE, int kLB, int NTHR>   // kLB: 16-byte chunks of a document block per thread = ceil(32 (E / 4) / NTHR)
 __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwdArgs a, const int Dpad) {
@@ -287,7 +258,7 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
   const int tid = threadIdx.x;
   const int64_t pair = blockIdx.x;
   const int Q = a.Q, D = a.D, E = a.E, K = a.K;
-  const int ES = kp_bwd_row_stride(E), QS = (Q + 3) & ~3, NC = E >> 2;
+  const int ES = row_stride(E), QS = (Q + 3) & ~3, NC = E >> 2;
   float* QH = (float*)smem;          // [Q][ES]    q_i / (|q_i| + tiny)
   float* DB = QH + Q * ES;           // [32][ES]   the current document block (raw rows)
   float* CT = DB + 32 * ES;          // [Dpad][QS] cosines of the whole document, [position][query token]
@@ -321,11 +292,8 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
 #endif
 
   // ---- query tile, constants ---------------------------------------------------------------------------------
-  for (int idx = tid; idx < Q * NC; idx += NTHR) {
-    const int i = idx / NC, c = idx - i * NC;
-    *(f32x4*)(QH + i * ES + 4 * c) = *(const f32x4*)(qb + (int64_t)i * E + 4 * c);
-  }
-  if (tid < kTK) {                                      // (entries past K are zeros: the G loop runs in fours)
+  load_query_rows<NTHR>(QH, qb, Q, NC, E, ES, tid);
+  if (tid < kTK) {                                   // (entries past K are zeros: the G loop runs in fours)
     f32x4 kp = {0.0f, 0.0f, 0.0f, 0.0f};
     if (tid < K) {
       const float sg = a.sigma[tid];
@@ -338,22 +306,10 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
   __syncthreads();
   if (tid < 512) {  // norms: sixteen threads per query token; the tile is stored normalised
     const int i = tid >> 4, sub = tid & 15;
-    float ss = 0.0f;
-    if (i < Q)
-      for (int c = sub; c < NC; c += 16) {
-        const f32x4 v = *(const f32x4*)(QH + i * ES + 4 * c);
-        ss += dot4(v, v);
-      }
-    ss += __shfl_xor(ss, 1, 64);
-    ss += __shfl_xor(ss, 2, 64);
-    ss += __shfl_xor(ss, 4, 64);
-    ss += __shfl_xor(ss, 8, 64);
+    const float ss = row_sumsq16(QH + i * ES, i < Q ? NC : 0, sub);
     const float n = sqrtf(ss), r = 1.0f / (n + 1e-13f);
     if (i < Q) {
-      for (int c = sub; c < NC; c += 16) {
-        f32x4* p = (f32x4*)(QH + i * ES + 4 * c);
-        *p = *p * r;
-      }
+      scale_row16(QH + i * ES, NC, sub, r);
       if (sub == 0) {
         nq[i] = n;
         rq[i] = r;
@@ -363,22 +319,9 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
   }
   __syncthreads();
 
-  // A document block travels global -> registers -> LDS in two steps: fetch() issues every load of a thread's share at
-  // once (kLB <= 8 chunks of 16 bytes) and is called one block AHEAD, right after the barrier that opens the
-  // current block's arithmetic; commit() stores them to DB once that arithmetic has read the current block.  With one
-  // workgroup per CU nothing else hides the load latency: issued at the point of use (round 4's first version) it was half
-  // of the kernel's time.  A thread's chunks are the same (row, column) in every block.
+  // A document block travels global -> registers -> LDS one block ahead (bwd_tiled_device.h, staging)
   int frow[kLB], fcol[kLB];
-#pragma unroll
-  for (int u = 0; u < kLB; ++u) {
-    const int idx = tid + u * NTHR;
-    frow[u] = 32;
-    fcol[u] = 0;
-    if (idx < 32 * NC) {
-      frow[u] = idx / NC;
-      fcol[u] = 4 * (idx - frow[u] * NC);
-    }
-  }
+  stage_plan<kLB, NTHR>(tid, NC, frow, fcol);
   f32x4 nxt[kLB];
   auto fetch = [&](int j0) {
     const int nj = D - j0 < 32 ? D - j0 : 32;
@@ -388,33 +331,21 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
       if (frow[u] < nj) nxt[u] = *(const f32x4*)(db + (uint32_t)((j0 + frow[u]) * E + fcol[u]));
     }
   };
-  auto commit = [&]() {
-#pragma unroll
-    for (int u = 0; u < kLB; ++u)
-      if (frow[u] < 32) *(f32x4*)(DB + frow[u] * ES + fcol[u]) = nxt[u];
-  };
+  auto commit = [&]() { stage_commit<kLB>(DB, ES, frow, fcol, nxt); };
   int dlen = a.dm.len ? a.dm.len[pair] : D;
   dlen = dlen < D ? dlen : D;
 
   // ---- sweep 1: cosines of every block, pooled kernels ---------------------------------------------------------
   fetch(0);
-  KP_PH(0);
+  BWD_PH(0);
   for (int j0 = 0; j0 < D; j0 += 32) {
     const int nj = D - j0 < 32 ? D - j0 : 32;
     commit();
     __syncthreads();
-    KP_PH(1);
+    BWD_PH(1);
     if (tid < 512) {  // row norms and masks: sixteen threads per row (whole wavefronts)
       const int row = tid >> 4, sub = tid & 15;
-      float ss = 0.0f;
-      for (int c = sub; c < NC; c += 16) {
-        const f32x4 v = *(const f32x4*)(DB + row * ES + 4 * c);
-        ss += dot4(v, v);
-      }
-      ss += __shfl_xor(ss, 1, 64);
-      ss += __shfl_xor(ss, 2, 64);
-      ss += __shfl_xor(ss, 4, 64);
-      ss += __shfl_xor(ss, 8, 64);
+      const float ss = row_sumsq16(DB + row * ES, NC, sub);
       if (sub == 0) {
         const float n = sqrtf(ss);
         const int j = j0 + row;
@@ -429,43 +360,18 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
       }
     }
     __syncthreads();
-    KP_PH(2);
+    BWD_PH(2);
     fetch(j0 + 32 < D ? j0 + 32 : 0);                   // the next block, or sweep 2's first
-    {  // cosine tile: this wavefront's K slice of the 32 x 32 tile; the eight partial tiles meet in LDS in a fixed order
-      f32x16 acc = {0};
-      const float* arow = DB + ln * ES;
-      const float* brow = QH + (ln < Q ? ln : Q - 1) * ES;
-      for (int p = wv; 2 * p < NC; p += NW) {
-        const int cc = 2 * p + lh;
-        const int cl = cc < NC ? cc : NC - 1;            // (odd NC: the last pair's upper half multiplies zeros)
-        f32x4 av = *(const f32x4*)(arow + 4 * cl);
-        const f32x4 bv = *(const f32x4*)(brow + 4 * cl);
-        if (cc >= NC) av = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-      }
-      float* ps = PS + (wv % NS) * 1024 + 4 * lh * 32 + ln;
-      if (wv >= NS) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ps[mrow(i) * 32] = acc[i];
-      }
-      __syncthreads();
-      if (wv < NS) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ps[mrow(i) * 32] += acc[i];
-      }
-    }
+    cosine_partials<NW>(DB, QH, PS, Q, NC, ES, wv, ln, lh);   // (one barrier inside)
     __syncthreads();
-    KP_PH(3);
+    BWD_PH(3);
     for (int idx = tid; idx < 1024; idx += NTHR) {
       const int row = idx >> 5, i = idx & 31;
-      float v = PS[idx];
-#pragma unroll
-      for (int w = 1; w < NS; ++w) v += PS[w * 1024 + idx];
+      const float v = partial_sum<NS>(PS, idx);
       if (i < Q) CT[(j0 + row) * QS + i] = v * RD[j0 + row];
     }
     __syncthreads();
-    KP_PH(4);
+    BWD_PH(4);
     for (int idx = tid / PP; idx < Q * K; idx += NTHR / PP) {   // (i, k): PP threads, 32 / PP positions each; owned across the blocks
       const int i = idx / K, k = idx - i * K;
       const float mu = kc[4 * k], c2 = kc[4 * k + 1];
@@ -481,7 +387,7 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
       if (!(tid % PP)) PK[i * kTK + k] += pk;
     }
     __syncthreads();
-    KP_PH(5);
+    BWD_PH(5);
   }
 
   // ---- A_ik and the parameter gradients of this pair -----------------------------------------------------------
@@ -506,10 +412,8 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
   }
   __syncthreads();
 
-  KP_PH(6);
+  BWD_PH(6);
   // ---- sweep 2: G per block, grad_d (complete per block), grad_q (register accumulators across the blocks) -------
-  // Everything the matrix pipe is fed with is read unconditionally (clamped addresses, zeros selected afterwards): a
-  // conditional LDS read in front of an MFMA becomes a branch, a wait and an exposed latency per step.
   const int NT = (E + 31) >> 5;                         // 32-column tiles of E; wavefront w owns tiles w and w + 8
   const int KQ = (Q + 1) >> 1;                          // MFMA steps over the query tokens
   f32x16 accq[TPW];
@@ -545,7 +449,7 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
       }
     }
     __syncthreads();
-    KP_PH(7);
+    BWD_PH(7);
     if (tid < 512) {  // sixteen threads per row / per query token, two terms each (whole wavefronts)
       const int r16 = tid >> 4, sub = tid & 15;
       float s = 0.0f, u = 0.0f, sgs = 0.0f;
@@ -569,107 +473,55 @@ __global__ void __launch_bounds__(NTHR) kernel_pool_bwd_tiled_kernel(const KpBwd
       }
     }
     __syncthreads();
-    KP_PH(8);
+    BWD_PH(8);
     // (lane coordinates behind an opaque copy: the ~80 per-lane LDS addresses derived from them below are then computed
     // here, per block, instead of once before the loop and kept in registers the 1,024-thread form does not have)
     int lq = ln, hq = lh;
     asm volatile("" : "+v"(lq), "+v"(hq));
     {  // grad_d of the block: A[row][token] = G (K = tokens, two per step; zero past Q), shared by this wavefront's tiles
       float ga[16];
-#pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int i = 2 * st + hq;
-        ga[st] = GJ[lq * QS + (i < QS ? i : QS - 1)];
-        if (i >= Q) ga[st] = 0.0f;
-      }
+      grad_d_operand(ga, GJ, Q, QS, lq, hq);
 #pragma unroll
       for (int t = 0; t < TPW; ++t) {
         const int nt = wv + NW * t;
         if (nt >= NT) break;                             // wave-uniform
         const int col = 32 * nt + lq;
         const bool cin = col < E;
-        const float* qcol = QH + (cin ? col : 0);
         const float* dcol = DB + (cin ? col : 0);
-        float bq[16];
-#pragma unroll
-        for (int st = 0; st < 16; ++st) {
-          const int i = 2 * st + hq;
-          bq[st] = qcol[(i < Q ? i : Q - 1) * ES];       // (multiplied by ga = 0 past Q)
-        }
-        f32x16 acc = {0};
-#pragma unroll
-        for (int g2 = 0; g2 < 8; ++g2) {
-          if (2 * g2 < KQ) {                             // wave-uniform
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[2 * g2], bq[2 * g2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[2 * g2 + 1], bq[2 * g2 + 1], acc, 0, 0, 0);
-          }
-        }
+        const f32x16 acc = grad_d_tile(ga, QH + (cin ? col : 0), Q, KQ, ES, hq);
         const uint32_t o0 = (uint32_t)((j0 + 4 * hq) * E + col);
         float ov[16];
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int row = mrow(i) + 4 * hq;
+          const int row = rowof(i) + 4 * hq;
           ov[i] = (acc[i] - dcol[row * ES] * td[row]) * RD[j0 + row];
         }
         if (nj == 32) {                                  // wave-uniform: a full block stores under ONE lane mask (the tile's columns < E)
           if (cin) {
 #pragma unroll
-            for (int i = 0; i < 16; ++i) gd[o0 + (uint32_t)(mrow(i) * E)] = ov[i];   // 128-byte row segments per store
+            for (int i = 0; i < 16; ++i) gd[o0 + (uint32_t)(rowof(i) * E)] = ov[i];   // 128-byte row segments per store
           }
         } else {
-          KP_KEEP16(ov);
+          BWD_KEEP16(ov);
 #pragma unroll
           for (int i = 0; i < 16; ++i)
-            if (cin && mrow(i) + 4 * hq < nj) gd[o0 + (uint32_t)(mrow(i) * E)] = ov[i];
+            if (cin && rowof(i) + 4 * hq < nj) gd[o0 + (uint32_t)(rowof(i) * E)] = ov[i];
         }
       }
     }
-    KP_PH(9);
-    {  // grad_q: A[token][row] = G / (|d_row| + tiny) (K = the block's rows), B = the raw document block
-      float gi[16];
-      const int tk = lq < Q ? lq : Q - 1;
-#pragma unroll
-      for (int st = 0; st < 16; ++st) {
-        const int i = 2 * st + hq;
-        gi[st] = GI[tk * 32 + i] * RD[j0 + i];
-        if (lq >= Q) gi[st] = 0.0f;
-      }
-#pragma unroll
-      for (int t = 0; t < TPW; ++t) {
-        const int nt = wv + NW * t;
-        if (nt >= NT) break;
-        const int col = 32 * nt + lq;
-        const float* dcol = DB + (col < E ? col : 0);
-        float bd[16];
-#pragma unroll
-        for (int st = 0; st < 16; ++st) bd[st] = dcol[(2 * st + hq) * ES];
-#pragma unroll
-        for (int st = 0; st < 16; ++st) accq[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(gi[st], bd[st], accq[t], 0, 0, 0);
-      }
-    }
+    BWD_PH(9);
+    grad_q_accumulate<NW, TPW>(accq, GI, RD + j0, DB, Q, E, ES, NT, wv, lq, hq);
     __syncthreads();
-    KP_PH(10);
+    BWD_PH(10);
   }
 #pragma unroll
   for (int t = 0; t < TPW; ++t) {
     const int nt = wv + NW * t;
     const int col = 32 * nt + ln;
-    if (nt < NT && col < E) {
-      float ov[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int tok = mrow(i) + 4 * lh, tc = tok < Q ? tok : Q - 1;
-        const float self = nq[tc] > 0.0f ? sq[tc] : 0.0f;            // QH holds q_i / |q_i| (to 1e-13)
-        ov[i] = (accq[t][i] - QH[tc * ES + col] * self) * rq[tc];
-      }
-      KP_KEEP16(ov);
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (mrow(i) + 4 * lh < Q) gq[(uint32_t)((mrow(i) + 4 * lh) * E + col)] = ov[i];
-    }
+    if (nt < NT && col < E) grad_q_store_tile(accq[t], QH, nq, sq, rq, gq, Q, E, ES, col, lh, [](float v, int) { return v; });
   }
 #if MM_KP_BWD_PHASE_TIMES
-  KP_PH(11);
+  BWD_PH(11);
   __syncthreads();
   if (tid == 0 && pair == 0)
     for (int k = 0; k < 12; ++k) (k < K ? a.gw[k] : a.galpha[k - K]) = ph[k];
@@ -710,16 +562,16 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
   if (K > kBK) return set_error(MM_EUNSUPPORTED, "kernel_pool_bwd: K=%d kernels (max %d)", K, kBK);
   if (n_pairs == 0) return MM_OK;
   if (n_pairs > 0x7fffffffLL) return set_error(MM_EUNSUPPORTED, "kernel_pool_bwd: too many pairs for one launch");
+  KpBwdArgs a{};
+  a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
+  a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
+  a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
+  WsCursor ws(workspace, workspace_bytes);
+  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   // The split-bf16 streaming kernel (kernel_pool_bwd_split.hip) for every shape the reference's configs train at (Q <= 32,
   // 11 kernels, E <= 320: kp_bwd_split_supported); MM_KP_BWD_F32=1 keeps the exact-f32 tiled kernel below as its parity twin (A/B runs).
   if (kp_bwd_split_supported(Q, E, K) && !env().kp_bwd_f32 && !env().kp_bwd_untiled &&
       !(((uintptr_t)q | (uintptr_t)d | (uintptr_t)grad_q | (uintptr_t)grad_d) & 15)) {
-    KpBwdArgs a{};
-    a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
-    a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
-    a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-    WsCursor ws(workspace, workspace_bytes);
-    if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
     float* pkq_ws = nullptr;
     if (!pooled) {
       const size_t skip = (size_t)(-(intptr_t)ws.p) & 255, need = kp_bwd_split_ws_bytes(n_pairs, Q, K);
@@ -741,12 +593,6 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
     const size_t tl = kp_bwd_tiled_lds_bytes(Q, E, Dpad, nthr);
     if (Q <= 32 && !(E & 3) && E <= 512 && K <= kTK && tl <= 150 * 1024 &&
         !(((uintptr_t)q | (uintptr_t)d | (uintptr_t)grad_q | (uintptr_t)grad_d) & 15) && !env().kp_bwd_untiled) {
-      KpBwdArgs a{};
-      a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
-      a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
-      a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-      WsCursor ws(workspace, workspace_bytes);
-      if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
       auto go = [&](auto kern) {
         if (tl > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl);
         hipLaunchKernelGGL(kern, dim3((unsigned)n_pairs), dim3((unsigned)nthr), tl, stream, a, Dpad);
@@ -773,12 +619,6 @@ extern "C" int mm_kernel_pool_ex_bwd2(const void* q, const void* d, const void* 
     DT = (int)((150 * 1024 - fixed) / ((size_t)(2 * Q + 5) * 4)) & ~31;
   }
   const size_t lds = kp_bwd_lds_bytes(Q, DT);
-  KpBwdArgs a{};
-  a.q = (const float*)q; a.d = (const float*)d; a.mu = mu; a.sigma = sigma; a.alpha = alpha; a.w = w; a.go = grad_out;
-  a.dw = d_gate; a.gdw = grad_gate; a.clamp_min = clamp_min;
-  a.gq = grad_q; a.gd = grad_d; a.galpha = grad_alpha; a.gw = grad_w; a.n_pairs = n_pairs; a.Q = Q; a.D = D; a.E = E; a.K = K;
-  WsCursor ws(workspace, workspace_bytes);
-  if (int e = resolve_mask_pair(q_mask, q_mask_kind, n_pairs, Q, &a.qm, d_mask, d_mask_kind, n_pairs, D, &a.dm, ws, stream)) return e;
   if (lds > 64 * 1024)
     (void)hipFuncSetAttribute((const void*)kernel_pool_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(kernel_pool_bwd_kernel, dim3((unsigned)n_pairs), dim3(256), lds, stream, a, DT);

@@ -39,8 +39,6 @@ __device__ __forceinline__ bool mask_bit(const PackedMask& m, int64_t row, int w
   return true;
 }
 
-__device__ __forceinline__ constexpr int mrow(int i) { return (i & 3) + 8 * (i >> 2); }   // C/D layout of the 32x32 MFMA: acc[i] of lane l = row mrow(i) + 4 (l >> 5), column l & 31
-
 // kernel_pool_bwd_split.hip: Q <= 32, K = 11, E = 4n <= 320 (kp_bwd_split_supported).  pkq_in: the forward's pooled kernel sums [n_pairs, Q, K]
 // (NULL: a pooling pre-pass of the same kernel writes them to pkq_ws first — the document then crosses HBM twice).
 bool kp_bwd_split_supported(int Q, int E, int K);

@@ -22,8 +22,10 @@
 // without atomics: deterministic.
 // tkl_bwd_tiled_kernel (below) is the product path; tkl_bwd_kernel (first) the general fallback for shapes its tiles do not fit.
 #include "mm_internal.h"
+#include "bwd_tiled_device.h"
 
 namespace mm {
+using namespace bwd_tiled;
 
 constexpr int kBwdT = 30;      // positions per window
 constexpr int kBwdQ = 32;      // query tokens held in LDS
@@ -374,9 +376,9 @@ __global__ void __launch_bounds__(kBwdThreads) tkl_bwd_kernel(const TklBwdArgs a
 // per FMA: 4.6 ms per DOCUMENT (bench.py extra.train_step: 22 ms for 2,048 documents, 24 x the forward).  Here, per
 // document (one 512-thread workgroup):
 //   * the normalised query tile and the 30 rows of the current window live in LDS; the three small products of a window
-//     (cosines, chunk-row gradients, query gradient) run on the matrix pipe in exact fp32 exactly as in
-//     kernel_pool_bwd_tiled_kernel (kernel_pool_bwd.hip: K split over the eight wavefronts for the cosines, 32-column tiles
-//     of E for the gradients); the query gradient accumulates in registers over the 15 windows;
+//     (cosines, chunk-row gradients, query gradient) run on the matrix pipe in exact fp32: the phases of bwd_tiled_device.h,
+//     shared with TK pooling's backward (kernel_pool_bwd.hip: K split over the eight wavefronts for the cosines, 32-column
+//     tiles of E for the gradients); the query gradient accumulates in registers over the 15 windows;
 //   * the 15 windows, their row tables (document position -> packed chunk row, two dependent global reads each) and masks are
 //     resolved ONCE, in parallel, before the window loop; the rows of window n + 1 are fetched into registers while window n
 //     is computed (one workgroup per CU: nothing else hides a load issued at its point of use);
@@ -388,31 +390,14 @@ __global__ void __launch_bounds__(kBwdThreads) tkl_bwd_kernel(const TklBwdArgs a
 // ---------------------------------------------------------------------------------------------
 constexpr int kKS = 12;        // row stride of the [token][kernel] tables (16-byte rows, the twelfth entry is zero)
 
-__host__ __device__ inline int tkl_bwd_row_stride(int E) { return ((E >> 2) & 1) ? E + 8 : E + 4; }   // odd number of 16-byte units
-
 __host__ __device__ inline size_t tkl_bwd_tiled_lds_bytes(int Wp, int Q, int E, int nthr = 512) {
-  const int ES = tkl_bwd_row_stride(E), QS = (Q + 3) & ~3;
+  const int ES = row_stride(E), QS = (Q + 3) & ~3;
   return ((size_t)Q * ES + 32 * (size_t)ES + 2 * 32 * (size_t)QS + 2 * kBwdQ * kKS + kBwdQ * 40 + 8 * kBwdQ + 4 * 32 + 16 + 4 * kKS +
           2 * kKS + 16 + (nthr / 128) * 1024 + 2 * 15 * 32 + 3 * 64 + 44 + 2 * 64 * (size_t)QS + 2 * (size_t)Wp) * 4 + 64;
 }
 
-__device__ __forceinline__ float dot4(const f32x4& a, const f32x4& b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-__device__ __forceinline__ constexpr int mrow(int i) { return (i & 3) + 8 * (i >> 2); }   // C/D layout of the 32x32 MFMA: acc[i] of lane l = row mrow(i) + 4 (l >> 5), column l & 31
-
-// Phase clocks (tools/build_variant.sh phases tkl_bwd -DMM_TKL_BWD_PHASE_TIMES=1): thread 0 of document 0 sums s_memtime
-// deltas per phase and overwrites the first entries of its parameter-gradient row with them.
-#ifndef MM_TKL_BWD_PHASE_TIMES
-#define MM_TKL_BWD_PHASE_TIMES 0
-#endif
-#if MM_TKL_BWD_PHASE_TIMES
-#define TKL_PH(k) do { const long long t_ = clock64(); ph[k] += (float)(t_ - t_last); t_last = t_; } while (0)
-#else
-#define TKL_PH(k) do { } while (0)
-#endif
+// (BWD_KEEP16 of bwd_tiled_device.h for the eight values of half a tile: the read-add-write below runs eight rows at a time)
 #define TKL_KEEP8(v) asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]))
-#define TKL_KEEP16(v)                                                                                                         \
-  asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), \
-               "+v"(v[9]), "+v"(v[10]), "+v"(v[11]), "+v"(v[12]), "+v"(v[13]), "+v"(v[14]), "+v"(v[15]))
 
 template <int kLB, int NTHR>   // kLB: 16-byte chunks of a window's rows per thread = ceil(32 (E / 4) / NTHR)
 __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a) {
@@ -440,7 +425,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
   const int ln = tid & 31, lh = (tid >> 5) & 1;          // MFMA lane coordinates within the wavefront
   const int C = a.C, Q = a.Q, E = a.E, W = a.W;
   const int Wp = W < 3 ? 3 : W;
-  const int ES = tkl_bwd_row_stride(E), QS = (Q + 3) & ~3, NC = E >> 2;
+  const int ES = row_stride(E), QS = (Q + 3) & ~3, NC = E >> 2;
   const float* prm = a.prm;
 
   float* QH = (float*)smem;                    // [Q][ES]  q_i / (|q_i| + tiny)
@@ -490,10 +475,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
 #endif
 
   // ---- query tile: raw rows -> norms, emb . q_i -> normalised in place; constants -----------------------------------
-  for (int idx = tid; idx < Q * NC; idx += NTHR) {
-    const int i = idx / NC, c = idx - i * NC;
-    *(f32x4*)(QH + i * ES + 4 * c) = *(const f32x4*)(qb + (int64_t)i * E + 4 * c);
-  }
+  load_query_rows<NTHR>(QH, qb, Q, NC, E, ES, tid);
   for (int idx = tid; idx < kBwdQ * 40; idx += NTHR) red[idx] = 0.0f;
   for (int idx = tid; idx < 2 * kBwdQ * kKS; idx += NTHR) pk[idx] = 0.0f;      // pk and dpk (their padding stays zero)
   if (tid < 16) {
@@ -536,17 +518,11 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
         ss += dot4(v, v);
         se += dot4(v, w4);
       }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) {
-      ss += __shfl_xor(ss, o, 64);
-      se += __shfl_xor(se, o, 64);
-    }
+    ss = sum16(ss);                                     // (row_sumsq16 with emb . q_i riding along on the same reads)
+    se = sum16(se);
     const float n = sqrtf(ss), r = 1.0f / (n + 1e-13f);
     if (i < Q) {
-      for (int c = sub; c < NC; c += 16) {
-        f32x4* p = (f32x4*)(QH + i * ES + 4 * c);
-        *p = *p * r;
-      }
+      scale_row16(QH + i * ES, NC, sub, r);
       if (sub == 0) { nq[i] = n; rq[i] = r; embv[i] = se; }
     }
   }
@@ -666,20 +642,10 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
   __syncthreads();
   const int nv = wlist[15];
 
-  // A block of rows travels global -> registers -> LDS in two steps (see kernel_pool_bwd_tiled_kernel): fetch() is called
-  // one window ahead inside a region, commit() once the current window's arithmetic has read DB.  A thread's chunks are the
-  // same (row, column) in every block.
+  // A block of rows travels global -> registers -> LDS in two steps (bwd_tiled_device.h, staging): fetch() is called
+  // one window ahead inside a region, commit() once the current window's arithmetic has read DB.
   int frow[kLB], fcol[kLB];
-#pragma unroll
-  for (int u = 0; u < kLB; ++u) {
-    const int idx = tid + u * NTHR;
-    frow[u] = 32;
-    fcol[u] = 0;
-    if (idx < 32 * NC) {
-      frow[u] = idx / NC;
-      fcol[u] = 4 * (idx - frow[u] * NC);
-    }
-  }
+  stage_plan<kLB, NTHR>(tid, NC, frow, fcol);
   f32x4 nxt[kLB];
   auto fetch = [&](const int* table) {
 #pragma unroll
@@ -689,21 +655,11 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
       if (flat >= 0) nxt[u] = *(const f32x4*)(a.chunks + (int64_t)flat * E + fcol[u]);
     }
   };
-  auto commit = [&]() {
-#pragma unroll
-    for (int u = 0; u < kLB; ++u)
-      if (frow[u] < 32) *(f32x4*)(DB + frow[u] * ES + fcol[u]) = nxt[u];
-  };
+  auto commit = [&]() { stage_commit<kLB>(DB, ES, frow, fcol, nxt); };
   auto row_norms = [&]() {                              // sixteen threads per row of DB (the first eight wavefronts)
     if (tid >= 512) return;
     const int row = tid >> 4, sub = tid & 15;
-    float ss = 0.0f;
-    for (int c = sub; c < NC; c += 16) {
-      const f32x4 v = *(const f32x4*)(DB + row * ES + 4 * c);
-      ss += dot4(v, v);
-    }
-#pragma unroll
-    for (int o = 1; o < 16; o <<= 1) ss += __shfl_xor(ss, o, 64);
+    const float ss = row_sumsq16(DB + row * ES, NC, sub);
     if (sub == 0) {
       const float nn = sqrtf(ss);
       nd[row] = nn;
@@ -716,7 +672,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
   f32x16 accq[TPW];
 #pragma unroll
   for (int t = 0; t < TPW; ++t) accq[t] = f32x16{0};
-  TKL_PH(0);
+  BWD_PH(0);
   for (int n = 0; n < nv; ++n) {
     const int j = wlist[n];
     const int r = j % 3;
@@ -734,50 +690,24 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
     commit();
     __syncthreads();
     if (!last) fetch(prowA + wlist[n + 1] * 32);
-    TKL_PH(1);
+    BWD_PH(1);
     row_norms();
     if (tid < kBwdQ) lmask[tid] = 0;
     int lw = ln, hw = lh;                                // (opaque copies: the addresses below are recomputed per window, not kept)
     asm volatile("" : "+v"(lw), "+v"(hw));
-    {  // cosine tile: this wavefront's K slice of the 32 x 32 tile; the eight partial tiles meet in LDS in a fixed order
-      f32x16 acc = {0};
-      const float* arow = DB + lw * ES;
-      const float* brow = QH + (lw < Q ? lw : Q - 1) * ES;
-      for (int p = wv; 2 * p < NC; p += NW) {
-        const int cc = 2 * p + hw;
-        const int cl = cc < NC ? cc : NC - 1;            // (odd NC: the last pair's upper half multiplies zeros)
-        f32x4 av = *(const f32x4*)(arow + 4 * cl);
-        const f32x4 bv = *(const f32x4*)(brow + 4 * cl);
-        if (cc >= NC) av = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q4], bv[q4], acc, 0, 0, 0);
-      }
-      float* ps = PS + (wv % NS) * 1024 + 4 * hw * 32 + lw;
-      if (wv >= NS) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ps[mrow(i) * 32] = acc[i];
-      }
-      __syncthreads();
-      if (wv < NS) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ps[mrow(i) * 32] += acc[i];
-      }
-    }
+    cosine_partials<NW>(DB, QH, PS, Q, NC, ES, wv, lw, hw);   // (one barrier inside: row_norms' rd is complete behind it)
     __syncthreads();
-    TKL_PH(2);
+    BWD_PH(2);
     for (int idx = tid; idx < 1024; idx += NTHR) {
       const int row = idx >> 5, i = idx & 31;
-      float v = PS[idx];
-#pragma unroll
-      for (int w2 = 1; w2 < NS; ++w2) v += PS[w2 * 1024 + idx];
-      v *= rd[row];
+      const float v = partial_sum<NS>(PS, idx) * rd[row];
       if (i < Q) {
         CT[row * QS + i] = v;
         if (row < kBwdT) CTR[(poff + row) * QS + i] = v;           // (the same bits from every window that holds the position)
       }
     }
     __syncthreads();
-    TKL_PH(3);
+    BWD_PH(3);
     for (int idx = tid / PP; idx < Q * kK; idx += NTHR / PP) {   // pooled kernels of the window: (i, k) on PP threads, 32 / PP positions each
       const int i = idx / kK, k = idx - i * kK;
       const float mu = kc[4 * k], c2 = kc[4 * k + 1];
@@ -802,7 +732,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
       }
     }
     __syncthreads();
-    TKL_PH(4);
+    BWD_PH(4);
     // ---- saturation forward + backward (as above): thread = (query token, kernel), sixteen lanes per token --------------------
     // (On the first wavefront alone — one lane per token looping over the kernels — this chain of logs, exponentials and
     // LDS read-modify-writes was 20 % of the kernel, the other seven wavefronts waiting at the barrier.)
@@ -876,7 +806,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
       if (k == 0) vals[i & 31] = tin ? val : 0.0f;
     }
     __syncthreads();
-    TKL_PH(5);
+    BWD_PH(5);
     if (wv == 0) {                                              // d chunk_scoring_j = g * w_j (:249 sum in index order)
       const float val = vals[lane & 31];
       float wj = 0.0f;
@@ -902,7 +832,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
       if (live) Gsum[(poff + t) * QS + i] += s;
     }
     __syncthreads();
-    TKL_PH(6);
+    BWD_PH(6);
     if (!last) continue;                                          // (wave-uniform)
 
     // ---- the region's gradient products: its <= 38 positions as two blocks of 32 rows -------------------------------------
@@ -938,7 +868,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
       }
       commit();
       __syncthreads();
-      TKL_PH(7);
+      BWD_PH(7);
       row_norms();
       __syncthreads();
       if (tid < 512) {  // sixteen threads per position / per query token, two terms each (whole wavefronts)
@@ -962,7 +892,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
         }
       }
       __syncthreads();
-      TKL_PH(8);
+      BWD_PH(8);
       // (lane coordinates behind an opaque copy: everything derived from them below — some 80 LDS addresses — is then computed
       // here, per block, instead of once before the window loop and kept in spilled registers)
       int lq = ln, hq = lh;
@@ -971,34 +901,15 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
          // Regions may overlap each other by a few positions: rows are read, added to and written back; the regions follow
          // each other inside this one workgroup.
         float ga[16];
-#pragma unroll
-        for (int st = 0; st < 16; ++st) {
-          const int i = 2 * st + hq;
-          ga[st] = gs[lq * QS + (i < QS ? i : QS - 1)];
-          if (i >= Q) ga[st] = 0.0f;
-        }
+        grad_d_operand(ga, gs, Q, QS, lq, hq);
 #pragma unroll
         for (int t = 0; t < TPW; ++t) {
           const int nt = wv + NW * t;
           if (nt >= NT) break;                             // wave-uniform
           const int col = 32 * nt + lq;
           const bool cin = col < E;
-          const float* qcol = QH + (cin ? col : 0);
           const float* dcol = DB + (cin ? col : 0);
-          float bq[16];
-#pragma unroll
-          for (int st = 0; st < 16; ++st) {
-            const int i = 2 * st + hq;
-            bq[st] = qcol[(i < Q ? i : Q - 1) * ES];       // (multiplied by ga = 0 past Q)
-          }
-          f32x16 acc = {0};
-#pragma unroll
-          for (int g2 = 0; g2 < 8; ++g2) {
-            if (2 * g2 < KQ) {                             // wave-uniform
-              acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[2 * g2], bq[2 * g2], acc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ga[2 * g2 + 1], bq[2 * g2 + 1], acc, 0, 0, 0);
-            }
-          }
+          const f32x16 acc = grad_d_tile(ga, QH + (cin ? col : 0), Q, KQ, ES, hq);
           // rows are addressed as 32-bit offsets from the block's lowest chunk row (one address register per store
           // instead of a 64-bit pair and two wide multiplies: the block ran on spilled registers before)
           float* gcol = gblk + (cin ? col : 0);
@@ -1009,7 +920,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
             uint32_t of[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-              const int row = mrow(8 * hf + i) + 4 * hq;
+              const int row = rowof(8 * hf + i) + 4 * hq;
               const int fl = ptab[row];                    // (-1: no such position, or a padding token)
               ov[i] = (acc[8 * hf + i] - dcol[row * ES] * td[row]) * rd[row];
               of[i] = (cin && fl >= 0) ? (uint32_t)(fl - fmin) * (uint32_t)E : 0xffffffffu;
@@ -1027,31 +938,10 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
           }
         }
       }
-      TKL_PH(9);
-      {  // query gradient: A[token][t] = G / (|d_t| + tiny) (K = the block's positions), B = the raw rows
-        float gi[16];
-        const int tk = lq < Q ? lq : Q - 1;
-#pragma unroll
-        for (int st = 0; st < 16; ++st) {
-          const int i = 2 * st + hq;
-          gi[st] = GI[tk * 32 + i] * rd[i];
-          if (lq >= Q) gi[st] = 0.0f;
-        }
-#pragma unroll
-        for (int t = 0; t < TPW; ++t) {
-          const int nt = wv + NW * t;
-          if (nt >= NT) break;
-          const int col = 32 * nt + lq;
-          const float* dcol = DB + (col < E ? col : 0);
-          float bd[16];
-#pragma unroll
-          for (int st = 0; st < 16; ++st) bd[st] = dcol[(2 * st + hq) * ES];
-#pragma unroll
-          for (int st = 0; st < 16; ++st) accq[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(gi[st], bd[st], accq[t], 0, 0, 0);
-        }
-      }
+      BWD_PH(9);
+      grad_q_accumulate<NW, TPW>(accq, GI, rd, DB, Q, E, ES, NT, wv, lq, hq);
       __syncthreads();   // the next block / region reuses the LDS tiles and may touch the same chunk rows
-      TKL_PH(10);
+      BWD_PH(10);
     }
   }
 
@@ -1070,17 +960,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
     const int col = 32 * nt + ln;
     if (nt < NT && col < E) {
       const float ew = emb_sat ? prm[TklParams::emb() + col] : 0.0f;
-      float ov[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int tok = mrow(i) + 4 * lh, tc = tok < Q ? tok : Q - 1;
-        const float self = nq[tc] > 0.0f ? sqs[tc] : 0.0f;            // QH holds q_i / |q_i| (to 1e-13)
-        ov[i] = (accq[t][i] - QH[tc * ES + col] * self) * rq[tc] + ew * dev[tc];
-      }
-      TKL_KEEP16(ov);
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if (mrow(i) + 4 * lh < Q) gq[(uint32_t)((mrow(i) + 4 * lh) * E + col)] = ov[i];
+      grad_q_store_tile(accq[t], QH, nq, sqs, rq, gq, Q, E, ES, col, lh, [&](float v, int tc) { return v + ew * dev[tc]; });
     }
   }
   float* gp = S > 1 ? a.part_gp + ((int64_t)b * 3 + r0) * a.NP : a.gprm + (int64_t)b * a.NP;
@@ -1102,7 +982,7 @@ __global__ void __launch_bounds__(NTHR) tkl_bwd_tiled_kernel(const TklBwdArgs a)
   }
   if (tid < 15) gp[TklParams::chunk_scoring() + tid] = csg[tid];
 #if MM_TKL_BWD_PHASE_TIMES
-  TKL_PH(11);
+  BWD_PH(11);
   __syncthreads();
   if (tid == 0 && b == 0)
     for (int k = 0; k < 12; ++k) gp[k] = ph[k];
