@@ -1033,6 +1033,99 @@ int mm_rank_metrics_depth_fwd(const int32_t* order, const int64_t* seg_begin, co
                               const int32_t* binary_num_relevant, const double* idcg, const double* log2_table, int n_log2,
                               int32_t* first_rank, int32_t* hits, double* ap, double* ndcg, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training losses: the reduced loss and its gradient with respect to the scores in ONE call, so that autograd's backward
+ * is a single multiply by grad_output (additive: MM_ABI_VERSION unchanged).  Both entries run on `stream` with no
+ * allocation, no read-back and no atomics, vector stores only, one linear chain of launches: graph-capturable, two calls
+ * give the same bits.  Scores are MM_F32 / MM_F16 / MM_BF16 and are widened exactly to fp32; labels are fp32.  Per-element
+ * terms of the list kinds are fp32 with the accurate library functions (expf, log1pf, logf, exp2f), those of the pair kinds
+ * float64 (sigmoid(x) - y and KLDiv's terms cancel: fp32 terms miss one 16-bit ulp of the gradient / four fp32 ulps of the
+ * loss there); every sum is float64 in a fixed order, rounded once to fp32; each gradient is rounded once to the scores' dtype.  STATED CHOICE: 16-bit
+ * scores are computed from their exact widened values (the reference rounds pos - neg to 16 bits first).  STATED CHOICE:
+ * inputs are never modified (lambdarank.py:66-67 writes -inf into y_pred / y_true in place).  Every output element is
+ * written on every successful call, zeros for padded entries and for lists with no counted pair included.
+ *
+ * mm_pair_loss_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/losses/ranknet.py:15-16, matchmaker/losses/all.py:48, matchmaker/losses/msmargin.py:13,
+ *           matchmaker/losses/teacher_mse_pointwise.py:13-14, matchmaker/losses/teacher_kldiv_pointwise.py:13-14,
+ *           matchmaker/losses/teacher_ranknetweighted.py:16-18, matchmaker/losses/teacher_mse_ranknet.py:13-15
+ *   pos, neg [n] of `dtype`; a, b [n] fp32 labels (b is not read by MM_PAIR_RANKNET and MM_PAIR_MARGIN and may be NULL
+ *   there); loss [1] fp32 = the MEAN over n of the per-element loss; grad_pos, grad_neg [n] of `dtype` = d loss / d pos,
+ *   d loss / d neg (the 1 / n included).  With x = pos - neg, sg = sigmoid, sp(x) = max(x, 0) + log1p(exp(-|x|)):
+ *     MM_PAIR_RANKNET          a = target y.  sp(x) - x y;  dx = sg(x) - y                      (BCEWithLogitsLoss)
+ *     MM_PAIR_MARGIN           a = label y.   max(0, 1 - y x);  dx = -y where 1 - y x >= 0, else 0
+ *                              (MarginRankingLoss(margin=1); torch's clamp_min backward: the kink passes the gradient)
+ *     MM_PAIR_MARGIN_MSE       (x - (a - b))^2;  dx = 2 (x - (a - b))
+ *     MM_PAIR_MSE_POINTWISE    ((pos - a)^2 + (neg - b)^2) / 2;  gpos = pos - a, gneg = neg - b
+ *     MM_PAIR_KLDIV_POINTWISE  (xlogy(a, a) - a pos + xlogy(b, b) - b neg) / 2;  gpos = -a / 2, gneg = -b / 2
+ *                              (KLDivLoss() fed raw scores, reproduced as it is; a negative label gives a NaN loss as in torch)
+ *     MM_PAIR_RANKNET_TEACHER  (a - b) (sp(x) - x);  dx = (a - b)(sg(x) - 1)
+ *     MM_PAIR_MSE_RANKNET      the MM_PAIR_MSE_POINTWISE term + sp(x) - x;  the sum of both gradients
+ *   For the kinds written with dx: gpos = dx, gneg = -dx.
+ *   0 <= n <= 2^31.  n = 0 writes loss = NaN (torch.mean of an empty tensor) and launches nothing else.
+ *   A grid that is a function of n alone strides over the elements; n <= 4,096 is one workgroup and one launch.  Larger n:
+ *   one float64 partial per workgroup in the workspace (mm_pair_loss_workspace_bytes(n), 0 up to 4,096 elements, at most
+ *   8 KiB), added by a second one-workgroup launch in a fixed order.
+ *   MM_EINVAL: NULL where required, n < 0, unknown kind or dtype.  MM_EUNSUPPORTED: n > 2^31.  MM_EWORKSPACE: short workspace.
+ */
+#define MM_PAIR_RANKNET 0
+#define MM_PAIR_MARGIN 1
+#define MM_PAIR_MARGIN_MSE 2
+#define MM_PAIR_MSE_POINTWISE 3
+#define MM_PAIR_KLDIV_POINTWISE 4
+#define MM_PAIR_RANKNET_TEACHER 5
+#define MM_PAIR_MSE_RANKNET 6
+
+size_t mm_pair_loss_workspace_bytes(int64_t n);
+int mm_pair_loss_fwd(const void* pos, const void* neg, int dtype, const float* a, const float* b, int64_t n, int kind,
+                     float* loss, void* grad_pos, void* grad_neg, void* workspace, size_t workspace_bytes, void* stream);
+
+/* mm_list_loss_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/losses/listnet.py:27-33, matchmaker/losses/teacher_kldiv_list.py:13,
+ *           matchmaker/losses/loss_smooth_mrr.py:11-33, matchmaker/losses/lambdarank.py:65-119 and :131-134
+ *   scores [B, L] of `dtype`, labels [B, L] fp32; loss [1] fp32; per_list [B] fp32 = the list's own term before the batch
+ *   reduction (what SmoothMRRLoss(agg=False) returns); grad [B, L] of `dtype` = d loss / d scores.  p = softmax(scores),
+ *   T = softmax(labels), both per list:
+ *     MM_LIST_LISTNET     per list -sum_i T_i log(p_i + 1e-6); mean over B.
+ *                         grad_k = -(1 / B) sum_i T_i p_i (d_ik - p_k) / (p_i + 1e-6)
+ *     MM_LIST_KLDIV       sum_i (xlogy(T_i, T_i) - T_i p_i), summed over the lists, divided by B (KLDivLoss("batchmean") fed
+ *                         probabilities, reproduced as it is).  grad_k = -(1 / B) sum_i T_i p_i (d_ik - p_k)
+ *     MM_LIST_SMOOTH_MRR  rank_i = 0.5 + sum_j sg(s_j - s_i), j = i included; rr_i = [label_i > 0] / rank_i; per list
+ *                         1 - max_i rr_i; mean over B.  The gradient flows through the arg-max only.  STATED CHOICE: the
+ *                         lowest index on ties.
+ *     MM_LIST_LAMBDA_NDCG2  LambdaLoss("ndcgLoss2_scheme") with padded_value_indicator=-1, eps=1e-6, k=None, sigma=1,
+ *                         reduction="sum", reduction_log="binary".  Entries with label == -1 are padded: score and label
+ *                         count as -inf and their gradient is 0.  Stable descending order of the scores; t = the labels in
+ *                         that order; D[m] = log2(2 + m); maxDCG = max(sum_m (2^max(label, 0) - 1) / D[m] over the labels in
+ *                         descending order, eps); G_i = (2^max(t_i, 0) - 1) / maxDCG.  For every ordered pair (i, j) of sorted
+ *                         positions with t_i, t_j finite and t_i > t_j:  w = |1 / D[|i - j| - 1] - 1 / D[|i - j|]| |G_i - G_j|,
+ *                         x = clamp(s_i - s_j, +-1e4), p = sg(x), term = -log2(max(max(p, eps)^w, eps)).  Loss = the sum over
+ *                         all lists, NOT divided by B.  d term / d x = -w (1 - p) / ln 2 when p >= eps and p^w >= eps, else 0;
+ *                         it is added to the score at sorted position i and subtracted from the one at j.  (The discount
+ *                         differences are formed in float64 and rounded once: two reciprocals that agree in ever more digits.
+ *                         The term is evaluated as min(w softplus(-x) / ln 2, -log2(eps)) where p >= eps: the same value
+ *                         without p^w and log(p) next to 1, where fp32 keeps a handful of the term's bits.)
+ *     MM_LIST_LAMBDA_NDCG2_TEACHER  labels <- softmax(labels) in fp32, then + 2 where > 0.001, on the device; then as above.
+ *                         Nothing is padded.
+ *   STATED CHOICE for the order: stable, as mm_segment_rank_fwd (equal scores in arrival order, -0 == +0); torch.sort on the
+ *   GPU leaves the order of ties open.  The loss depends on it only when non-padded scores tie exactly.
+ *   Lists of <= 64 entries take one wavefront each (four per workgroup, no LDS), longer ones one workgroup each; ranks come
+ *   from counting the keys below one's own; the pair loop is O(L^2) per list.  L > MM_LOSS_MAX_LIST returns MM_EUNSUPPORTED
+ *   before any launch.  A second one-workgroup launch adds per_list in a fixed order.  No workspace.
+ *   B = 0: loss = NaN for the mean kinds, 0 for the Lambda kinds.  L = 0: every per_list term is its empty sum (1 for
+ *   MM_LIST_SMOOTH_MRR).
+ *   MM_EINVAL: NULL where required, B < 0, L < 0, unknown kind or dtype.
+ */
+#define MM_LIST_LISTNET 0
+#define MM_LIST_KLDIV 1
+#define MM_LIST_SMOOTH_MRR 2
+#define MM_LIST_LAMBDA_NDCG2 3
+#define MM_LIST_LAMBDA_NDCG2_TEACHER 4
+#define MM_LOSS_MAX_LIST 1024
+
+int mm_list_loss_fwd(const void* scores, int dtype, const float* labels, int B, int L, int kind, float* loss,
+                     float* per_list, void* grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ from ._lib import NativeError, LIB_PATH  # noqa: F401
 from . import ops  # noqa: F401
 
 __all__ = ["ops", "NativeError", "LIB_PATH", "FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer",
-           "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8"]
+           "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8",
+           "losses", "get_loss", "patch_losses"]
 
 
 def __getattr__(name):          # the indexers, imported on first use (retrieval pulls in torch.distributed)
@@ -23,4 +24,13 @@ def __getattr__(name):          # the indexers, imported on first use (retrieval
         return encode_collection
     if name in ("fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8"):   # the fp8 store's operators
         return getattr(ops, name)
+    if name == "losses":        # the native training losses (drop-ins for matchmaker/losses/*.py) and their get_loss
+        import importlib
+        return importlib.import_module(".losses", __name__)
+    if name == "get_loss":
+        from .losses import get_loss
+        return get_loss
+    if name == "patch_losses":  # opt-in: patch_matchmaker() rebinds the models only
+        from .patch import patch_losses
+        return patch_losses
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

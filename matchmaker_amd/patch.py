@@ -65,3 +65,47 @@ def patch_matchmaker(strict: bool = False):
             pass
         _idcm_note_given = True
     return done
+
+
+# ---- losses (opt-in) ---------------------------------------------------------------------------------------------------------
+# (reference module, attribute) -> attribute of matchmaker_amd.losses.  Not part of _TABLE: a caller who patched the models
+# must not silently get different losses.
+_LOSS_TABLE = [
+    ("matchmaker.losses.msmargin", "MSMarginLoss", "MSMarginLoss"),
+    ("matchmaker.losses.teacher_mse_pointwise", "MSETeacherPointwise", "MSETeacherPointwise"),
+    ("matchmaker.losses.teacher_kldiv_pointwise", "KLDivTeacherPointwise", "KLDivTeacherPointwise"),
+    ("matchmaker.losses.teacher_ranknetweighted", "RankNetTeacher", "RankNetTeacher"),
+    ("matchmaker.losses.teacher_mse_ranknet", "MSERanknetTeacher", "MSERanknetTeacher"),
+    ("matchmaker.losses.ranknet", "RankNetLoss", "RankNetLoss"),
+    ("matchmaker.losses.loss_smooth_mrr", "SmoothMRRLoss", "SmoothMRRLoss"),
+    ("matchmaker.losses.listnet", "ListNetLoss", "ListNetLoss"),
+    ("matchmaker.losses.teacher_kldiv_list", "KLDivTeacherList", "KLDivTeacherList"),
+    ("matchmaker.losses.lambdarank", "LambdaLoss", "LambdaLoss"),
+    ("matchmaker.losses.lambdarank", "LambdaLossTeacher", "LambdaLossTeacher"),
+]
+
+
+def patch_losses(strict: bool = False):
+    """Opt-in: rebinds the reference's loss classes (in their defining modules) to the matchmaker_amd.losses drop-ins and,
+    when matchmaker.losses.all is already imported, the copies its `import *` made there together with its get_loss
+    ("margin" builds torch.nn.MarginRankingLoss inline in get_loss, so only the rebound get_loss reaches that one).
+    Returns the list of "module.attribute" names that were rebound.  patch_matchmaker() does not call this."""
+    from . import losses as ours
+    done = []
+    for ref_mod, ref_attr, our_attr in _LOSS_TABLE:
+        try:
+            ref = importlib.import_module(ref_mod)
+        except Exception:
+            if strict:
+                raise
+            continue
+        setattr(ref, ref_attr, getattr(ours, our_attr))
+        done.append(ref_mod + "." + ref_attr)
+    all_mod = sys.modules.get("matchmaker.losses.all")
+    if all_mod is not None:
+        for _, ref_attr, our_attr in _LOSS_TABLE:
+            if hasattr(all_mod, ref_attr):
+                setattr(all_mod, ref_attr, getattr(ours, our_attr))
+        all_mod.get_loss = ours.get_loss
+        done.append("matchmaker.losses.all.get_loss")
+    return done

@@ -16,10 +16,12 @@ Importing this module defines
     torch.ops.mm_native.maxsim_ragged_fp8(q, codes, scales, doc_begin, doc_end, q_mask=None, pairs_per_query=1,
                                           check_ranges=True, sim_round=False, sum_round=False) -> [n_pairs]
     torch.ops.mm_native.segment_rank(scores, seg_begin, max_len)                    -> order [N] int32
+    torch.ops.mm_native.pair_loss(pos, neg, a, b, kind)                             -> (loss [], grad_pos, grad_neg)
+    torch.ops.mm_native.list_loss(scores, labels, kind)                             -> (loss [], per_list [B], grad [B, L])
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
-(maxsim, maxsim_inbatch, kernel_pool) and an autocast rule that mirrors what the reference's eager code does under
+(maxsim, maxsim_inbatch, kernel_pool; the two losses return their own gradient) and an autocast rule that mirrors what the reference's eager code does under
 `torch.cuda.amp.autocast(enabled=use_fp16)` (colbert.py:60: the bmm runs in fp16 and RETURNS fp16 — the MaxSim ops cast
 their vectors to the autocast dtype and set sim_round, so every per-token maximum is rounded as the reference's fp16 `max`
 is — and the promoted `sum` returns fp32; the TK family stays fp32 — allennlp's cosine has no fp16 path the configs use, tk.yaml `use_fp16: False`).
@@ -525,3 +527,58 @@ def segment_rank(scores: Tensor, seg_begin: Tensor, max_len: int) -> Tensor:
 @segment_rank.register_fake
 def _(scores, seg_begin, max_len):
     return scores.new_empty((scores.shape[0],), dtype=torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------- training losses
+from . import losses as _losses  # noqa: E402
+
+
+@torch.library.custom_op(_NS + "::pair_loss", mutates_args=(), device_types="cuda")
+def pair_loss(pos: Tensor, neg: Tensor, a: Tensor, b: Optional[Tensor], kind: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(loss [] float32, grad_pos, grad_neg): a pairwise / pointwise training loss with its gradient (losses.pair_loss;
+    kind = a value of losses.PAIR_KINDS).  Differentiable in pos and neg through `loss`; the labels get no gradient."""
+    return _losses.pair_loss(pos, neg, a, b, kind)
+
+
+@pair_loss.register_fake
+def _(pos, neg, a, b, kind):
+    return pos.new_empty((), dtype=torch.float32), pos.new_empty(pos.shape), neg.new_empty(pos.shape)
+
+
+def _pair_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1], output[2])
+    ctx.mark_non_differentiable(output[1], output[2])
+
+
+def _pair_loss_backward(ctx, g, _gpos, _gneg):
+    gpos, gneg = ctx.saved_tensors
+    return gpos * g, gneg * g, None, None, None
+
+
+pair_loss.register_autograd(_pair_loss_backward, setup_context=_pair_loss_setup)
+
+
+@torch.library.custom_op(_NS + "::list_loss", mutates_args=(), device_types="cuda")
+def list_loss(scores: Tensor, labels: Tensor, kind: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """(loss [] float32, per_list [B] float32, grad [B, L]): a listwise training loss with its gradient (losses.list_loss;
+    kind = a value of losses.LIST_KINDS).  Differentiable in scores through `loss` and `per_list`; the labels get no gradient."""
+    return _losses.list_loss(scores, labels, kind)
+
+
+@list_loss.register_fake
+def _(scores, labels, kind):
+    return (scores.new_empty((), dtype=torch.float32), scores.new_empty((scores.shape[0],), dtype=torch.float32),
+            scores.new_empty(scores.shape))
+
+
+def _list_loss_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[2])
+    ctx.kind = inputs[2]
+    ctx.mark_non_differentiable(output[2])
+
+
+def _list_loss_backward(ctx, g_loss, g_per_list, _ggrad):
+    return _losses.list_loss_backward(ctx.saved_tensors[0], ctx.kind, g_loss, g_per_list), None, None
+
+
+list_loss.register_autograd(_list_loss_backward, setup_context=_list_loss_setup)
