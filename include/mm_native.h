@@ -1126,6 +1126,36 @@ int mm_pair_loss_fwd(const void* pos, const void* neg, int dtype, const float* a
 int mm_list_loss_fwd(const void* scores, int dtype, const float* labels, int B, int L, int kind, float* loss,
                      float* per_list, void* grad, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * mm_distinct_hits_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/dense_retrieval.py:414-429 (the `maxP->bert_dot` branch of the search loop: per query a Python loop
+ *           over the passage hits with a `set` of ids, the first hit of every id kept until top_n documents are found), on
+ *           an index whose external ids repeat per passage (dense_retrieval.py:237-265, `current_ids[start:end] = len(seq_ids)`).
+ *   hit_scores [nq, K] fp32, hit_ids [nq, K] int64, contiguous, in the order the search returned them (score descending, ties
+ *   in the search's own order).  The list is NOT re-sorted by score: per query the first occurrence of every id IN LIST ORDER
+ *   is kept, which is the reference's loop and, for a descending list, the document's maximum passage score.
+ *   Every id < 0 is "no hit" and dropped (-1 is not the only such value); every id >= 0 is valid, INT64_MAX included (ids are
+ *   ordered as unsigned numbers, so the sign bit is the valid bit and no id value is reserved).  Scores are payload: copied bit
+ *   for bit (NaN, +-inf, -0.0) and never compared.
+ *   out_scores fp32, out_ids int64, out_pos int32, each [nq, top_n]: the first min(distinct, top_n) kept hits in list order,
+ *   out_pos = the hit's position in the list (the caller recovers the winning passage row from it); behind them -inf / -1 / -1.
+ *   n_distinct [nq] int32 = distinct valid ids of the WHOLE list (not capped at top_n); n_valid [nq] int32 = ids >= 0.
+ *   Certificate: when the list is the exact top-K in descending order, a document with no passage in it scores <= the K-th
+ *   hit, so the kept hits are the exact document ranking as far as they go; n_distinct >= top_n or n_valid < K (the index was
+ *   exhausted) means out_* is the exact top_n of all documents.
+ *   1 <= K <= MM_DISTINCT_MAX_HITS, 1 <= top_n <= K, else MM_EUNSUPPORTED before any launch; nq < 0 or a NULL pointer with
+ *   nq > 0: MM_EINVAL; nq = 0 succeeds without a launch (its pointers are not looked at); nq < 2^31 by its type.
+ *   One workgroup per query in grid.x.  LDS: 16 bytes per key for the next power of two >= K, K flag bytes, 64 bytes of scan
+ *   scratch: 136 KiB at K = 8,192 (one workgroup per CU), 2.2 KiB at K = 128.  Every output element is stored exactly once,
+ *   nothing else is written, whatever the ids hold every access stays inside the arrays.  No workspace, no atomics, no
+ *   read-back: graph-capturable, two calls give the same bits.
+ */
+#define MM_DISTINCT_MAX_HITS 8192
+
+int mm_distinct_hits_fwd(const float* hit_scores, const int64_t* hit_ids, int nq, int K, int top_n,
+                         float* out_scores, int64_t* out_ids, int32_t* out_pos,
+                         int32_t* n_distinct, int32_t* n_valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

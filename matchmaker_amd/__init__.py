@@ -5,12 +5,12 @@ from ._lib import NativeError, LIB_PATH  # noqa: F401
 from . import ops  # noqa: F401
 
 __all__ = ["ops", "NativeError", "LIB_PATH", "FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer",
-           "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8",
+           "MaxPIndexer", "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8",
            "losses", "get_loss", "patch_losses"]
 
 
 def __getattr__(name):          # the indexers, imported on first use (retrieval pulls in torch.distributed)
-    if name in ("FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer"):
+    if name in ("FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer", "MaxPIndexer"):
         from . import retrieval
         return getattr(retrieval, name)
     if name == "TokenStore":    # the ColBERT token store (16-bit, or fp8: TokenStore.quantize_fp8 / load(..., fp8=True))

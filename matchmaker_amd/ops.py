@@ -1246,6 +1246,17 @@ def colbert_candidates(hit_rows: torch.Tensor, begin_sorted: torch.Tensor, end_s
     return cand_doc, cand_begin, cand_end, count
 
 
+DISTINCT_MAX_HITS = _lib.DISTINCT_MAX_HITS      # hits per query of mm_distinct_hits_fwd (128 KB of 16-byte keys in LDS)
+
+
+def distinct_hits(scores: torch.Tensor, ids: torch.Tensor, top_n: int):
+    """Passage hits -> distinct documents (matchmaker/dense_retrieval.py:414-429; native mm_distinct_hits_fwd): see
+    matchmaker_amd/maxp.py, where the torch <-> ABI wrapper lives as the losses' lives in losses.py (a module of its own that
+    tests/poison.py can be pointed at; the poisoned-memory case of this operator is in tests/test_maxp_gpu.py)."""
+    from . import maxp
+    return maxp.distinct_hits(scores, ids, top_n)
+
+
 def store_append(x: torch.Tensor, rows_out: Optional[torch.Tensor], codes_out: Optional[torch.Tensor],
                  scales_out: Optional[torch.Tensor], capacity: int, fill: torch.Tensor, doc_begin: torch.Tensor,
                  doc_end: torch.Tensor, status: torch.Tensor, keep_zero_rows: bool = False) -> None:

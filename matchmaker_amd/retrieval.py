@@ -30,6 +30,9 @@ library in the reference): int(sqrt(n)) spherical k-means leaves, 4-bit anisotro
 residuals (mm_ah_encode), probe selection with the top-k kernel, the scan of the probed leaves' codes (mm_ah_scan_fwd) and
 the exact re-score of the best candidates from the resident originals (mm_gather_dot).
 
+MaxPIndexer wraps any of them for document retrieval over a passage index (`maxP->bert_dot`, dense_retrieval.py:414-429): the
+inner index returns passage hits under repeated document ids and ops.distinct_hits keeps the first hit of every document.
+
 What the indexers have in common lives once, in two private bases: `_DeviceIndex` (the config and device set-up with the
 float16 refusal, the chunk-by-chunk copy to the device, rows -> ids) and, for the four that shard over a process group,
 `_ShardedIndex` (this rank's shard, the resident-shard check, `search()`, the all-gather + merge, the archive writer and
@@ -1137,3 +1140,128 @@ class ScannIPIndexer(_ShardedIndex):
         self.vectors = torch.from_numpy(z["vectors"]).to(self.device)
         self.ids = torch.from_numpy(z["ids"].astype(np.int64)).to(self.device)
         self.nlist, self.eta = nlist, float(z["eta"])
+
+
+class MaxPIndexer:
+    """Document retrieval over a PASSAGE index (`maxP->bert_dot`, matchmaker/models/max_p_adapter.py:109-151 + the search
+    branch dense_retrieval.py:414-429): the inner index holds one vector per passage under its document's id
+    (dense_retrieval.py:237-265, `current_ids[start:end] = len(seq_ids)`), a search asks it for `index_hit_top_n` passage
+    hits and keeps the first hit of every document until `top_n` documents are found (ops.distinct_hits: one kernel instead
+    of the host loop).
+
+    `inner` is any object with `search_device(query_vec, k)`: FlatIPIndexer, IVFFlatIPIndexer, IVFFp8IPIndexer,
+    GraphIPIndexer, ScannIPIndexer.  With several ranks the inner search already returns the merged top-k, so a document
+    whose passages lie on two shards is deduplicated after the merge.  distinct_fn(scores, ids, top_n) defaults to
+    ops.distinct_hits; the CPU test-suite injects a stand-in, as for the other indexers.
+
+    Certificate: the hits are the top-K passages in descending order, so a document with no passage among them scores at
+    most the K-th hit, which is at most every listed hit: the kept hits are the document ranking as far as they go.  A query
+    is `complete` when its list holds >= top_n documents or fewer than K valid hits (the index ran out); with an exact inner
+    index its row is then the exact top_n of all documents.  With an approximate inner index `complete` means that asking
+    for more hits cannot add documents the inner search would have found, not that the row is exact."""
+
+    MAX_HITS = ops.DISTINCT_MAX_HITS
+
+    def __init__(self, inner, distinct_fn=None, max_hits: Optional[int] = None):
+        """max_hits: where widening stops (default and maximum MAX_HITS, the kernel's limit).  The native inner indexers take
+        k <= 4096 (the top-k kernel's candidate sorter): pass max_hits=4096 to widen over one of them."""
+        self.inner = inner
+        self._distinct = distinct_fn if distinct_fn is not None else ops.distinct_hits
+        self.max_hits = self.MAX_HITS if max_hits is None else int(max_hits)
+        if not 1 <= self.max_hits <= self.MAX_HITS:
+            raise ops.NativeError(f"MaxPIndexer: max_hits={max_hits} outside 1 .. {self.MAX_HITS}", ops._lib.MM_EUNSUPPORTED)
+
+    def prepare(self, *args, **kw):
+        return self.inner.prepare(*args, **kw)
+
+    def index(self, ids, data_chunks):
+        """As the inner index's: `ids` repeat per passage."""
+        return self.inner.index(ids, data_chunks)
+
+    def index_resident(self, ids: torch.Tensor, vectors: torch.Tensor):
+        return self.inner.index_resident(ids, vectors)
+
+    def index_store(self, store):
+        """The passages of a TokenStore (TokenStoreWriter.finish(): one range of rows per document, the zero rows of the
+        [docs, chunks, dim] encoder output already removed) become the inner index: every row under the index of its document
+        in store.seq_ids.  The ids are built on the device; the rows are used as they lie when the ranges tile the matrix in
+        document order (the writer's layout) and gathered otherwise.  With several ranks each takes its contiguous shard."""
+        if store.is_fp8 and store._tokens is None:
+            raise ops.NativeError("MaxPIndexer.index_store: an fp8-only store has no 16-bit rows to index; build the passage "
+                                  "index with IVFFp8IPIndexer over its codes, or keep the rows (keep_tokens=True)")
+        inner, tokens = self.inner, store.tokens
+        dev = tokens.device
+        begin, end = store._begin, store._end
+        length = torch.from_numpy(end - begin).to(dev)
+        ids = torch.repeat_interleave(torch.arange(length.numel(), dtype=torch.int64, device=dev), length)
+        tiled = begin.size == 0 or (begin[0] == 0 and end[-1] == tokens.shape[0] and bool((begin[1:] == end[:-1]).all()))
+        if not tiled:
+            first = torch.cumsum(length, 0) - length                        # the document's first row in the packed order
+            rows = torch.arange(ids.numel(), dtype=torch.int64, device=dev) + torch.repeat_interleave(
+                torch.from_numpy(begin).to(dev) - first, length)
+            tokens = tokens[rows]
+        world, rank = inner._world() if hasattr(inner, "_world") else (1, 0)
+        if world > 1:
+            lo, hi = shard_range(ids.numel(), world, rank)
+            ids, tokens = ids[lo:hi], tokens[lo:hi]
+        vec = tokens.to(inner.device).to(inner.dtype)
+        if vec.shape[1] != inner.E_pad:
+            if vec.shape[1] > inner.E_pad:
+                raise ops.NativeError(f"MaxPIndexer.index_store: {vec.shape[1]}-dim rows for an index of width {inner.E_pad}")
+            vec = torch.nn.functional.pad(vec, (0, inner.E_pad - vec.shape[1]))
+        inner.index_resident(ids.to(inner.device), vec.contiguous())
+
+    def _check(self, top_n, index_hit_top_n):
+        top_n = int(top_n)
+        K = int(index_hit_top_n) if index_hit_top_n else top_n      # test_config.get("index_hit_top_n", top_n), dense_retrieval.py:391
+        if top_n > self.MAX_HITS or K > self.MAX_HITS:
+            raise ops.NativeError(f"MaxPIndexer.search: top_n={top_n} / index_hit_top_n={K} above the limit of {self.MAX_HITS} "
+                                  "hits per query (the distinct-hits kernel sorts a query's hits in LDS)", ops._lib.MM_EUNSUPPORTED)
+        if not 1 <= top_n <= K:
+            raise ops.NativeError(f"MaxPIndexer.search: top_n={top_n} outside 1 .. index_hit_top_n={K}")
+        return top_n, K
+
+    def search_device(self, query_vec, top_n: int, index_hit_top_n: Optional[int] = None, widen: bool = False,
+                      return_info: bool = False):
+        """(scores [nq, top_n] float32, ids [nq, top_n] int64) on the device: the first top_n distinct documents among the
+        K = index_hit_top_n (default top_n) passage hits of every query, -inf / -1 where the hits held fewer.
+        widen=False: one search and one kernel, no host synchronisation (the reference's behaviour).  widen=True: the
+        `complete` flags are read back and the incomplete queries ALONE are searched again with K doubled (capped at
+        max_hits) until every query is complete or K is at the cap; rows still incomplete there stay flagged.
+        return_info: also a dict of pos [nq, top_n] int32 (the kept hit's position in its list), n_distinct [nq] int32,
+        complete [nq] bool and hits_used [nq] int32 (the K of the search the row comes from)."""
+        top_n, K = self._check(top_n, index_hit_top_n)
+        hs, hi = self.inner.search_device(query_vec, K)
+        s, ids, pos, nd, nv = self._distinct(hs, hi, top_n)
+        complete = (nd >= top_n) | (nv < K)
+        used = torch.full_like(nd, K)
+        if widen:
+            q = torch.as_tensor(query_vec)
+            q = q[None, :] if q.dim() == 1 else q
+            while K < self.max_hits:
+                todo = torch.nonzero(~complete).flatten()                   # the read-back
+                if todo.numel() == 0:
+                    break
+                K = min(2 * K, self.max_hits)
+                hs, hi = self.inner.search_device(q[todo.to(q.device)], K)
+                s2, i2, p2, nd2, nv2 = self._distinct(hs, hi, top_n)
+                s[todo], ids[todo], pos[todo], nd[todo] = s2, i2, p2, nd2
+                complete[todo] = (nd2 >= top_n) | (nv2 < K)
+                used[todo] = K
+        if return_info:
+            return s, ids, {"pos": pos, "n_distinct": nd, "complete": complete, "hits_used": used}
+        return s, ids
+
+    def search(self, query_vec, top_n: int, index_hit_top_n: Optional[int] = None, widen: bool = False,
+               return_info: bool = False):
+        """search_device() as numpy arrays (the info dict's values included)."""
+        out = self.search_device(query_vec, top_n, index_hit_top_n, widen, return_info)
+        if return_info:
+            return out[0].cpu().numpy(), out[1].cpu().numpy(), {k: v.cpu().numpy() for k, v in out[2].items()}
+        return out[0].cpu().numpy(), out[1].cpu().numpy()
+
+    def save(self, path: str):
+        return self.inner.save(path)
+
+    def load(self, path: str):
+        return self.inner.load(path)

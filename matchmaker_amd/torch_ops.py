@@ -12,7 +12,8 @@ Importing this module defines
                                         B, C, K, saturation)                        -> (score [B], windows [B, W])
     torch.ops.mm_native.colbert_candidates(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T,
                                            c_cap=None)          -> (cand_doc, cand_begin, cand_end, count)
-    torch.ops.mm_native.fp8_quantize_rows(x)                                        -> (codes [T, E] uint8, scales [T])
+    torch.ops.mm_native.distinct_hits(scores, ids, top_n)        -> (scores, ids, pos, n_distinct, n_valid)
+    torch.ops.mm_native.fp8_quantize_rows(x)                                       -> (codes [T, E] uint8, scales [T])
     torch.ops.mm_native.maxsim_ragged_fp8(q, codes, scales, doc_begin, doc_end, q_mask=None, pairs_per_query=1,
                                           check_ranges=True, sim_round=False, sum_round=False) -> [n_pairs]
     torch.ops.mm_native.segment_rank(scores, seg_begin, max_len)                    -> order [N] int32
@@ -467,6 +468,23 @@ def _(hit_rows, begin_sorted, end_sorted, doc_of_sorted, T, c_cap=None):
     C = min(H, begin_sorted.shape[0]) if c_cap is None else c_cap
     return (hit_rows.new_empty((nq, C), dtype=torch.int32), hit_rows.new_empty((nq, C), dtype=torch.int64),
             hit_rows.new_empty((nq, C), dtype=torch.int64), hit_rows.new_empty((nq,), dtype=torch.int32))
+
+
+# ---------------------------------------------------------------------------------------------- MaxP retrieval
+@torch.library.custom_op(_NS + "::distinct_hits", mutates_args=(), device_types="cuda")
+def distinct_hits(scores: Tensor, ids: Tensor, top_n: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(scores [nq, top_n] float32, ids [nq, top_n] int64, pos [nq, top_n] int32, n_distinct [nq] int32, n_valid [nq] int32): the
+    first hit of every document in a query's passage hits (ops.distinct_hits; dense_retrieval.py:414-429).  A selection: no
+    autograd formula."""
+    return ops.distinct_hits(scores, ids, top_n)
+
+
+@distinct_hits.register_fake
+def _(scores, ids, top_n):
+    nq = scores.shape[0]
+    return (scores.new_empty((nq, top_n), dtype=torch.float32), scores.new_empty((nq, top_n), dtype=torch.int64),
+            scores.new_empty((nq, top_n), dtype=torch.int32), scores.new_empty((nq,), dtype=torch.int32),
+            scores.new_empty((nq,), dtype=torch.int32))
 
 
 # ---------------------------------------------------------------------------------------------- fp8 token store
