@@ -1156,6 +1156,78 @@ int mm_distinct_hits_fwd(const float* hit_scores, const int64_t* hit_ids, int nq
                          float* out_scores, int64_t* out_ids, int32_t* out_pos,
                          int32_t* n_distinct, int32_t* n_valid, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * In-batch negatives of dense-retriever training: from the vectors (or the [B, B] score matrices) to the in-batch loss, its
+ * statistics and every gradient, in one fixed linear chain of launches (additive: MM_ABI_VERSION unchanged).  Both entries
+ * run on `stream` with no allocation, no read-back and no atomics, vector stores only: graph-capturable, two calls give the
+ * same bits.  Every output element is written on every successful call.
+ *
+ *   sp [B] = the paired score of (query i, its positive); Sp[i, j] = <Q_i, Dp_j>, Sn[i, j] = <Q_i, Dn_j>; Tp, Tn [B, B] fp32
+ *   teacher scores of the same pairs or both NULL; M = B (B - 1); "off" = every (i, j) with i != j.
+ *   family MM_INBATCH_PAIR, kind = an MM_PAIR_* value:
+ *     loss = (mean_off l(sp_i, Sp_ij; a_i, b_ij) + mean_off l(sp_i, Sn_ij; a_i, b'_ij)) / 2, l = the per-element term of
+ *     mm_pair_loss_fwd with sp in the `pos` role and the in-batch score in the `neg` role (ONE device function serves both
+ *     entries and mm_pair_loss_fwd: float64 terms).  With a teacher a_i = Tp_ii, b_ij = Tp_ij, b'_ij = Tn_ij (every kind with
+ *     two labels); without one the label is 1 (MM_PAIR_RANKNET, MM_PAIR_MARGIN).  A kind with two labels and no teacher, or a
+ *     one-label kind with a teacher, is MM_EINVAL.  The diagonal takes no part; its gradient is written as 0.
+ *   family MM_INBATCH_LIST, kind = an MM_LIST_* value: mm_list_loss_fwd's loss of the lists cat([Sp, Sn], 1) [B, 2B] against
+ *     cat([Tp, Tn], 1), the diagonal included, sp not used (grad_sp = 0); the teacher is required; the same device code as
+ *     mm_list_loss_fwd, reading the two matrices in place.  2B <= MM_LOSS_MAX_LIST, else MM_EUNSUPPORTED before any launch.
+ *   stats [3] fp32, for every kind:
+ *     [0] accuracy    (mean_off [sp_i > Sp_ij] + mean_off [sp_i > Sn_ij]) / 2      (a tie counts as not greater)
+ *     [1] score_diff  (mean_off (sp_i - Sp_ij) + mean_off (sp_i - Sn_ij)) / 2
+ *     [2] teacher accuracy (mean_off [Tp_ii > Tp_ij] + mean_off [Tp_ii > Tn_ij]) / 2 for the pair family with a teacher, else NaN
+ *   Every sum is float64 in a fixed order: per lane, per wavefront, per workgroup, then one workgroup over the workgroups'
+ *   partials; loss and statistics are rounded once to fp32.  B = 0: loss (0 for the Lambda list kinds, as mm_list_loss_fwd) and
+ *   statistics are NaN, one launch, nothing else is written.  B = 1 in the pair family: loss and statistics NaN (means of empty
+ *   sets, as torch), gradients 0.
+ *
+ * mm_inbatch_select_loss_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/train.py:434-438 and :443-472 (the selection of the off-diagonal pairs, the loss calls and the three
+ *           statistics, on score matrices the caller has: train.py:439-440, or ColBERT's forward_inbatch_aggregation)
+ *   sp [B], Sp, Sn [B, B] of `dtype` (MM_F32 / MM_F16 / MM_BF16, widened exactly).  grad_sp [B], grad_Sp, grad_Sn [B, B] of
+ *   `dtype` = d loss / d sp, d Sp, d Sn, each rounded once.  Two launches (three for the list family): the selection kernel
+ *   (32 x 32 tiles, one per wavefront), [the list kernel,] the one-workgroup finish.  0 <= B <= 1024.
+ *   Workspace: mm_inbatch_select_loss_workspace_bytes(B, family) (float64 partials, per-list terms).
+ *
+ * mm_inbatch_dot_loss_fwd (additive: MM_ABI_VERSION unchanged)
+ * Replaces: matchmaker/train.py:434-472 (the two torch.mm included) and the backward of that block in loss.backward()
+ *           (train.py:503-524): two mm, twelve masked indexings with their host synchronisations, three expand copies, two loss calls
+ *   Q, Dp, Dn [B, E] of `dtype`; sp [B] of `sp_dtype` (under autocast 16-bit, else fp32).  grad_Q, grad_Dp, grad_Dn [B, E] of
+ *   `dtype`, grad_sp [B] of `sp_dtype`; each of the four may be NULL and is then not computed; all of grad_Q, grad_Dp, grad_Dn NULL
+ *   skips the gradient launch (loss and statistics only, the same bits).
+ *   1. Scores: Sp = Q Dp^T and Sn = Q Dn^T on the matrix cores, v_mfma_f32_32x32x16_{bf16,f16} for 16-bit vectors (every
+ *      product exact in fp32) and v_mfma_f32_32x32x2_f32 for fp32 vectors (no rounding of the inputs), fp32 accumulation in a
+ *      fixed order inside blocks of 64 k, the blocks added in float64 and S rounded once to fp32.  STATED CHOICE: S stays fp32; it is not rounded to 16 bits as an autocast torch.mm rounds it.  The
+ *      pair-family epilogue runs in the same launch on the accumulator registers: term, statistics, G = d loss / d S (fp32,
+ *      the 1 / (2M) included), one float64 partial set per workgroup, float64 row sums for grad_sp.
+ *   2. List family only: the list kernel on S, writing G.
+ *   3. Finish: one workgroup adds the partials in a fixed order and writes loss, stats and grad_sp.
+ *   4. Gradients, one launch: grad_Q = Gp Dp + Gn Dn, grad_Dp = Gp^T Q, grad_Dn = Gn^T Q with v_mfma_f32_32x32x2_f32 on the
+ *      exactly widened vectors; G is not rounded to 16 bits; each gradient is rounded once to `dtype`.
+ *   The select entry fed this entry's Sp, Sn (the workspace begins with them) gives the same loss, stats and grad_sp bits: both
+ *   walk the elements in the same order.
+ *   1 <= B <= 1024 (list family: 2B <= MM_LOSS_MAX_LIST), 8 <= E <= 1024, rows of 16 bytes (E % 8 == 0 for 16-bit vectors,
+ *   E % 4 == 0 for fp32), else MM_EUNSUPPORTED before any launch; Q, Dp and Dn 16-byte aligned (the
+ *   rows are loaded 16 bytes per lane), else MM_EINVAL.
+ *   Workspace: mm_inbatch_dot_loss_workspace_bytes(B, E, family).  It begins with Sp, Sn [2][B][B] fp32, followed at the next
+ *   multiple of 256 bytes by Gp, Gn [2][B][B] fp32; then the float64 partials and row sums and the per-list terms.
+ *   MM_EINVAL: NULL where required, B < 0, unknown family, kind or dtype, a teacher that does not fit the kind.
+ *   MM_EWORKSPACE: short workspace.
+ */
+#define MM_INBATCH_PAIR 0
+#define MM_INBATCH_LIST 1
+
+size_t mm_inbatch_select_loss_workspace_bytes(int B, int family);
+int mm_inbatch_select_loss_fwd(const void* sp, const void* Sp, const void* Sn, int dtype, const float* Tp, const float* Tn,
+                               int B, int family, int kind, float* loss, float* stats, void* grad_sp, void* grad_Sp,
+                               void* grad_Sn, void* workspace, size_t workspace_bytes, void* stream);
+size_t mm_inbatch_dot_loss_workspace_bytes(int B, int E, int family);
+int mm_inbatch_dot_loss_fwd(const void* Q, const void* Dp, const void* Dn, int dtype, const void* sp, int sp_dtype,
+                            const float* Tp, const float* Tn, int B, int E, int family, int kind, float* loss, float* stats,
+                            void* grad_Q, void* grad_Dp, void* grad_Dn, void* grad_sp, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ from . import ops  # noqa: F401
 
 __all__ = ["ops", "NativeError", "LIB_PATH", "FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer",
            "MaxPIndexer", "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8",
-           "losses", "get_loss", "patch_losses"]
+           "losses", "get_loss", "patch_losses", "inbatch", "InBatchNegatives"]
 
 
 def __getattr__(name):          # the indexers, imported on first use (retrieval pulls in torch.distributed)
@@ -27,6 +27,12 @@ def __getattr__(name):          # the indexers, imported on first use (retrieval
     if name == "losses":        # the native training losses (drop-ins for matchmaker/losses/*.py) and their get_loss
         import importlib
         return importlib.import_module(".losses", __name__)
+    if name == "inbatch":       # the native in-batch negatives of dense-retriever training (train.py:434-472)
+        import importlib
+        return importlib.import_module(".inbatch", __name__)
+    if name == "InBatchNegatives":
+        from .inbatch import InBatchNegatives
+        return InBatchNegatives
     if name == "get_loss":
         from .losses import get_loss
         return get_loss

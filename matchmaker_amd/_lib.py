@@ -63,7 +63,8 @@ for _name in ("MM_F32 MM_F16 MM_BF16 MASK_NONE MASK_LEN_I32 MASK_U8 MASK_I64 MAS
               "STORE_KEEP_ZERO_ROWS ABI_VERSION MM_OK MM_EINVAL MM_EUNSUPPORTED MM_EWORKSPACE MM_ELAUNCH "
               "RANK_MAX_LEN RANK_MAX_CUTOFFS RANK_NOT_JUDGED DISTINCT_MAX_HITS "
               "PAIR_RANKNET PAIR_MARGIN PAIR_MARGIN_MSE PAIR_MSE_POINTWISE PAIR_KLDIV_POINTWISE PAIR_RANKNET_TEACHER PAIR_MSE_RANKNET "
-              "LIST_LISTNET LIST_KLDIV LIST_SMOOTH_MRR LIST_LAMBDA_NDCG2 LIST_LAMBDA_NDCG2_TEACHER LOSS_MAX_LIST").split():
+              "LIST_LISTNET LIST_KLDIV LIST_SMOOTH_MRR LIST_LAMBDA_NDCG2 LIST_LAMBDA_NDCG2_TEACHER LOSS_MAX_LIST "
+              "INBATCH_PAIR INBATCH_LIST").split():
     globals()[_name] = _DEFINES[_name if _name in _DEFINES else "MM_" + _name]
 
 _lib = None

@@ -1257,6 +1257,14 @@ def distinct_hits(scores: torch.Tensor, ids: torch.Tensor, top_n: int):
     return maxp.distinct_hits(scores, ids, top_n)
 
 
+def inbatch_dot_loss(Q, Dp, Dn, sp, Tp, Tn, family, kind, need_grad=True, return_scores=False):
+    """In-batch negatives from the vectors: loss, statistics and every gradient (matchmaker/train.py:434-472; native
+    mm_inbatch_dot_loss_fwd): see matchmaker_amd/inbatch.py, where the torch <-> ABI wrapper lives as the losses' lives in
+    losses.py (the poisoned-memory case of this operator is in tests/test_inbatch_gpu.py)."""
+    from . import inbatch
+    return inbatch.inbatch_dot_loss(Q, Dp, Dn, sp, Tp, Tn, family, kind, need_grad=need_grad, return_scores=return_scores)
+
+
 def store_append(x: torch.Tensor, rows_out: Optional[torch.Tensor], codes_out: Optional[torch.Tensor],
                  scales_out: Optional[torch.Tensor], capacity: int, fill: torch.Tensor, doc_begin: torch.Tensor,
                  doc_end: torch.Tensor, status: torch.Tensor, keep_zero_rows: bool = False) -> None:

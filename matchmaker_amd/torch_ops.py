@@ -19,6 +19,8 @@ Importing this module defines
     torch.ops.mm_native.segment_rank(scores, seg_begin, max_len)                    -> order [N] int32
     torch.ops.mm_native.pair_loss(pos, neg, a, b, kind)                             -> (loss [], grad_pos, grad_neg)
     torch.ops.mm_native.list_loss(scores, labels, kind)                             -> (loss [], per_list [B], grad [B, L])
+    torch.ops.mm_native.inbatch_dot_loss(q, dp, dn, sp, tp, tn, family, kind)       -> (loss [], stats [3], grad_q, grad_dp, grad_dn, grad_sp)
+    torch.ops.mm_native.inbatch_select_loss(sp, s_pos, s_neg, tp, tn, family, kind) -> (loss [], stats [3], grad_sp, grad_s_pos, grad_s_neg)
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
@@ -600,3 +602,60 @@ def _list_loss_backward(ctx, g_loss, g_per_list, _ggrad):
 
 
 list_loss.register_autograd(_list_loss_backward, setup_context=_list_loss_setup)
+
+
+# ---------------------------------------------------------------------------------------------- in-batch negatives
+from . import inbatch as _inbatch  # noqa: E402
+
+
+@torch.library.custom_op(_NS + "::inbatch_dot_loss", mutates_args=(), device_types="cuda")
+def inbatch_dot_loss(q: Tensor, dp: Tensor, dn: Tensor, sp: Tensor, tp: Optional[Tensor], tn: Optional[Tensor], family: int,
+                     kind: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(loss [], stats [3], grad_q, grad_dp, grad_dn, grad_sp): the in-batch negatives of train.py:434-472 from the vectors
+    (inbatch.inbatch_dot_loss; family = inbatch.FAMILIES value, kind = a value of losses.PAIR_KINDS / LIST_KINDS).
+    Differentiable in q, dp, dn and sp through `loss`; the teacher matrices get no gradient."""
+    return _inbatch.inbatch_dot_loss(q, dp, dn, sp, tp, tn, family, kind)
+
+
+@inbatch_dot_loss.register_fake
+def _(q, dp, dn, sp, tp, tn, family, kind):
+    return (q.new_empty((), dtype=torch.float32), q.new_empty((3,), dtype=torch.float32), q.new_empty(q.shape), dp.new_empty(q.shape),
+            dn.new_empty(q.shape), sp.new_empty(sp.shape))
+
+
+def _inbatch_dot_setup(ctx, inputs, output):
+    ctx.save_for_backward(*output[2:])
+    ctx.mark_non_differentiable(*output[1:])
+
+
+def _inbatch_dot_backward(ctx, g, *_unused):
+    return tuple(_inbatch._scaled(t, g, True) for t in ctx.saved_tensors) + (None,) * 4
+
+
+inbatch_dot_loss.register_autograd(_inbatch_dot_backward, setup_context=_inbatch_dot_setup)
+
+
+@torch.library.custom_op(_NS + "::inbatch_select_loss", mutates_args=(), device_types="cuda")
+def inbatch_select_loss(sp: Tensor, s_pos: Tensor, s_neg: Tensor, tp: Optional[Tensor], tn: Optional[Tensor], family: int,
+                        kind: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """(loss [], stats [3], grad_sp, grad_s_pos, grad_s_neg): the in-batch negatives over [B, B] score matrices
+    (inbatch.inbatch_select_loss).  Differentiable in sp, s_pos and s_neg through `loss`."""
+    return _inbatch.inbatch_select_loss(sp, s_pos, s_neg, tp, tn, family, kind)
+
+
+@inbatch_select_loss.register_fake
+def _(sp, s_pos, s_neg, tp, tn, family, kind):
+    return (sp.new_empty((), dtype=torch.float32), sp.new_empty((3,), dtype=torch.float32), sp.new_empty(sp.shape),
+            s_pos.new_empty(s_pos.shape), s_neg.new_empty(s_pos.shape))
+
+
+def _inbatch_select_setup(ctx, inputs, output):
+    ctx.save_for_backward(*output[2:])
+    ctx.mark_non_differentiable(*output[1:])
+
+
+def _inbatch_select_backward(ctx, g, *_unused):
+    return tuple(_inbatch._scaled(t, g, True) for t in ctx.saved_tensors) + (None,) * 4
+
+
+inbatch_select_loss.register_autograd(_inbatch_select_backward, setup_context=_inbatch_select_setup)
