@@ -393,6 +393,15 @@ int mm_tkl_fwd_peaks(const void* q_ctx, const void* chunks, const float* chunk_m
  *   grad_out [B];  grad_q [B, Q, E];  grad_chunks [P, 50, E] (zeroed by the call; only rows of selected windows are non-zero);
  *   grad_params [B, MM_TKL_NPARAMS(K, E)]: per-document gradients in the layout of `params` (mu / sigma columns are 0) —
  *   sum over the documents on the host side (deterministic, no atomics).  Q <= 32.
+ * Exact zeros: every row of grad_chunks that none of the document's 15 selected windows reads (the 5 + 5 overlap rows of every
+ *   chunk among them) is +0.0 bit for bit, on every kernel below; so is a padding row inside a selected window.
+ * Kernels (the same gradients within fp32 rounding; Q > 32 or K != 11: MM_EUNSUPPORTED, nothing written):
+ *   E <= 320        tiled kernel, five 16-byte chunks of a block of rows per thread    } E % 4 == 0, q_ctx / chunks / params /
+ *   320 < E <= 512  tiled kernel, eight chunks per thread                              } grad_q / grad_chunks 16-byte aligned, and
+ *                   the tiles fit 150 KiB of LDS (Q = 32 at E = 512 does not; Q = 12 does)
+ *   anything else   the per-element kernel, one workgroup per document (E > 512, or MM_KP_BWD_UNTILED=1 in the environment)
+ *   The tiled kernels run three workgroups per document while 3 B <= the device's CUs and the workspace has
+ *   mm_tkl_bwd_workspace_bytes2 bytes, else (or with MM_TKL_BWD_NOSPLIT=1) one: grad_chunks bit-equal between the two.
  * Workspace: mm_tkl_bwd_workspace_bytes(B, C). */
 size_t mm_tkl_bwd_workspace_bytes(int64_t B, int C);
 /* ... plus the per-region shares of grad_q and of the parameter rows of a small batch (3 B <= 256: three workgroups per document,
