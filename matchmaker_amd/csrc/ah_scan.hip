@@ -94,28 +94,21 @@ __global__ void __launch_bounds__(256) ah_score_kernel(const IvfArgs a, int roun
       f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
 #pragma unroll
       for (int s = 0; s < KS; s += 2) {
-        acc0 = IvfMfma<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
-        acc1 = IvfMfma<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
+        acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
+        acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
       }
       if (t0 + r < nqs) {
         const float ps = a.probe_scores[p];
         float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+          const int row = rowof(i) + 4 * h;
           if (row < rows) dst[row] = ps + (acc0[i] + acc1[i]);
         }
       }
     }
   }
 }
-
-template <int DT>
-__device__ __forceinline__ float to_f32(short v);
-template <>
-__device__ __forceinline__ float to_f32<MM_F16>(short v) { return (float)__builtin_bit_cast(_Float16, v); }
-template <>
-__device__ __forceinline__ float to_f32<MM_BF16>(short v) { return __uint_as_float((uint32_t)(uint16_t)v << 16); }
 
 // Workgroup = 64 (query, row) pairs of ONE query: 16 lanes per pair, 16 pairs at a time, four passes.
 template <int DT, int NSL>
@@ -145,7 +138,7 @@ __global__ void __launch_bounds__(256) gather_dot_kernel(const void* queries, co
 #pragma unroll
     for (int i = 0; i < NSL; ++i)
 #pragma unroll
-      for (int e = 0; e < 8; ++e) acc = fmaf(to_f32<DT>(x[u][i][e]), to_f32<DT>(qf[i][e]), acc);
+      for (int e = 0; e < 8; ++e) acc = fmaf(bits_to_f32<DT>((uint16_t)x[u][i][e]), bits_to_f32<DT>((uint16_t)qf[i][e]), acc);
 #pragma unroll
     for (int m = 8; m >= 1; m >>= 1) acc += __shfl_xor(acc, m, 16);
     if (c == 0 && j0 + u < R) out[(int64_t)q * R + j0 + u] = ok[u] ? acc : neg_inf();

@@ -41,12 +41,6 @@ struct CandArgs {
   int32_t* ws;          // [gridDim.x, n2] the distinct sorted-view positions of the query a workgroup works on
 };
 
-static int cand_pow2_ge(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
-}
-
 // Owner of `row`: the last j with dbeg[j] <= row owns it when row < dend[j] (zero-length documents sort in front of a
 // document that shares their begin, so they never own a row).  Fixed step count and no data-dependent branch: the U
 // searches of a lane run side by side and their loads overlap.  Every load index is below n_docs whatever `row` is.
@@ -189,7 +183,7 @@ using namespace mm;
 extern "C" size_t mm_colbert_candidates_workspace_bytes(int nq, int H) {
   if (nq <= 0 || H < 1 || H > kCandMaxH) return 0;
   const int grid = nq < kCandMaxGrid ? nq : kCandMaxGrid;
-  return (size_t)grid * cand_pow2_ge(H) * sizeof(int32_t);
+  return (size_t)grid * pow2_ge(H) * sizeof(int32_t);
 }
 
 extern "C" int mm_colbert_candidates(const int64_t* hit_rows, const int64_t* doc_begin_sorted, const int64_t* doc_end_sorted,
@@ -214,7 +208,7 @@ extern "C" int mm_colbert_candidates(const int64_t* hit_rows, const int64_t* doc
   CandArgs a{};
   a.hit = hit_rows; a.dbeg = doc_begin_sorted; a.dend = doc_end_sorted; a.doc_of = doc_of_sorted;
   a.n_docs = n_docs; a.T = T; a.nq = nq; a.H = H; a.C_cap = C_cap;
-  a.n2 = cand_pow2_ge(H);
+  a.n2 = pow2_ge(H);
   a.top = 1;
   while (a.top * 2 <= n_docs) a.top *= 2;
   a.cand_doc = cand_doc; a.cand_begin = cand_begin; a.cand_end = cand_end; a.cand_count = cand_count;

@@ -34,6 +34,8 @@
 // different query groups at about the same time, so the collection is fetched from HBM once per
 // XCD sweep and re-read from that XCD's L2.
 #include "mm_internal.h"
+#include "elem_device.h"
+#include "bitonic_device.h"
 #include <type_traits>
 
 namespace mm {
@@ -65,23 +67,6 @@ struct DotArgs {
   double expect;      // FILTER: expected fraction of a query's scores above its threshold
   unsigned long long* prof;  // optional [grid * 4 wavefronts][8] cycle counters (MM_DOT_PROF=1, tools only)
 };
-
-template <int DT>
-struct DotMfma;
-template <>
-struct DotMfma<MM_BF16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <>
-struct DotMfma<MM_F16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
-
-__device__ __forceinline__ constexpr int drowof(int i) { return (i & 3) + 8 * (i >> 2); }
 
 // 8 x 16 B of one query row slice (256 B): chunks (2kk + h).  NO wait inside: the prologue requests every slice of both query
 // tiles (96 loads per lane at dim 768) and waits once (dot_q_landed) — a wait per slice made the prologue twelve dependent round
@@ -236,7 +221,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
       const int ls = (int)(code & 63u), e = (int)((code >> 6) & 31u);
       const int qq = q0 + 32 * (e >> 4) + (ls & 31);
       if (qq >= a.nq) continue;   // (a query past the end has tau = +inf: only an infinite score gets here)
-      const int doc = (int32_t)(((b_base + (int64_t)(code >> 11)) * 32 + 4 * (ls >> 5) + drowof(e & 15)) * a.stride);
+      const int doc = (int32_t)(((b_base + (int64_t)(code >> 11)) * 32 + 4 * (ls >> 5) + rowof(e & 15)) * a.stride);
       const int slot = atomicAdd(a.count + qq, 1);
       if ((unsigned)slot < (unsigned)a.cap) {
         a.cand_score[(int64_t)qq * a.cap + slot] = __uint_as_float(ent.x);
@@ -392,7 +377,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
     if (!whole) {   // wave-uniform, the shard's last block only: documents past the end do not exist
       uint32_t exist = 0;
 #pragma unroll
-      for (int i = 0; i < 16; ++i) exist |= (d0 + drowof(i) < a.ndocs) ? (0x00010001u << i) : 0u;
+      for (int i = 0; i < 16; ++i) exist |= (d0 + rowof(i) < a.ndocs) ? (0x00010001u << i) : 0u;
       pmask &= exist;
     }
 #if defined(MM_DOT_CUT) && MM_DOT_CUT == 1   // by-removal timing builds (tools/build_variant.sh; results are wrong)
@@ -459,9 +444,9 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
 #endif
 #pragma unroll
 #if defined(MM_DOT_CUT) && MM_DOT_CUT == 7   // no matrix work: every fourth step keeps the operands alive
-      for (int n = 0; n < NQT; ++n) if ((s & 3) == 0) acc[n] = DotMfma<DT>::run(av[s % (AHEAD + 1)], qf[n][s >> 3][s & 7], acc[n]); else asm volatile("" :: "v"(av[s % (AHEAD + 1)]), "v"(qf[n][s >> 3][s & 7]));
+      for (int n = 0; n < NQT; ++n) if ((s & 3) == 0) acc[n] = Mfma32x16<DT>::run(av[s % (AHEAD + 1)], qf[n][s >> 3][s & 7], acc[n]); else asm volatile("" :: "v"(av[s % (AHEAD + 1)]), "v"(qf[n][s >> 3][s & 7]));
 #else
-      for (int n = 0; n < NQT; ++n) acc[n] = DotMfma<DT>::run(av[s % (AHEAD + 1)], qf[n][s >> 3][s & 7], acc[n]);
+      for (int n = 0; n < NQT; ++n) acc[n] = Mfma32x16<DT>::run(av[s % (AHEAD + 1)], qf[n][s >> 3][s & 7], acc[n]);
 #endif
       __builtin_amdgcn_sched_group_barrier(0x008, NQT, 0);  // NQT MFMAs of step s
       __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);    // then the read for step s + AHEAD
@@ -539,7 +524,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
       tp[2] += t3 - t2; tp[3] += t4 - t3;
     }
 
-    // ---- epilogue: acc[n][i] = <document b*32 + drowof(i) + 4h, query qid[n]> ----------------------
+    // ---- epilogue: acc[n][i] = <document b*32 + rowof(i) + 4h, query qid[n]> ----------------------
     const int64_t d0 = b * 32 + 4 * h;
     if (MODE == DOT_SAMPLE) {
 #pragma unroll
@@ -657,14 +642,7 @@ __device__ __forceinline__ void bitonic_desc(float* key, int* val, int n2, int t
 }
 
 // m-th largest of a row of n <= 16384 sample scores -> tau[row].  Values stay in registers (16 per
-// thread) as order-preserving integers.
-__device__ __forceinline__ uint32_t f2ord(float f) {  // larger float <=> larger unsigned
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ord2f(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+// thread) as order-preserving integers (asc_key of bitonic_device.h: larger float <=> larger unsigned).
 
 // The m-th largest of NK keys per thread x 1,024 threads, one byte per pass: a pass counts the keys that match the prefix found
 // so far into a 256-bin LDS histogram, wavefront 0 scans it from the top.  Bytes on which all keys agree (kmax / kmin: bounds
@@ -732,7 +710,7 @@ __global__ void __launch_bounds__(1024) sample_tau_kernel(const float* __restric
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
     const int i = tid + 1024 * e;
-    key[e] = i < n ? f2ord(all[(int64_t)row * ld + i]) : 0u;  // 0 sorts below every real value (incl. -inf)
+    key[e] = i < n ? asc_key(all[(int64_t)row * ld + i]) : 0u;  // 0 sorts below every real value (incl. -inf)
     kmax = key[e] > kmax ? key[e] : kmax;
     kmin = key[e] < kmin ? key[e] : kmin;
   }
@@ -773,14 +751,14 @@ __global__ void __launch_bounds__(1024) sample_tau_kernel(const float* __restric
           const uint32_t o = cand[j];
           rank += (o > mine || (o == mine && j < tid)) ? 1 : 0;
         }
-        if (rank == m - 1) tau[row] = ord2f(mine);
+        if (rank == m - 1) tau[row] = asc_unkey(mine);
       }
       return;
     }
     __syncthreads();
   }
   const uint32_t prefix = radix_mth_largest<16>(key, m, kmax, kmin, hist, misc, tid, lane);
-  if (tid == 0) tau[row] = ord2f(prefix);
+  if (tid == 0) tau[row] = asc_unkey(prefix);
 }
 
 // (score descending, index ascending) bitonic sort of 1024 entries held ONE PER THREAD: the 45 stages whose partner
@@ -854,7 +832,7 @@ __global__ void __launch_bounds__(1024) topk_rows_kernel(const float* __restrict
     // ---- (1) select the k-th largest key --------------------------------------------------------
     uint32_t kmax = 0u, kmin = 0xffffffffu;
     for (int i = tid; i < n; i += 1024) {
-      const uint32_t o = f2ord(key[i]);
+      const uint32_t o = asc_key(key[i]);
       kmax = o > kmax ? o : kmax;
       kmin = o < kmin ? o : kmin;
     }
@@ -883,7 +861,7 @@ __global__ void __launch_bounds__(1024) topk_rows_kernel(const float* __restrict
       __syncthreads();
       const uint32_t hi_mask = shift == 24 ? 0u : (0xffffffffu << (shift + 8));
       for (int i = tid; i < n; i += 1024) {
-        const uint32_t o = f2ord(key[i]);
+        const uint32_t o = asc_key(key[i]);
         if ((o & hi_mask) == (prefix & hi_mask)) atomicAdd(&hist[(o >> shift) & 0xffu], 1);
       }
       __syncthreads();
@@ -918,7 +896,7 @@ __global__ void __launch_bounds__(1024) topk_rows_kernel(const float* __restrict
     const uint32_t thr = prefix;
     for (int i = tid; i < n; i += 1024) {
       const float kf = key[i];
-      if (f2ord(kf) >= thr) {
+      if (asc_key(kf) >= thr) {
         const int pos = atomicAdd(&misc[2], 1);
         if (pos < kSelMax) {
           skey[pos] = kf;
@@ -971,7 +949,6 @@ __global__ void __launch_bounds__(256) fill_tau_kernel(float* tau, int n, float 
   if (i < n) tau[i] = v;
 }
 
-static int pow2_ge(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 // Launch geometry of one call: NQT query tiles per wavefront, query groups of 128 * NQT, at most 32
 // groups per launch (one per CU of an XCD), T sub-slices per XCD.

@@ -22,6 +22,8 @@
 // flight, fp32 accumulation, cross-lane reduction; the query's chunks stay in registers for the whole call.  The merge
 // is a bitonic sort of the new pairs (descending) and a bitonic merge with L.  No MFMA, plain vector stores only.
 #include "mm_internal.h"
+#include "elem_device.h"
+#include "bitonic_device.h"
 
 namespace mm {
 
@@ -51,16 +53,6 @@ struct GsArgs {
   int32_t* stats;           // [nq, 2] or null
 };
 
-// order-preserving key of a score, ASCENDING key = DESCENDING score (-0 counts as +0)
-__device__ __forceinline__ uint32_t gs_key(float s) {
-  const uint32_t u = __float_as_uint(s + 0.0f);
-  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
-__device__ __forceinline__ float gs_unkey(uint32_t k) {
-  const uint32_t m = ~k;
-  return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
-}
-
 template <int DT>
 __device__ __forceinline__ float gs_dot8(short8 a, short8 b, float acc);
 template <>
@@ -74,7 +66,7 @@ template <>
 __device__ __forceinline__ float gs_dot8<MM_BF16>(short8 a, short8 b, float acc) {
 #pragma unroll
   for (int i = 0; i < 8; ++i)
-    acc = __builtin_fmaf(__uint_as_float((uint32_t)(uint16_t)a[i] << 16), __uint_as_float((uint32_t)(uint16_t)b[i] << 16), acc);
+    acc = __builtin_fmaf(bits_to_f32<MM_BF16>((uint16_t)a[i]), bits_to_f32<MM_BF16>((uint16_t)b[i]), acc);
   return acc;
 }
 
@@ -118,8 +110,8 @@ __device__ __forceinline__ void gs_score(const GsArgs& a, const short8 (&qv)[NSL
       s1 += __shfl_xor(s1, o, 64);
     }
     if (gl == 0) {
-      if (i0 < C) nk[i0] = ((unsigned long long)gs_key(s0) << 32) | ((unsigned long long)r0 << 1);
-      if (i1 < C) nk[i1] = ((unsigned long long)gs_key(s1) << 32) | ((unsigned long long)r1 << 1);
+      if (i0 < C) nk[i0] = ((unsigned long long)desc_key(s0) << 32) | ((unsigned long long)r0 << 1);
+      if (i1 < C) nk[i1] = ((unsigned long long)desc_key(s1) << 32) | ((unsigned long long)r1 << 1);
     }
   }
 }
@@ -249,7 +241,7 @@ __global__ void __launch_bounds__(kGsThreads) graph_search_kernel(const GsArgs a
     for (int i = tid; i < a.k; i += kGsThreads) {
       const unsigned long long e = L[i];
       const bool ok = e != kGsEmpty;
-      a.out_s[(int64_t)q * a.k + i] = ok ? gs_unkey((uint32_t)(e >> 32)) : neg_inf();
+      a.out_s[(int64_t)q * a.k + i] = ok ? desc_unkey((uint32_t)(e >> 32)) : neg_inf();
       a.out_r[(int64_t)q * a.k + i] = ok ? (int64_t)((uint32_t)e >> 1) : -1;
     }
     if (a.stats && tid == 0) {
@@ -258,12 +250,6 @@ __global__ void __launch_bounds__(kGsThreads) graph_search_kernel(const GsArgs a
     }
     __syncthreads();
   }
-}
-
-static int64_t gs_pow2_ge(int64_t v) {
-  int64_t p = 1;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 // the largest visited table the envelope allows is 2^28 slots: its size fits an int
@@ -278,15 +264,15 @@ struct GsGeom {
 static GsGeom gs_geom(int64_t n, int nq, int M, int ef, int width, int n_entry, int max_iters) {
   GsGeom g;
   const int wm = width * M;
-  g.ccap = (int)gs_pow2_ge(wm > n_entry ? wm : n_entry);
-  const int ef2 = (int)gs_pow2_ge(ef);
+  g.ccap = (int)pow2_ge<int64_t>(wm > n_entry ? wm : n_entry);
+  const int ef2 = (int)pow2_ge<int64_t>(ef);
   g.lcap = ef2 > g.ccap ? ef2 : g.ccap;
   // rows a query can visit: the placement goes by the bound of the call's parameters alone, the size of a slice in the
   // workspace also knows that no more than n distinct rows exist
   const int64_t bound = (int64_t)n_entry + (int64_t)max_iters * wm;
   g.lds_table = 2 * bound <= kGsLdsSlots;
   const int64_t need = g.lds_table ? bound : (bound < n ? bound : n);
-  g.slots = (int)gs_pow2_ge(2 * (need > 32 ? need : 32));     // <= 2^28, see above
+  g.slots = (int)pow2_ge<int64_t>(2 * (need > 32 ? need : 32));     // <= 2^28, see above
   g.grid = nq < kGsMaxGrid ? nq : kGsMaxGrid;
   g.lds = (size_t)g.lcap * 8 + (size_t)g.ccap * 8 + (kGsMaxWidth + 8) * 4 + (g.lds_table ? (size_t)g.slots * 4 : 0);
   return g;

@@ -44,8 +44,6 @@ struct IbArgs {
   double* rowpart;     // [column tiles][B]
 };
 
-__device__ __forceinline__ int ib_row(int v, int h) { return (v & 3) + 8 * (v >> 2) + 4 * h; }      // row of accumulator register v
-
 // s: the wavefront's 32 x 32 tile of cat([Sp, Sn], 1) at (row0, col0) in the accumulator layout.  red: 16 doubles of LDS.
 __device__ __forceinline__ void ib_epilogue(const IbArgs& A, const f32x16& s, int row0, int col0, double* red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
@@ -56,12 +54,12 @@ __device__ __forceinline__ void ib_epilogue(const IbArgs& A, const f32x16& s, in
   double acc[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int i = row0 + ib_row(v, h);
+    const int i = row0 + (rowof(v) + 4 * h);
     const bool in = cin && i < B, off = in && i != j;
     double rs = 0.0;
     float gv = 0.0f;
     if (off) {
-      const double p = (double)ld_score(A.sp, A.spdt, i), g = (double)s[v];
+      const double p = (double)load_elem(A.sp, A.spdt, i), g = (double)s[v];
       acc[1] += p > g ? 1.0 : 0.0;
       acc[2] += p - g;
       if (pair) {
@@ -98,19 +96,10 @@ __device__ __forceinline__ void ib_epilogue(const IbArgs& A, const f32x16& s, in
 }
 
 template <int DT>
-struct IbMfma;
-template <>
-struct IbMfma<MM_BF16> {
+struct IbMfma {      // the 16-bit types
   static constexpr int STEP = 16;      // k per step; a lane half supplies 8 of them: 16 bytes
   static __device__ __forceinline__ f32x16 run(const f32x4& a, const f32x4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <>
-struct IbMfma<MM_F16> {
-  static constexpr int STEP = 16;
-  static __device__ __forceinline__ f32x16 run(const f32x4& a, const f32x4& b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    return Mfma32x16<DT>::run(__builtin_bit_cast(short8, a), __builtin_bit_cast(short8, b), c);
   }
 };
 template <>
@@ -171,8 +160,8 @@ __global__ void __launch_bounds__(256) ib_select_kernel(const IbArgs A) {
   f32x16 s = {0};
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int i = row0 + ib_row(v, h);
-    if (c < 2 * B && i < B) s[v] = ld_score(c >= B ? A.Sn : A.Sp, A.sdt, (int64_t)i * B + (c >= B ? c - B : c));
+    const int i = row0 + (rowof(v) + 4 * h);
+    if (c < 2 * B && i < B) s[v] = load_elem(c >= B ? A.Sn : A.Sp, A.sdt, (int64_t)i * B + (c >= B ? c - B : c));
   }
   ib_epilogue(A, s, row0, col0, red);
 }
@@ -251,7 +240,7 @@ __global__ void __launch_bounds__(64) ib_grad_kernel(const IbGradArgs A) {
     const bool second = z == 0 && kc >= B;
     const int kr = second ? kc - B : kc;      // the row of its matrix
     float a = z == 0 ? (second ? A.Gn : A.Gp)[(int64_t)rc * B + kr] : (z == 1 ? A.Gp : A.Gn)[(int64_t)kr * B + rc];
-    float b = ld_score(z == 0 ? (second ? A.Dn : A.Dp) : A.Q, A.vdt, (int64_t)kr * E + (ein ? e : 0));
+    float b = load_elem(z == 0 ? (second ? A.Dn : A.Dp) : A.Q, A.vdt, (int64_t)kr * E + (ein ? e : 0));
     if (!kin || !rin) a = 0.0f;
     if (!kin || !ein) b = 0.0f;
     acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
@@ -259,7 +248,7 @@ __global__ void __launch_bounds__(64) ib_grad_kernel(const IbGradArgs A) {
   if (!ein) return;
 #pragma unroll
   for (int v = 0; v < 16; ++v) {
-    const int i = blockIdx.y * 32 + ib_row(v, h);
+    const int i = blockIdx.y * 32 + (rowof(v) + 4 * h);
     if (i < B) st_grad(A.out[z], A.vdt, (int64_t)i * E + e, acc[v]);
   }
 }

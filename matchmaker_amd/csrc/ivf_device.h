@@ -6,6 +6,8 @@
 // includes this header gets its own copy of the small ones.
 #pragma once
 #include "mm_internal.h"
+#include "elem_device.h"
+#include "bitonic_device.h"
 
 namespace mm {
 namespace ivf_dev {
@@ -186,31 +188,6 @@ static __global__ void __launch_bounds__(1024) ivf_lscan_kernel(const IvfArgs a,
   block_excl_scan<int>([&](int l) { return a.cnt[l]; }, [&](int l, int v) { a.start[l] = v; }, a.nlist, sh);
 }
 
-template <int DT>
-struct IvfMfma;
-template <>
-struct IvfMfma<MM_BF16> {
-  static __device__ __forceinline__ f32x16 run(short8 x, short8 y, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x), __builtin_bit_cast(bf16x8, y), c, 0, 0, 0);
-  }
-};
-template <>
-struct IvfMfma<MM_F16> {
-  static __device__ __forceinline__ f32x16 run(short8 x, short8 y, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, x), __builtin_bit_cast(f16x8, y), c, 0, 0, 0);
-  }
-};
-
-// order-preserving key of a score, ASCENDING key = DESCENDING score (-0 counts as +0)
-__device__ __forceinline__ uint32_t ivf_key(float s) {
-  const uint32_t u = __float_as_uint(s + 0.0f);
-  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
-__device__ __forceinline__ float ivf_unkey(uint32_t k) {
-  const uint32_t m = ~k;
-  return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
-}
-
 // The `want`-th smallest key (want >= 1) among the elements i < n with ok(i), by ONE workgroup: 4 passes of 8 bits.
 // Returns the key; *below = elements with a smaller key, *ties = elements with that key.
 template <typename OK, typename KEY>
@@ -280,17 +257,17 @@ static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a
   __syncthreads();
   const int kk = C < k ? C : k;
   if (C <= k) {
-    for (int i = tid; i < C; i += 1024) sel[i] = ((unsigned long long)ivf_key(row[i]) << 32) | vrow(i);
+    for (int i = tid; i < C; i += 1024) sel[i] = ((unsigned long long)desc_key(row[i]) << 32) | vrow(i);
   } else {
     int below, ties;
-    const uint32_t T = ivf_radix_kth(C, k, [&](int) { return true; }, [&](int i) { return ivf_key(row[i]); }, hist, sh, &below, &ties);
+    const uint32_t T = ivf_radix_kth(C, k, [&](int) { return true; }, [&](int i) { return desc_key(row[i]); }, hist, sh, &below, &ties);
     uint32_t Trow = 0xffffffffu;
     if (below + ties > k) {   // more candidates tie with the k-th score than fit: the lower rows win
       int b2, t2;
-      Trow = ivf_radix_kth(C, k - below, [&](int i) { return ivf_key(row[i]) == T; }, vrow, hist, sh, &b2, &t2);
+      Trow = ivf_radix_kth(C, k - below, [&](int i) { return desc_key(row[i]) == T; }, vrow, hist, sh, &b2, &t2);
     }
     for (int i = tid; i < C; i += 1024) {
-      const uint32_t kx = ivf_key(row[i]);
+      const uint32_t kx = desc_key(row[i]);
       if (kx > T) continue;
       const uint32_t vr = vrow(i);
       if (kx == T && vr > Trow) continue;
@@ -298,32 +275,13 @@ static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a
       if (slot < k) sel[slot] = ((unsigned long long)kx << 32) | vr;   // (slot >= k: only with a list probed twice)
     }
   }
-  __syncthreads();
-  // bitonic sort, ascending
-  for (int size = 2; size <= k2; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < k2; i += 1024) {
-        const int j = i ^ stride;
-        if (j > i) {
-          const unsigned long long x = sel[i], y = sel[j];
-          const bool up = (i & size) == 0;
-          if ((x > y) == up) { sel[i] = y; sel[j] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_asc(sel, k2, tid, 1024);      // (its first barrier orders the selection's writes before the sort)
   for (int i = tid; i < k; i += 1024) {
     const unsigned long long e = sel[i];
     const bool okv = i < kk && e != ~0ull;
-    a.out_s[(int64_t)q * k + i] = okv ? ivf_unkey((uint32_t)(e >> 32)) : neg_inf();
+    a.out_s[(int64_t)q * k + i] = okv ? desc_unkey((uint32_t)(e >> 32)) : neg_inf();
     a.out_r[(int64_t)q * k + i] = okv ? (int64_t)(uint32_t)e : -1;
   }
-}
-
-inline int pow2_ge_i(int v) {
-  int p = 1;
-  while (p < v) p <<= 1;
-  return p;
 }
 
 // The workspace of a scan, stated once: block by block in the order of IvfArgs.  On a measuring cursor this leaves the size in
@@ -381,7 +339,7 @@ int ivf_run(IvfArgs a, WsCursor ws, hipStream_t stream, const char* what, Score 
   hipLaunchKernelGGL(ivf_chunks_kernel, dim3(1), dim3(1024), 0, stream, a, g.rounds);
   if (int e = check_launch(what)) return e;
 
-  const int k2 = pow2_ge_i(k);
+  const int k2 = pow2_ge(k);
   const size_t lds_sel = (size_t)k2 * 8 + 256 * 4 + 32;
   const unsigned grid_pairs = (unsigned)((pairs + 255) / 256 < 4096 ? (pairs + 255) / 256 : 4096);
   for (int r = 0; r < g.rounds; ++r) {

@@ -76,14 +76,14 @@ __global__ void __launch_bounds__(256) ivf_score_kernel(const IvfArgs a, int rou
     f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
 #pragma unroll
     for (int s = 0; s < KS; s += 2) {
-      acc0 = IvfMfma<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
-      acc1 = IvfMfma<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
+      acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
+      acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
     }
     if (t0 + r < nqs) {
       float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int row = rowof(i) + 4 * h;
         if (row < rows) dst[row] = acc0[i] + acc1[i];
       }
     }

@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(256) ivf_fp8_score_kernel(const IvfArgs a, int
     // lane r (h = 0) holds the scale of row r; register i of a lane is row (i & 3) + 8 (i >> 2) + 4 h
     const float mine = h == 0 ? a.scales[trow] : 0.0f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) sc[i] = __shfl(mine, (i & 3) + 8 * (i >> 2) + 4 * h, 64);
+    for (int i = 0; i < 16; ++i) sc[i] = __shfl(mine, rowof(i) + 4 * h, 64);
   }
   const int32_t* pl = a.pairs + a.start[l];
   for (int t0 = 0; t0 < nqs; t0 += 32) {
@@ -72,14 +72,14 @@ __global__ void __launch_bounds__(256) ivf_fp8_score_kernel(const IvfArgs a, int
     f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
 #pragma unroll
     for (int s = 0; s < KS; s += 2) {
-      acc0 = IvfMfma<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
-      acc1 = IvfMfma<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
+      acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
+      acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
     }
     if (t0 + r < nqs) {
       float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int row = rowof(i) + 4 * h;
         if (row < rows) dst[row] = (acc0[i] + acc1[i]) * sc[i];
       }
     }

@@ -27,6 +27,7 @@
 //                            longer list go to the workspace.
 //     kms_combine_kernel     one workgroup per list: zeros for an empty list, the chunks of a long list added in ascending order
 #include "mm_internal.h"
+#include "elem_device.h"
 
 namespace mm {
 
@@ -35,26 +36,8 @@ constexpr int kKmSplit = 512;     // rows per chunk of the segment sum
 constexpr int kKmTile = 128;      // rows of x per workgroup of the assignment (4 wavefronts x 32)
 constexpr int kKmBlock = 32;      // centroids per LDS block
 
-template <int DT>
-struct KmMfma;
-template <>
-struct KmMfma<MM_BF16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float to_f32(unsigned short u) { return __uint_as_float((uint32_t)u << 16); }
-};
-template <>
-struct KmMfma<MM_F16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-  static __device__ __forceinline__ float to_f32(unsigned short u) { return (float)__builtin_bit_cast(_Float16, u); }
-};
-
 // A = the centroid block from LDS (lane (r, h): centroid c0 + r, elements 16 s + 8 h .. + 7 of k-step s), B = the wavefront's 32
-// rows of x (lane (r, h): row r, same elements); D: lane's column = its row of x, register i = centroid c0 + (i & 3) + 8 (i >> 2)
-// + 4 h.
+// rows of x (lane (r, h): row r, same elements); D: lane's column = its row of x, register i = centroid c0 + rowof(i) + 4 h.
 template <int DT, int NSL>
 __global__ void __launch_bounds__(256) kmeans_assign_kernel(const void* __restrict__ x, const void* __restrict__ cent, int64_t n,
                                                             int nlist, int32_t* __restrict__ out_list,
@@ -109,18 +92,18 @@ __global__ void __launch_bounds__(256) kmeans_assign_kernel(const void* __restri
     const char* arow = smem + (b & 1) * (kKmBlock * LROW) + r * LROW + h * 16;
     f32x16 acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
-    for (int s = 0; s < KS; ++s) acc = KmMfma<DT>::run(*(const short8*)(arow + s * 32), bf[s], acc);
+    for (int s = 0; s < KS; ++s) acc = Mfma32x16<DT>::run(*(const short8*)(arow + s * 32), bf[s], acc);
     if (c0 + kKmBlock <= nlist) {
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const int c = c0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        const int c = c0 + rowof(i) + 4 * h;
         if (acc[i] > best) { best = acc[i]; arg = c; }
       }
     } else {
       // the repeated last centroid keeps its own number: a copy can tie with it but never replace a lower centroid
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        int c = c0 + (i & 3) + 8 * (i >> 2) + 4 * h;
+        int c = c0 + rowof(i) + 4 * h;
         c = c < nlist ? c : nlist - 1;
         if (acc[i] > best) { best = acc[i]; arg = c; }
       }
@@ -227,7 +210,7 @@ __global__ void __launch_bounds__(256) kms_partial_kernel(const KmsArgs a) {
       for (int u = 0; u < 4; ++u)
         if (ok[u]) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e) s[e] += KmMfma<DT>::to_f32((unsigned short)v[u][e]);
+          for (int e = 0; e < 8; ++e) s[e] += bits_to_f32<DT>((uint16_t)v[u][e]);
         }
     }
     for (; j < rows; j += RL) {
@@ -235,7 +218,7 @@ __global__ void __launch_bounds__(256) kms_partial_kernel(const KmsArgs a) {
       if (rr >= 0 && rr < a.n) {
         const short8 v = *(const short8*)(xb + rr * rbytes);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) s[e] += KmMfma<DT>::to_f32((unsigned short)v[e]);
+        for (int e = 0; e < 8; ++e) s[e] += bits_to_f32<DT>((uint16_t)v[e]);
       }
     }
     float* dst = red + rl * E + cg * 8;

@@ -5,6 +5,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
+// Small functions that the kernels use and a plain C++17 compiler can also take (the sort keys of bitonic_device.h, the bf16
+// rounding of elem_device.h): inlined into host and device code under a HIP compiler, ordinary inline functions without one.
+#ifdef __HIPCC__
+#define MM_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define MM_HD inline
+#endif
+
 namespace mm {
 
 constexpr int kCUs = 256;  // MI355X

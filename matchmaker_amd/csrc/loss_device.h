@@ -3,7 +3,8 @@
 // with its two policies and kernels, the fixed-order float64 sums.  ONE copy of every loss formula.
 #pragma once
 #include "mm_internal.h"
-#include "ivf_device.h"
+#include "elem_device.h"
+#include "bitonic_device.h"
 
 namespace mm {
 
@@ -14,22 +15,11 @@ constexpr float kEps = 1e-6f;           // listnet.py:10, lambdarank.py:4
 constexpr float kInvLn2 = 1.44269504088896340736f;
 constexpr float kNegLog2Eps = 19.93156857296663f;        // -log2 of the fp32 value 1e-6f
 
-__device__ __forceinline__ float ld_score(const void* p, int dt, int64_t i) {
-  if (dt == MM_F32) return ((const float*)p)[i];
-  if (dt == MM_F16) return (float)((const _Float16*)p)[i];
-  return __uint_as_float((uint32_t)((const uint16_t*)p)[i] << 16);
-}
-
-// the fp32 value rounded once (to nearest even) to the scores' dtype
+// the fp32 value rounded once (to nearest even) to the scores' dtype; a NaN gradient stays a NaN in bf16 too
 __device__ __forceinline__ void st_grad(void* p, int dt, int64_t i, float v) {
-  if (dt == MM_F32) {
-    ((float*)p)[i] = v;
-  } else if (dt == MM_F16) {
-    ((_Float16*)p)[i] = (_Float16)v;
-  } else {
-    const uint32_t u = __float_as_uint(v);
-    ((uint16_t*)p)[i] = v != v ? (uint16_t)0x7fc0 : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  }
+  if (dt == MM_F32) store_elem<MM_F32>(p, i, v);
+  else if (dt == MM_F16) store_elem<MM_F16>(p, i, v);
+  else ((uint16_t*)p)[i] = (uint16_t)bf16_rne_bits_nan(v);
 }
 
 // p = sigmoid(x) and q = 1 - p = sigmoid(-x), each to fp32 accuracy at both ends, from one expf
@@ -237,9 +227,6 @@ __device__ __forceinline__ void list_softmax(const P& p, int L, const float (&v)
   }
 }
 
-// the order-preserving key of rank_metrics.hip: ascending key = descending score, -0 == +0, every NaN behind -inf
-__device__ __forceinline__ uint32_t loss_key(float s) { return s != s ? 0xffffffffu : ivf_dev::ivf_key(s); }
-
 template <class P, int KIND>
 __device__ __forceinline__ void list_body(P& p, const ListArgs& A, int list) {
   constexpr int N = P::NPT;
@@ -252,7 +239,7 @@ __device__ __forceinline__ void list_body(P& p, const ListArgs& A, int list) {
     in[k] = p.idx(k) < L;
     second[k] = p.idx(k) >= A.split;
     at[k] = second[k] ? (int64_t)list * (L - A.split) + (p.idx(k) - A.split) : (int64_t)list * A.split + p.idx(k);
-    s[k] = in[k] ? ld_score(second[k] ? A.scores2 : A.scores, A.dtype, at[k]) : 0.0f;
+    s[k] = in[k] ? load_elem(second[k] ? A.scores2 : A.scores, A.dtype, at[k]) : 0.0f;
     y[k] = in[k] ? (second[k] ? A.labels2 : A.labels)[at[k]] : 0.0f;
     g[k] = 0.0f;
   }
@@ -341,7 +328,7 @@ __device__ __forceinline__ void list_body(P& p, const ListArgs& A, int list) {
     uint32_t key[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
-      key[k] = loss_key(s[k]);
+      key[k] = desc_key_nan_last(s[k]);      // the key of rank_metrics.hip: descending score, -0 == +0, every NaN behind -inf
       p.share(SL_S, k, s[k]);
       p.share(SL_Y, k, y[k]);
       p.share(SL_K, k, __uint_as_float(key[k]));

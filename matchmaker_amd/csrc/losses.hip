@@ -41,7 +41,7 @@ __global__ void __launch_bounds__(256) pair_loss_kernel(const PairArgs A) {
   double acc = 0.0;
   const int64_t stride = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < A.n; i += stride) {
-    const double p = (double)ld_score(A.pos, A.dtype, i), g = (double)ld_score(A.neg, A.dtype, i);
+    const double p = (double)load_elem(A.pos, A.dtype, i), g = (double)load_elem(A.neg, A.dtype, i);
     const double a = (double)A.a[i], b = A.b ? (double)A.b[i] : 0.0;
     double term, gp, gn;
     pair_term(A.kind, p, g, a, b, &term, &gp, &gn);

@@ -508,49 +508,6 @@ __global__ void __launch_bounds__(256, 2) maxsim_allpairs_wg_kernel(const Maxsim
 // One wavefront per pair; query tiles of 32 tokens looped sequentially (deterministic sum order).
 // ---------------------------------------------------------------------------------------------
 template <int DT>
-__device__ __forceinline__ f32x16 dot_block(const char* drow, const char* qrow, int E) {
-  f32x16 acc = {0};
-  if constexpr (DT == MM_F32) {
-    // v_mfma_f32_32x32x2_f32: lane (r,h) supplies A[r][k=h].  K is walked in 16-B chunks: chunk
-    // pair (2c, 2c+1) -> h=0 takes chunk 2c, h=1 chunk 2c+1; the 4 floats of a chunk are 4 steps.
-    const int h = (threadIdx.x >> 5) & 1;      // lane half within the wavefront (workgroups may hold several)
-    const int nch = E >> 2;
-    for (int c = 0; c < nch; c += 2) {
-      const int cc = c + h;
-      f32x4 av = {0, 0, 0, 0}, bv = {0, 0, 0, 0};
-      if (cc < nch) {
-        av = *(const f32x4*)(drow + cc * 16);
-        bv = *(const f32x4*)(qrow + cc * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-    }
-  } else {
-    const int h = (threadIdx.x >> 5) & 1;      // lane half within the wavefront (workgroups may hold several)
-    const int nch = E >> 3;
-    // four K steps per trip: their eight 16-byte loads are issued before the first MFMA waits for any of them (the one
-    // load pair -> one MFMA form ran a row block as nch / 2 dependent memory round trips); same accumulation order
-    for (int c = 0; c < nch; c += 8) {
-      short8 av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int cc = c + 2 * u + h;
-        av[u] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        bv[u] = av[u];
-        if (cc < nch) {
-          av[u] = *(const short8*)(drow + cc * 16);
-          bv[u] = *(const short8*)(qrow + cc * 16);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c + 2 * u < nch) acc = Mfma32x16<DT == MM_F32 ? MM_BF16 : DT>::run(av[u], bv[u], acc);   // wave-uniform
-    }
-  }
-  return acc;
-}
-
-template <int DT>
 __global__ void __launch_bounds__(64) maxsim_generic_kernel(const MaxsimArgs a) {
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
@@ -599,7 +556,9 @@ __global__ void __launch_bounds__(64) maxsim_generic_kernel(const MaxsimArgs a) 
     for (int t = 0; t < nb; ++t) {
       const int drow = 32 * t + r;
       const int dr = drow < D ? drow : D - 1;
-      const f32x16 acc = dot_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E);
+      // (h & 1 == h: the masked form is what the tile derived for itself before it took h, and keeps this kernel's registers;
+      // plain h is as right, and may replace it once equality with the code before the shared tile no longer matters)
+      const f32x16 acc = dot_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E, h & 1);
       const int rem = len - 32 * t;
       const uint32_t ex = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
       const uint32_t va = (!rag && a.dm.bits) ? (a.dm.bits[mi * nblk_tot + t] & ex) : ex;
@@ -632,49 +591,6 @@ struct MaxsimBwdArgs {
   int Q, D, E;
   int row_masks;   // 1: LDS holds, per document row, the bit set of the query tokens whose first arg-max it is
 };
-
-// One 16-byte chunk of a token row as floats (4 for float32 rows, 8 for 16-bit rows), and the matching gradient store
-// (16 bytes for 16-bit gradients, 16 or 2 x 16 for float32 ones).
-template <int DT>
-__device__ __forceinline__ void load_chunk(const char* p, float* v) {
-  if constexpr (DT == MM_F32) {
-    const f32x4 x = *(const f32x4*)p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = x[k];
-  } else if constexpr (DT == MM_F16) {
-    typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-    const half8_t x = *(const half8_t*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (float)x[k];
-  } else {
-    const short8 x = *(const short8*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = __uint_as_float((uint32_t)(uint16_t)x[k] << 16);
-  }
-}
-
-template <int GT, int PER>
-__device__ __forceinline__ void store_chunk(char* base, int64_t elem, const float* v) {
-  if constexpr (GT == MM_F32) {
-    f32x4* o = (f32x4*)(base + elem * 4);
-#pragma unroll
-    for (int k = 0; k < PER / 4; ++k) o[k] = f32x4{v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
-  } else {
-    static_assert(PER == 8, "16-bit gradients come from 16-bit rows");
-    if constexpr (GT == MM_F16) {
-      typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
-      half8_t o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (_Float16)v[k];
-      *(half8_t*)(base + elem * 2) = o;
-    } else {
-      short8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (short)(uint16_t)(__float_as_uint(round_like<MM_BF16>(v[k])) >> 16);
-      *(short8*)(base + elem * 2) = o;
-    }
-  }
-}
 
 // GT: element type of the gradients — float32, or the token vectors' own 16-bit type (what autograd hands back to an
 // fp16 / bf16 encoder: written once, rounded once; rounds 1-3 wrote fp32 into a memset buffer and cast afterwards:
@@ -727,7 +643,7 @@ __global__ void __launch_bounds__(256) maxsim_bwd_kernel(const MaxsimBwdArgs a) 
     for (int t = wv; t < nb; t += 4) {
       const int drow = 32 * t + r;
       const int dr = drow < D ? drow : D - 1;
-      const f32x16 acc = dot_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E);
+      const f32x16 acc = dot_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E, h);
       const int rem = len - 32 * t;
       const uint32_t ex = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
       const uint32_t va = a.dm.bits ? (a.dm.bits[pair * nblk_tot + t] & ex) : ex;

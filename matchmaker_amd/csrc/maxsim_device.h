@@ -2,6 +2,7 @@
 // epilogue of kernel_pool128.hip.  gfx950 only.
 #pragma once
 #include "mm_internal.h"
+#include "elem_device.h"
 
 namespace mm {
 
@@ -33,21 +34,6 @@ struct MaxsimArgs {
 bool maxsim_pair_supported(int Q, int E, int dtype);
 bool maxsim_pair_i64_supported(int Q, int D, const void* qm, const void* dm);
 int maxsim_pair_launch(const MaxsimArgs& a, int dtype, bool i64, hipStream_t stream);
-
-template <int DT>
-struct Mfma32x16;
-template <>
-struct Mfma32x16<MM_BF16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  }
-};
-template <>
-struct Mfma32x16<MM_F16> {
-  static __device__ __forceinline__ f32x16 run(short8 a, short8 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-  }
-};
 
 // Running max of one 32-row document block into m[16].
 //   ex: bit r set <=> row r of the block is below the document's effective length
@@ -146,8 +132,7 @@ __device__ __forceinline__ float round_like(float x) {
   if constexpr (DT == MM_F16) {
     return (float)(_Float16)x;                                 // v_cvt_f16_f32: RNE, overflow -> inf as torch's cast
   } else if constexpr (DT == MM_BF16) {
-    const uint32_t u = __float_as_uint(x);
-    return __uint_as_float((u + 0x7fffu + ((u >> 16) & 1u)) & 0xffff0000u);   // RNE (no NaNs reach here)
+    return bits_to_f32<MM_BF16>((uint16_t)bf16_rne_bits(x));   // RNE (no NaNs reach here)
   } else {
     return x;
   }

@@ -23,7 +23,7 @@
 // A null grad_q or grad_d is a gradient the caller does not need (a frozen encoder): launch 2 or 3 is left out.
 // The result is a pure function of the inputs: two calls give the same bits.
 #include "mm_internal.h"
-#include "maxsim_device.h"
+#include "elem_device.h"
 
 namespace mm {
 namespace {
@@ -43,45 +43,6 @@ struct InbBwdArgs {
 };
 
 constexpr int kEnt = 1024;   // (query, token) entries staged per round of inb_gradd_kernel
-
-// <document rows 32t.., query rows 32n..> as one 32 x 32 MFMA tile: lane (r, h) supplies the K chunks of parity h of document row
-// r (A) and query row r (B); C: lane holds query column r, document rows rowof(i) + 4h.  K is walked in 16-byte chunks.
-template <int DT>
-__device__ __forceinline__ f32x16 sim_block(const char* drow, const char* qrow, int E, int h) {
-  f32x16 acc = {0};
-  if constexpr (DT == MM_F32) {
-    const int nch = E >> 2;
-    for (int c = 0; c < nch; c += 2) {
-      const int cc = c + h;
-      f32x4 av = {0, 0, 0, 0}, bv = {0, 0, 0, 0};
-      if (cc < nch) {
-        av = *(const f32x4*)(drow + cc * 16);
-        bv = *(const f32x4*)(qrow + cc * 16);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc, 0, 0, 0);
-    }
-  } else {
-    const int nch = E >> 3;
-    for (int c = 0; c < nch; c += 8) {          // four K steps per trip: eight loads in flight before the first MFMA
-      short8 av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int cc = c + 2 * u + h;
-        av[u] = short8{0, 0, 0, 0, 0, 0, 0, 0};
-        bv[u] = av[u];
-        if (cc < nch) {
-          av[u] = *(const short8*)(drow + cc * 16);
-          bv[u] = *(const short8*)(qrow + cc * 16);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (c + 2 * u < nch) acc = Mfma32x16<DT == MM_F32 ? MM_BF16 : DT>::run(av[u], bv[u], acc);   // wave-uniform
-    }
-  }
-  return acc;
-}
 
 template <int DT>
 __global__ void __launch_bounds__(256) inb_argmax_kernel(const InbBwdArgs a) {
@@ -115,7 +76,7 @@ __global__ void __launch_bounds__(256) inb_argmax_kernel(const InbBwdArgs a) {
     for (int t = 0; t < nb; ++t) {
       const int drow = 32 * t + r;
       const int dr = drow < D ? drow : D - 1;
-      const f32x16 acc = sim_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E, h);
+      const f32x16 acc = dot_block<DT>(dbase + dr * rowb, qbase + qr * rowb, E, h);
       const int rem = len - 32 * t, remd = D - 32 * t;
       const uint32_t ex = rem >= 32 ? 0xffffffffu : ((1u << rem) - 1u);
       const uint32_t ind = remd >= 32 ? 0xffffffffu : ((1u << remd) - 1u);    // rows that exist; the others take no part
@@ -139,60 +100,6 @@ __global__ void __launch_bounds__(256) inb_argmax_kernel(const InbBwdArgs a) {
     if (real && a.dm.bits) real = (a.dm.bits[mi * words + (bpos >> 5)] >> (bpos & 31)) & 1u;
     if (h == 0 && qtok < Q) trow[qtok] = (int16_t)((qvalid && real) ? bpos : -1);
   }
-}
-
-// One 16-byte chunk of a token row as floats (4 for float32 rows, 8 for 16-bit rows) and the matching gradient store.
-template <int DT>
-__device__ __forceinline__ void ld16(const char* p, float* v) {
-  if constexpr (DT == MM_F32) {
-    const f32x4 x = *(const f32x4*)p;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) v[k] = x[k];
-  } else if constexpr (DT == MM_F16) {
-    const f16x8 x = *(const f16x8*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = (float)x[k];
-  } else {
-    const short8 x = *(const short8*)p;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) v[k] = __uint_as_float((uint32_t)(uint16_t)x[k] << 16);
-  }
-}
-
-template <int GT, int PER>
-__device__ __forceinline__ void st16(char* base, int64_t elem, const float* v) {
-  if constexpr (GT == MM_F32) {
-    f32x4* o = (f32x4*)(base + elem * 4);
-#pragma unroll
-    for (int k = 0; k < PER / 4; ++k) o[k] = f32x4{v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]};
-  } else {
-    static_assert(PER == 8, "16-bit gradients come from 16-bit rows");
-    if constexpr (GT == MM_F16) {
-      f16x8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (_Float16)v[k];
-      *(f16x8*)(base + elem * 2) = o;
-    } else {
-      short8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (short)(uint16_t)(__float_as_uint(round_like<MM_BF16>(v[k])) >> 16);
-      *(short8*)(base + elem * 2) = o;
-    }
-  }
-}
-
-template <int DT>
-__device__ __forceinline__ float ld1(const void* base, int64_t elem) {
-  if constexpr (DT == MM_F32) return ((const float*)base)[elem];
-  else if constexpr (DT == MM_F16) return (float)((const _Float16*)base)[elem];
-  else return __uint_as_float((uint32_t)((const uint16_t*)base)[elem] << 16);
-}
-
-template <int GT>
-__device__ __forceinline__ void st1(void* base, int64_t elem, float v) {
-  if constexpr (GT == MM_F32) ((float*)base)[elem] = v;
-  else if constexpr (GT == MM_F16) ((_Float16*)base)[elem] = (_Float16)v;
-  else ((uint16_t*)base)[elem] = (uint16_t)(__float_as_uint(round_like<MM_BF16>(v)) >> 16);
 }
 
 // grad_q[i, t, chunk] = sum_j grad_out[i, j] d[j, j*(i, j, t), chunk]: ascending j, fp32, stored once (zeros without a gradient)
@@ -220,12 +127,12 @@ __global__ void __launch_bounds__(256) inb_gradq_kernel(const InbBwdArgs a) {
     const int p = tp[j * Q];
     if (p >= 0) {
       const float g = gp[j];
-      ld16<DT>(dc + (j * D + p) * rowb, x);
+      load_chunk<DT>(dc + (j * D + p) * rowb, x);
 #pragma unroll
       for (int k = 0; k < PER; ++k) v[k] += g * x[k];
     }
   }
-  st16<GT, PER>((char*)a.gq, row * E + (int64_t)c * PER, v);
+  store_chunk<GT, PER>((char*)a.gq, row * E + (int64_t)c * PER, v);
 }
 
 // grad_d[j, p, e0 + col] = sum over (i, t) ascending with j*(i, j, t) = p of grad_out[i, j] q[i, t, e0 + col]
@@ -272,7 +179,7 @@ __global__ void __launch_bounds__(256) inb_gradd_kernel(const InbBwdArgs a) {
         for (int u = 0; u < 8; ++u) {
           const int p = pp[u];
           if (p >= 0 && (p & 3) == s) {        // wave-uniform: cell (p, col) is this thread's alone
-            const float x = ld1<DT>(a.q, (base + k0 + u) * E + e0 + col);
+            const float x = load_elem<DT>(a.q, (base + k0 + u) * E + e0 + col);
             acc[p * et + col] += ent_g[k0 + u] * x;
           }
         }
@@ -282,7 +189,7 @@ __global__ void __launch_bounds__(256) inb_gradd_kernel(const InbBwdArgs a) {
   __syncthreads();
   for (int k = tid; k < D * w; k += 256) {
     const int p = k / w, c = k - p * w;
-    st1<GT>(a.gd, (dj * D + p) * (int64_t)E + e0 + c, acc[p * et + c]);
+    store_elem<GT>(a.gd, (dj * D + p) * (int64_t)E + e0 + c, acc[p * et + c]);
   }
 }
 

@@ -17,8 +17,8 @@
 //                              [hi, hi] exists (core_metrics.py:40, 88-92 builds it).
 // No atomics, no workspace, no read-back, vector stores only: graph-capturable, and two calls give the same bits.
 #include "mm_internal.h"
+#include "elem_device.h"
 #include "bitonic_device.h"
-#include "ivf_device.h"
 
 namespace mm {
 
@@ -27,18 +27,8 @@ constexpr int kRankMaxCut = MM_RANK_MAX_CUTOFFS;
 constexpr int32_t kNoGrade = INT32_MIN;           // MM_RANK_NOT_JUDGED
 constexpr uint64_t kPadKey = ~0ull;               // sorts behind every row (a row's low word is < kRankMaxLen)
 
-template <int DT>
-__device__ __forceinline__ float score_at(const void* p, int64_t i) {
-  if constexpr (DT == MM_F32) return ((const float*)p)[i];
-  else if constexpr (DT == MM_F16) return (float)((const _Float16*)p)[i];
-  else return __uint_as_float((uint32_t)((const uint16_t*)p)[i] << 16);
-}
-
-// ascending key = descending score, -0 == +0 (ivf_key); every NaN gets the one key behind -inf's
-__device__ __forceinline__ uint64_t rank_key(float s, int i) {
-  const uint32_t k = s != s ? 0xffffffffu : ivf_dev::ivf_key(s);
-  return ((uint64_t)k << 32) | (uint32_t)i;
-}
+// ascending key = descending score, -0 == +0, every NaN on the one key behind -inf's; equal scores in arrival order
+__device__ __forceinline__ uint64_t rank_key(float s, int i) { return ((uint64_t)desc_key_nan_last(s) << 32) | (uint32_t)i; }
 
 // rows [beg, beg + len) of segment s, clamped into [0, n) whatever seg_begin holds
 __device__ __forceinline__ void seg_range(const int64_t* sb, int s, int64_t n, int64_t* beg, int64_t* len) {
@@ -63,7 +53,7 @@ __global__ void __launch_bounds__(256) seg_rank_wave_kernel(const void* scores, 
     return;
   }
   const bool in = lane < len;
-  const uint64_t mine = in ? rank_key(score_at<DT>(scores, beg + (in ? lane : 0)), lane) : kPadKey;
+  const uint64_t mine = in ? rank_key(load_elem<DT>(scores, beg + (in ? lane : 0)), lane) : kPadKey;
   int rank = 0;
   for (int j = 0; j < (int)len; ++j) {
     const uint32_t hi = __shfl((int)(mine >> 32), j, 64), lo = __shfl((int)(uint32_t)mine, j, 64);
@@ -82,7 +72,7 @@ __global__ void seg_rank_block_kernel(const void* scores, const int64_t* sb, int
   const int len = (int)len64;
   int n2 = 128;
   while (n2 < len) n2 <<= 1;                    // <= the LDS of the launch: len <= cap <= its power of two
-  for (int i = tid; i < n2; i += nt) rank_keys[i] = i < len ? rank_key(score_at<DT>(scores, beg + i), i) : kPadKey;
+  for (int i = tid; i < n2; i += nt) rank_keys[i] = i < len ? rank_key(load_elem<DT>(scores, beg + i), i) : kPadKey;
   bitonic_asc(rank_keys, n2, tid, nt);
   for (int i = tid; i < len; i += nt) order[beg + i] = (int32_t)(beg + (int64_t)(uint32_t)rank_keys[i]);
 }

@@ -16,6 +16,7 @@
 // Positions come from the scan, never from an atomic: the row order is fixed and two runs give the same bits.  No
 // workgroup waits on another inside a launch; the launches are the only synchronisation.
 #include "mm_internal.h"
+#include "elem_device.h"
 #include "fp8_device.h"
 
 namespace mm {
@@ -135,11 +136,6 @@ __device__ __forceinline__ int64_t kept_before(const StoreArgs& a, int64_t r) {
   return n;
 }
 
-__device__ __forceinline__ uint32_t bf16_rne(float f) {      // finite input: round to nearest even, overflow to inf
-  const uint32_t u = __float_as_uint(f);
-  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-}
-
 template <int ODT>
 __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
   if constexpr (ODT == MM_F16) {
@@ -148,7 +144,7 @@ __device__ __forceinline__ uint32_t pack2(float lo, float hi) {
     h[1] = (_Float16)hi;
     return __builtin_bit_cast(uint32_t, h);
   } else {
-    return bf16_rne(lo) | (bf16_rne(hi) << 16);
+    return bf16_rne_bits(lo) | (bf16_rne_bits(hi) << 16);      // finite input (elem_device.h)
   }
 }
 

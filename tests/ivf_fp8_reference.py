@@ -58,7 +58,8 @@ def exact_problem(E, nq, nprobe, seed):
 
 # the exact cases of the GPU suite: (E, nq, k), nprobe 6, both query dtypes
 EXACT = [(128, 1, 1), (128, 37, 10), (128, 700, 1000), (256, 37, 10), (384, 1, 1000), (384, 700, 10), (512, 37, 1),
-         (768, 1, 10), (768, 37, 1000), (768, 700, 1)]
+         (768, 1, 10), (768, 37, 1000), (768, 700, 1),
+         (128, 3, 16), (128, 3, 4096)]         # k equal to its padded power of two; the operator's limit
 EXACT_NPROBE = 6
 
 

@@ -73,7 +73,8 @@ def _problem(dtype, E, nq, nprobe, seed):
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("E,nq,k", [(128, 1, 1), (128, 37, 10), (128, 700, 1000), (384, 1, 1000), (384, 37, 1),
-                                    (384, 700, 10), (768, 1, 10), (768, 37, 1000), (768, 700, 1)])
+                                    (384, 700, 10), (768, 1, 10), (768, 37, 1000), (768, 700, 1),
+                                    (128, 3, 16), (128, 3, 4096)])      # k equal to its padded power of two; the operator's limit
 def test_ah_scan_is_the_exact_topk_of_the_probed_union(dtype, E, nq, k):
     from matchmaker_amd import ops
     dev = util.require_gpu()
