@@ -1237,6 +1237,36 @@ int mm_inbatch_dot_loss_fwd(const void* Q, const void* Dp, const void* Dn, int d
                             void* grad_Q, void* grad_Dp, void* grad_Dn, void* grad_sp, void* workspace,
                             size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * mm_self_attention_fwd, mm_self_attention_supported (additive: MM_ABI_VERSION unchanged)
+ * Replaces: the attention core of the contextualiser's encoder layers, matchmaker/models/published/ecai20_tk.py:138,
+ *           sigir20_tkl.py:296-308 and sigir21_idcm.py:174-175 (nn.TransformerEncoder, batch_first=False, with
+ *           src_key_padding_mask: per layer F.multi_head_attention_forward -> scaled_dot_product_attention with a float mask).
+ *           The projections, LayerNorm and the feed-forward block stay torch's; there is no backward.
+ *   out[b, i, h dh + d] = sum_j softmax_j(q[b,i,h] . k[b,j,h] / sqrt(dh) + (mask[b,j] ? 0 : -inf)) v[b,j,h,d]
+ *   qkv [B, L, 3 E] of `dtype` (MM_F32 / MM_F16 / MM_BF16), contiguous, E = H dh: what F.linear(x, in_proj_weight, in_proj_bias)
+ *   returns.  Q in columns [0, E), K in [E, 2E), V in [2E, 3E); head h at column offset h dh.  qkv and out aligned to their
+ *   element type, nothing more: every global access is made in chunks of the largest of 16 / 8 / 4 / 2 bytes that divides both
+ *   addresses, E and dh in bytes, and the result does not depend on it.
+ *   mask [B, L] (or [B] lengths) of mask_kind MM_MASK_*: nonzero = token.  An arbitrary pattern, not a length.  Only KEYS are
+ *   masked: all L query rows are computed and written.  A sequence with no unmasked key gets +0 in every row (torch 2.10's
+ *   safe softmax gives the same).
+ *   out [B, L, E] of `dtype`: heads concatenated, ready for out_proj.
+ *   Arithmetic: q k^T by v_mfma_f32_32x32x2_f32 for fp32 inputs and by v_mfma_f32_32x32x16_{f16,bf16} for 16-bit ones (every
+ *   product exact in fp32), the weighted sum of v by v_mfma_f32_32x32x2_f32 on the exactly widened v for every type (no rounding
+ *   of an operand or of a weight, fp32 accumulation in a fixed order), scores scaled by log2(e) / sqrt(dh) with the mask added in one fma, softmax on v_exp_f32 in
+ *   fp32, the weighted sum divided by the weights' sum, one rounding to `dtype` at the store.
+ *   mm_self_attention_supported(dtype, L, H, dh) -> 1 / 0, a pure host function: 1 <= L <= 256, 1 <= dh <= 64, dh even for
+ *   the 16-bit types, H >= 1.  Anything else: MM_EUNSUPPORTED from mm_self_attention_fwd before any launch.
+ *   One workgroup per (sequence, head) in grid.x (B H < 2^31), K and V of the head in LDS (at most 76 KiB for dh <= 32, 138 KiB beyond).  One launch, no
+ *   workspace, no atomics, no read-back, vector stores only, every element of out stored exactly once: graph-capturable, two
+ *   calls give the same bits.  B = 0 succeeds without a launch.
+ *   MM_EINVAL: NULL where required, B < 0, unknown dtype or mask kind, misaligned qkv / out.
+ */
+int mm_self_attention_supported(int dtype, int L, int H, int dh);
+int mm_self_attention_fwd(const void* qkv, int dtype, const void* mask, int mask_kind, int B, int L, int H, int dh, void* out,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

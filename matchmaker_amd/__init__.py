@@ -6,7 +6,7 @@ from . import ops  # noqa: F401
 
 __all__ = ["ops", "NativeError", "LIB_PATH", "FlatIPIndexer", "IVFFlatIPIndexer", "DynamicIVFIndexer", "GraphIPIndexer", "ScannIPIndexer",
            "MaxPIndexer", "TokenStore", "TokenStoreWriter", "encode_collection", "fp8_quantize_rows", "fp8_dequantize_rows", "maxsim_ragged_fp8",
-           "losses", "get_loss", "patch_losses", "inbatch", "InBatchNegatives"]
+           "losses", "get_loss", "patch_losses", "inbatch", "InBatchNegatives", "contextualize"]
 
 
 def __getattr__(name):          # the indexers, imported on first use (retrieval pulls in torch.distributed)
@@ -30,6 +30,9 @@ def __getattr__(name):          # the indexers, imported on first use (retrieval
     if name == "inbatch":       # the native in-batch negatives of dense-retriever training (train.py:434-472)
         import importlib
         return importlib.import_module(".inbatch", __name__)
+    if name == "contextualize":  # the TK-family contextualiser with its attention core on csrc/self_attention.hip
+        import importlib
+        return importlib.import_module(".contextualize", __name__)
     if name == "InBatchNegatives":
         from .inbatch import InBatchNegatives
         return InBatchNegatives

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(CSRC, "libmm_native.so")
-SOURCES = ["common.hip", "maxsim.hip", "maxsim_pair.hip", "maxsim_inbatch_bwd.hip", "maxsim_fp8.hip", "kernel_pool.hip", "kernel_pool128.hip", "kernel_pool_bwd.hip", "kernel_pool_bwd_split.hip", "tkl.hip", "tkl_stage1_rows.hip", "tkl_bwd.hip", "dot_topk.hip", "dot_topk_fp8.hip", "ivf_scan.hip", "ivf_scan_fp8.hip", "ah_scan.hip", "ah_encode.hip", "graph_search.hip", "kmeans.hip", "pacrr.hip", "co_pacrr.hip", "drmm.hip", "matchpyramid.hip", "colbert_candidates.hip", "store_writer.hip", "rank_metrics.hip", "losses.hip", "inbatch_loss.hip", "distinct_hits.hip"]
+SOURCES = ["common.hip", "maxsim.hip", "maxsim_pair.hip", "maxsim_inbatch_bwd.hip", "maxsim_fp8.hip", "kernel_pool.hip", "kernel_pool128.hip", "kernel_pool_bwd.hip", "kernel_pool_bwd_split.hip", "tkl.hip", "tkl_stage1_rows.hip", "tkl_bwd.hip", "dot_topk.hip", "dot_topk_fp8.hip", "ivf_scan.hip", "ivf_scan_fp8.hip", "ah_scan.hip", "ah_encode.hip", "graph_search.hip", "kmeans.hip", "pacrr.hip", "co_pacrr.hip", "drmm.hip", "matchpyramid.hip", "colbert_candidates.hip", "store_writer.hip", "rank_metrics.hip", "losses.hip", "inbatch_loss.hip", "distinct_hits.hip", "self_attention.hip"]
 # every header of csrc/ (a new one cannot be forgotten) and the C ABI: any of them newer than an object rebuilds it
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")) + [os.path.join(HERE, "..", "include", "mm_native.h")]
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-comment"]

@@ -19,7 +19,7 @@ from typing import Optional
 import torch
 from torch import nn
 
-from . import ops
+from . import contextualize, ops
 from .tk import kernel_pool_train
 
 MU = [1.0, 0.9, 0.7, 0.5, 0.3, 0.1, -0.1, -0.3, -0.5, -0.7, -0.9]     # sigir21_idcm.py:106
@@ -48,12 +48,13 @@ def sampler_scores(query_ctx: torch.Tensor, document_ctx: torch.Tensor, query_ma
 
 
 # ---- the sampler's token vectors (sigir21_idcm.py:167-180, without the normalize) -----------------------
-def sampler_vectors(self, ids: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
-    """`self`: an IDCM module (the reference's class or any module with its attributes)."""
+def sampler_vectors(self, ids: torch.Tensor, mask: torch.Tensor, native_attention: bool = False) -> torch.Tensor:
+    """`self`: an IDCM module (the reference's class or any module with its attributes).  native_attention: the `tk`
+    contextualiser's attention core on csrc/self_attention.hip where no gradient is needed (contextualize.encode)."""
     emb = self.bert_model.embeddings(ids).detach()
     if self.sample_context == "ck-small":
         return self.sample_cnn3(self.sample_projector(emb).transpose(1, 2)).transpose(1, 2)
     if self.sample_context == "ck":
         return self.sample_cnn3(emb.transpose(1, 2)).transpose(1, 2)
     proj = self.tk_projector(emb)
-    return self.tk_contextualizer(proj.transpose(1, 0), src_key_padding_mask=~mask.bool()).transpose(1, 0)
+    return contextualize.encode(self.tk_contextualizer, proj, mask, native=native_attention)

@@ -1265,6 +1265,14 @@ def inbatch_dot_loss(Q, Dp, Dn, sp, Tp, Tn, family, kind, need_grad=True, return
     return inbatch.inbatch_dot_loss(Q, Dp, Dn, sp, Tp, Tn, family, kind, need_grad=need_grad, return_scores=return_scores)
 
 
+def self_attention(qkv: torch.Tensor, mask: Optional[torch.Tensor], num_heads: int) -> torch.Tensor:
+    """The attention core of the TK-family contextualiser on the in-projection as it lies in memory (ecai20_tk.py:138,
+    sigir20_tkl.py:296-308, sigir21_idcm.py:174-175; native mm_self_attention_fwd): see matchmaker_amd/contextualize.py, where the
+    torch <-> ABI wrapper lives (the poisoned-memory case of this operator is in tests/test_contextualize_gpu.py)."""
+    from . import contextualize
+    return contextualize.self_attention(qkv, mask, num_heads)
+
+
 def store_append(x: torch.Tensor, rows_out: Optional[torch.Tensor], codes_out: Optional[torch.Tensor],
                  scales_out: Optional[torch.Tensor], capacity: int, fill: torch.Tensor, doc_begin: torch.Tensor,
                  doc_end: torch.Tensor, status: torch.Tensor, keep_zero_rows: bool = False) -> None:

@@ -12,7 +12,7 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from . import _fast, ops
+from . import _fast, contextualize, ops
 
 
 def sinusoid_positions(dim: int, length: int, min_timescale: float = 1.0, max_timescale: float = 1.0e4) -> torch.Tensor:
@@ -70,6 +70,8 @@ def kernel_pool_train(q, d, q_mask, d_mask, mu, sigma, alpha, w, gate=None, clam
 
 class ECAI20_TK(nn.Module):
     """TK: Transformer contextualisation + kernel pooling (https://arxiv.org/abs/2002.01854)."""
+
+    native_attention = False      # True: the contextualiser's attention core on csrc/self_attention.hip where no gradient is needed (contextualize.encode)
 
     @staticmethod
     def from_config(config, word_embeddings_out_dim):      # ecai20_tk.py:22-32
@@ -143,8 +145,8 @@ class ECAI20_TK(nn.Module):
         """ecai20_tk.py:133-143."""
         if positional_features is None:
             positional_features = self.positional_features_d[:, :sequence_embeddings.shape[1], :]
-        ctx = self.contextualizer((sequence_embeddings + positional_features).transpose(1, 0),
-                                  src_key_padding_mask=~sequence_mask.bool()).transpose(1, 0)
+        ctx = contextualize.encode(self.contextualizer, sequence_embeddings + positional_features, sequence_mask,
+                                   native=self.native_attention)
         if self.mix_hybrid_context:
             return self.mixer * sequence_embeddings + (1 - self.mixer) * ctx
         return ctx

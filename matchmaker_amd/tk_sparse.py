@@ -13,12 +13,14 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import contextualize, ops
 from .tk import kernel_pool_train, sinusoid_positions
 
 
 class CIKM20_TK_Sparse(nn.Module):
     """TK with a learned per-document-token gate that removes stop words from the score."""
+
+    native_attention = False      # True: the contextualiser's attention core on csrc/self_attention.hip where no gradient is needed (contextualize.encode)
 
     @staticmethod
     def from_config(config, word_embeddings_out_dim):      # cikm20_tk_sparse.py:18-28
@@ -108,8 +110,8 @@ class CIKM20_TK_Sparse(nn.Module):
         if positional_features is None:
             positional_features = self.positional_features_d[:, :sequence_embeddings.shape[1], :]
         sequence_embeddings = sequence_embeddings * sequence_mask.unsqueeze(-1)
-        ctx = self.contextualizer((sequence_embeddings + positional_features).transpose(1, 0),
-                                  src_key_padding_mask=~sequence_mask.bool()).transpose(1, 0)
+        ctx = contextualize.encode(self.contextualizer, sequence_embeddings + positional_features, sequence_mask,
+                                   native=self.native_attention)
         mixed = (self.mixer * sequence_embeddings + (1 - self.mixer) * ctx) * sequence_mask.unsqueeze(-1)
         return mixed, ctx
 

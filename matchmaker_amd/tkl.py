@@ -20,7 +20,7 @@ from typing import List
 import torch
 import torch.nn as nn
 
-from . import _fast, ops
+from . import _fast, contextualize, ops
 from ._lib import NativeError
 from .tk import sinusoid_positions
 
@@ -133,6 +133,8 @@ def _layout_tensor(sizes):
 
 class TKL_sigir20(nn.Module):
     """TKL: TK for long documents (https://arxiv.org/abs/2005.04908)."""
+
+    native_attention = False      # True: the contextualiser's attention core on csrc/self_attention.hip where no gradient is needed (contextualize.encode)
 
     @staticmethod
     def from_config(config, word_embeddings_out_dim):      # sigir20_tkl.py:17-29
@@ -329,8 +331,7 @@ class TKL_sigir20(nn.Module):
             if positional_features is None:
                 positional_features = self.positional_features_d[:, :sequence_embeddings.shape[1], :]
             pos_sequence = sequence_embeddings + positional_features
-        ctx = self.contextualizer(pos_sequence.transpose(1, 0),
-                                  src_key_padding_mask=~sequence_mask.bool()).transpose(1, 0)
+        ctx = contextualize.encode(self.contextualizer, pos_sequence, sequence_mask, native=self.native_attention)
         mixed = (self.mixer * sequence_embeddings + (1 - self.mixer) * ctx) * sequence_mask.unsqueeze(-1)
         return mixed, ctx
 

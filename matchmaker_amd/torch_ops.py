@@ -21,6 +21,7 @@ Importing this module defines
     torch.ops.mm_native.list_loss(scores, labels, kind)                             -> (loss [], per_list [B], grad [B, L])
     torch.ops.mm_native.inbatch_dot_loss(q, dp, dn, sp, tp, tn, family, kind)       -> (loss [], stats [3], grad_q, grad_dp, grad_dn, grad_sp)
     torch.ops.mm_native.inbatch_select_loss(sp, s_pos, s_neg, tp, tn, family, kind) -> (loss [], stats [3], grad_sp, grad_s_pos, grad_s_neg)
+    torch.ops.mm_native.self_attention(qkv, mask, num_heads)                        -> out [B, L, E] (no autograd formula)
 
 for HIP tensors only (dispatch key CUDA; a CPU tensor raises NotImplementedError: there is no CPU kernel), each
 with a fake (meta) implementation for tracing, an autograd formula backed by the native backward kernels
@@ -659,3 +660,19 @@ def _inbatch_select_backward(ctx, g, *_unused):
 
 
 inbatch_select_loss.register_autograd(_inbatch_select_backward, setup_context=_inbatch_select_setup)
+
+
+# ---------------------------------------------------------------------------------------------- contextualiser attention
+from . import contextualize as _contextualize  # noqa: E402
+
+
+@torch.library.custom_op(_NS + "::self_attention", mutates_args=(), device_types="cuda")
+def self_attention(qkv: Tensor, mask: Optional[Tensor], num_heads: int) -> Tensor:
+    """out [B, L, E] of qkv's dtype: the attention core of the TK-family contextualiser on the in-projection qkv [B, L, 3E]
+    with a key mask (contextualize.self_attention).  No autograd formula: the operator serves inference."""
+    return _contextualize.self_attention(qkv, mask, num_heads)
+
+
+@self_attention.register_fake
+def _(qkv, mask, num_heads):
+    return qkv.new_empty((qkv.shape[0], qkv.shape[1], qkv.shape[2] // 3))
