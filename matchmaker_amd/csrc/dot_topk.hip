@@ -36,6 +36,7 @@
 #include "mm_internal.h"
 #include "elem_device.h"
 #include "bitonic_device.h"
+#include "lds_dma_device.h"
 #include <type_traits>
 
 namespace mm {
@@ -122,27 +123,14 @@ __device__ __forceinline__ void dot_q_landed(short8 (&qf)[8]) {
 // NSL LDS-DMA instructions: 4 document rows x 256 B of every 128-dim slice -> 1 KiB of LDS each, the
 // slices 8 KiB apart (m0 walks).  The per-slice source offsets come in VGPRs: an instruction offset
 // would also be added to the LDS address (LDS_addr = M0 + inst_offset + lane * 16).
-#define MM_DOT_LD(N) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #N ", %7\n\ts_add_u32 m0, m0, 0x2000\n\t"
-#define MM_DOT_ISSUE(BODY)                                                                              \
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %8\n\t" BODY "s_mov_b32 m0, %0" \
-               : "=&s"(keep)                                                                            \
-               : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "s"(gbase), "s"(lds_dst) \
-               : "memory", "scc")
 template <int NSL>
 __device__ __forceinline__ void dot_issue(const char* gbase, uint32_t voff, uint32_t lds_dst) {
   static_assert(NSL == 1 || NSL == 2 || NSL == 3 || NSL == 4 || NSL == 6, "E = 128 * NSL");
-  uint32_t keep;
-  uint32_t v[6];
+  uint32_t v[NSL];
 #pragma unroll
-  for (int sl = 0; sl < 6; ++sl) v[sl] = voff + (sl < NSL ? sl : 0) * 256;
-  if constexpr (NSL == 1) MM_DOT_ISSUE(MM_DOT_LD(1));
-  else if constexpr (NSL == 2) MM_DOT_ISSUE(MM_DOT_LD(1) MM_DOT_LD(2));
-  else if constexpr (NSL == 3) MM_DOT_ISSUE(MM_DOT_LD(1) MM_DOT_LD(2) MM_DOT_LD(3));
-  else if constexpr (NSL == 4) MM_DOT_ISSUE(MM_DOT_LD(1) MM_DOT_LD(2) MM_DOT_LD(3) MM_DOT_LD(4));
-  else MM_DOT_ISSUE(MM_DOT_LD(1) MM_DOT_LD(2) MM_DOT_LD(3) MM_DOT_LD(4) MM_DOT_LD(5) MM_DOT_LD(6));
+  for (int sl = 0; sl < NSL; ++sl) v[sl] = voff + sl * 256;
+  lds_dma<0x2000, false, true>(gbase, v, lds_dst);
 }
-#undef MM_DOT_ISSUE
-#undef MM_DOT_LD
 
 // ONE LDS-DMA instruction (4 rows x 256 B of one slice), for the K loop: issued right after the block barrier the 2 NSL
 // instructions of a wavefront queue behind those of the three other wavefronts at the CU's one address unit (48 KiB per
@@ -158,18 +146,8 @@ __device__ __forceinline__ void dot_issue_one(const char* gbase, uint32_t voff, 
                : "v"(voff), "s"(gbase), "s"(lds_dst)
                : "memory", "m0");
 #else
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_dst)
-               : "memory");
+  lds_dma_one(gbase, voff, lds_dst);
 #endif
-}
-
-template <int N>
-__device__ __forceinline__ void dot_wait() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 #ifndef MM_DOT_AHEAD
@@ -245,7 +223,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
       else dot_load_q<false>(qrow + sl * 256, qf[n][sl]);
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every fragment of the query tiles
+  wait_vm(0);   // every fragment of the query tiles
 #pragma unroll
   for (int n = 0; n < NQT; ++n)
 #pragma unroll
@@ -392,7 +370,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
     if (PROF) t0 = now();
     // This wavefront's part of block b has landed: FILTER waited for it behind the previous K loop, in front of the flush — a
     // wait here would also wait for that flush's stores to be acknowledged (~1 k cycles in every flush block).
-    if (MODE != DOT_FILTER || b == b_lo) dot_wait<0>();
+    if (MODE != DOT_FILTER || b == b_lo) wait_vm(0);
     if (PROF) t1 = now();
     __syncthreads();  // every part of block b landed; every wavefront is done with block b - 1
     if (PROF) t2 = now();
@@ -544,7 +522,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
       // Threshold test without a scalar branch per element: every lane collects the elements that pass in a bit mask
       // (bit e = 16 n + i), the accumulators are parked in LDS ([e][lane]), and the survivors (~5 per wavefront-block at
       // the working threshold) are filed from there: every lane takes its lowest pending element per round.
-      dot_wait<0>();   // block b + 1's rows (requested in the first half of the K loop) — and nothing else is in flight here
+      wait_vm(0);   // block b + 1's rows (requested in the first half of the K loop) — and nothing else is in flight here
       // What the in-loop rounds left of block b - 1 (a lane with three survivors):
 #if !defined(MM_DOT_CUT) || MM_DOT_CUT != 4
       file_rounds(pmask_prev, code_prev);
@@ -563,7 +541,7 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
         flush_wave();
         b_base = b;
         if (PROF) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          wait_vm(0);
           tp[6] += now() - tf;
         }
       }
@@ -590,14 +568,14 @@ __global__ void __launch_bounds__(256) dot_stream_kernel(const DotArgs a) {
       run_block(b, accB, accA);
       if (++b == b_hi) { last_in_a = false; break; }
     }
-    dot_wait<0>();   // the last block's redundant request has landed before the workgroup's LDS can go to another one
+    wait_vm(0);   // the last block's redundant request has landed before the workgroup's LDS can go to another one
     // tail: the last block of the range has no K loop behind it
     uint32_t pm = last_in_a ? test_park(accA, b_hi - 1) : test_park(accB, b_hi - 1);
     file_rounds(pm, ((uint32_t)(b_hi - 1 - b_base) << 11) | (uint32_t)lane);
     flush_wave();
   } else {
     for (int64_t b = b_lo; b < b_hi; ++b) run_block(b, accA, accA);
-    dot_wait<0>();   // the last block's redundant request has landed before the workgroup's LDS can go to another one
+    wait_vm(0);   // the last block's redundant request has landed before the workgroup's LDS can go to another one
     if (MODE == DOT_FILTER) {   // the last block has no K loop behind it
       file_rounds(pmask_prev, ((uint32_t)(b_hi - 1 - b_base) << 11) | (uint32_t)lane);
       flush_wave();

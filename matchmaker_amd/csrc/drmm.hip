@@ -156,36 +156,7 @@ __device__ __forceinline__ void load_rdr(const float* rdbuf, int h, float (&rdr)
 }
 
 // ---- the LDS-DMA document stream (the slice geometry of kernel_pool.hip's streaming kernels) -----------------------------
-constexpr int kSC = 25;                       // 16-B chunks per row per slice (odd: conflict-free)
-constexpr int kSliceInstr = 13;               // ceil(32*25 / 64) LDS-DMA instructions per slice
-constexpr int kSliceBytes = kSliceInstr * 1024;
-constexpr int kPairSteps = 13;                // chunk pairs per slice (last one half empty)
 constexpr int kNbuf = 3;
-
-__device__ __forceinline__ void issue_slice(const char* gbase, const uint32_t (&voff)[kSliceInstr], uint32_t vmax, bool clamp,
-                                            uint32_t lds_dst) {
-  uint32_t v[kSliceInstr];
-#pragma unroll
-  for (int n = 0; n < kSliceInstr; ++n) v[n] = clamp ? (voff[n] < vmax ? voff[n] : vmax) : voff[n];
-  uint32_t keep;
-#define MM_GLDS(N) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #N ", %14 nt\n\ts_add_u32 m0, m0, 0x400\n\t"
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %15\n\t" MM_GLDS(1) MM_GLDS(2) MM_GLDS(3) MM_GLDS(4)
-                   MM_GLDS(5) MM_GLDS(6) MM_GLDS(7) MM_GLDS(8) MM_GLDS(9) MM_GLDS(10) MM_GLDS(11) MM_GLDS(12)
-                       MM_GLDS(13) "s_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "v"(v[8]), "v"(v[9]),
-                 "v"(v[10]), "v"(v[11]), "v"(v[12]), "s"(gbase), "s"(lds_dst)
-               : "memory", "scc");
-#undef MM_GLDS
-}
-
-__device__ __forceinline__ void wait_slices(int younger) {
-  switch (younger) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(13)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); break;
-  }
-}
 
 template <int NS>
 __global__ void __launch_bounds__(64) drmm_stream_kernel(const DrmmArgs a) {
@@ -226,7 +197,7 @@ __global__ void __launch_bounds__(64) drmm_stream_kernel(const DrmmArgs a) {
   auto top_up = [&]() {
     while (pp < p1 && inflight < kNbuf) {
       const char* g = dbase + (pp * D + (int64_t)pt * 32) * RB + ps * (kSC * 16);
-      issue_slice(g, voff, vmax_tail, pt == nblk_tot - 1 && rows_last != 32, lds0 + (uint32_t)pbuf * kSliceBytes);
+      issue_slice<true>(g, voff, vmax_tail, pt == nblk_tot - 1 && rows_last != 32, lds0 + (uint32_t)pbuf * kSliceBytes);
       pbuf = (pbuf + 1 == kNbuf) ? 0 : pbuf + 1;
       ++inflight;
       if (++ps == NS) {
@@ -281,7 +252,7 @@ __global__ void __launch_bounds__(64) drmm_stream_kernel(const DrmmArgs a) {
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         top_up();
-        wait_slices(inflight - 1);
+        wait_slices<kNbuf - 1>(inflight - 1);
         const char* buf = smem + cbuf * kSliceBytes + a_off;
 #pragma unroll
         for (int p = 0; p < kPairSteps; ++p) {

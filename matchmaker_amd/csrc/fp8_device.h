@@ -2,6 +2,7 @@
 // row quantiser and the LDS-DMA ring slot of one-byte elements.  gfx950 only.
 #pragma once
 #include "mm_internal.h"
+#include "lds_dma_device.h"
 
 namespace mm {
 
@@ -118,10 +119,9 @@ struct Fp8Slot {
 };
 
 // ROWS / 8 + 1 LDS-DMA instructions = one ring slot.  Code instruction k moves 1 KiB, rows 8k..8k+7: 8 lanes per row,
-// each lane one 16-byte chunk of the row's 128-byte slice.  The LDS destination is lane-linear (M0 + lane*16: row-major
-// 128-byte rows), so the bank swizzle is applied on the SOURCE side: the chunk stored at slot p of row R is chunk
-// p ^ ((R >> 1) & 7).  The A-fragment read of K step kk is a ds_read_b64 of half h of chunk kk of row (lane & 31), at slot
-// kk ^ ((R >> 1) & 7).  ds_read_b64 is served in two groups of 32 lanes, and a group has ONE h: its reads touch only the
+// each lane one 16-byte chunk of the row's 128-byte slice (row-major 128-byte rows in LDS).  Source-side bank swizzle (in
+// voff): the chunk stored at slot p of row R is chunk p ^ ((R >> 1) & 7).  The A-fragment read of K step kk is a
+// ds_read_b64 of half h of chunk kk of row (lane & 31), at slot kk ^ ((R >> 1) & 7).  ds_read_b64 is served in two groups of 32 lanes, and a group has ONE h: its reads touch only the
 // 8-byte halves h of the 16-byte chunks, i.e. 32 of the 64 banks, so 32 lanes x 2 banks cannot be conflict-free — 2-way
 // is the floor for this layout.  The swizzle reaches it: 8-byte bank pair = 16 (R & 1) + 2 slot + h, and over the 32 rows
 // of a group (R & 1, (R >> 1) & 7) takes each of its 16 values exactly twice.  Unswizzled (slot = kk for every row) the
@@ -131,78 +131,15 @@ struct Fp8Slot {
 template <int ROWS>
 __device__ __forceinline__ void issue_slot(const uint8_t* gbase, const uint32_t (&voff)[8], const float* sbase, uint32_t soff,
                                            uint32_t lds_dst) {
-  uint32_t keep;
-  if constexpr (ROWS == 64) {
-    asm volatile(
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %12\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %5, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %6, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %7, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %8, %10 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dword %9, %11\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]), "v"(voff[7]),
-          "v"(soff), "s"(gbase), "s"(sbase), "s"(lds_dst)
-        : "memory", "scc");
-  } else {
-    asm volatile(
-        "s_waitcnt lgkmcnt(0)\n\t"
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %8\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, %6 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %2, %6 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %3, %6 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %4, %6 nt\n\t"
-        "s_add_u32 m0, m0, 0x400\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dword %5, %7\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(soff), "s"(gbase), "s"(sbase), "s"(lds_dst)
-        : "memory", "scc");
-  }
+  static_assert(ROWS == 32 || ROWS == 64, "Fp8Slot");
+  uint32_t v[ROWS / 8];
+#pragma unroll
+  for (int n = 0; n < ROWS / 8; ++n) v[n] = voff[n];
+  lds_dma_two<0x400, true, false>(gbase, v, sbase, soff, lds_dst);
 }
 
 // Wait until at most `younger` slots (VM vector-memory operations each) issued after the one we need are pending.
 template <int VM>
-__device__ __forceinline__ void wait_slot(int younger) {
-  switch (younger) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * VM) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * VM) : "memory"); break;
-  }
-}
+__device__ __forceinline__ void wait_slot(int younger) { wait_ring<VM, 3>(younger); }
 
 }  // namespace mm

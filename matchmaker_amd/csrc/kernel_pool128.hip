@@ -31,36 +31,17 @@ constexpr int kS128Steps = 4;
 constexpr int kS128Nbuf = 4;
 
 __device__ __forceinline__ void issue_slice8(const char* gbase, const uint32_t (&v)[kS128Instr], uint32_t lds_dst) {
-  uint32_t keep;
-#define MM_GLDS(N) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #N ", %9 nt\n\ts_add_u32 m0, m0, 0x400\n\t"
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %10\n\t" MM_GLDS(1) MM_GLDS(2) MM_GLDS(3) MM_GLDS(4)
-                   MM_GLDS(5) MM_GLDS(6) MM_GLDS(7) MM_GLDS(8) "s_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]), "s"(gbase),
-                 "s"(lds_dst)
-               : "memory", "scc");
-#undef MM_GLDS
+  lds_dma<0x400, true, true>(gbase, v, lds_dst);
 }
 
 // one dword per lane through the LDS-DMA path into a 256-byte scratch row: a cache-line prefetch that owns no register
 __device__ __forceinline__ void touch_line(const char* gbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dword %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(gbase), "s"(lds_dst)
-               : "memory");
+  lds_dma_one_dword(gbase, voff, lds_dst);
 }
 
-// wait until at most `younger` whole slices are still in flight (extra vector loads in the queue — the
-// query tile, the gate — only make this wait longer, never shorter: completion is in order)
-__device__ __forceinline__ void wait_slices8(int younger) {
-  switch (younger) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-  }
-}
+// wait until at most `younger` whole slices are still in flight (the query tile and the gate, vector loads in the same
+// queue, only make this wait longer)
+__device__ __forceinline__ void wait_slices8(int younger) { wait_ring<kS128Instr, kS128Nbuf - 1>(younger); }
 
 // LDS map of a workgroup of KS waves: [KS rings of NBUF slices][KS x rdbuf 128 B][exchange, KS == 2 only:
 // xacc 2 x 4 KiB | xss 2 x 128 B | xq 2 x 2 x 128 B | xtot 2 x 16 B][KS gate vectors]

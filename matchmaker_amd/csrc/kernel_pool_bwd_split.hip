@@ -64,11 +64,7 @@ struct BwdGeo {
 
 // ONE LDS-DMA instruction: 64 lanes x 16 bytes, global (sbase + voff) -> LDS (m0 + 16 lane)
 __device__ __forceinline__ void glds16(const char* sbase, uint32_t voff, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(sbase), "s"(lds_dst)
-               : "memory");
+  lds_dma_one(sbase, voff, lds_dst);
 }
 
 // barrier for LDS traffic only: __syncthreads() would also drain vmcnt — the LDS-DMA prefetch and the gradient stores in flight
@@ -329,7 +325,7 @@ __global__ void __launch_bounds__(256, 2) kp_bwd_split_kernel(const KpBwdArgs a,
       }
     }
     KPS_PH(1);                                                // block head (masks, gate)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the slice has landed
+    wait_vm(0);                                              // the slice has landed
     KPS_PH(2);                                                // wait for the slice (and the previous block's stores)
 
     // ---- cosines: this wavefront's K range; norms from the very A operands -----------------------------------------------

@@ -1,6 +1,7 @@
 // Device helpers shared by the kernel-pooling translation units (kernel_pool.hip, kernel_pool128.hip).
 #pragma once
 #include "mm_internal.h"
+#include "lds_dma_device.h"
 
 namespace mm {
 
@@ -629,6 +630,27 @@ __device__ __forceinline__ void tkl_publish_slot(const KpArgs& a, int64_t p, int
     if (sl >= 0 && sl < a.n_slots) a.slot2p[sl] = (int32_t)((p << 2) | blocks);
   }
 }
+
+// ---- the slice-25 document stream of the E = 100 n kernels (kernel_pool.hip, drmm.hip) -----------------------------------
+constexpr int kSC = 25;                       // 16-B chunks per row per slice (odd: conflict-free)
+constexpr int kSliceInstr = 13;               // ceil(32*25 / 64) LDS-DMA instructions per slice
+constexpr int kSliceBytes = kSliceInstr * 1024;
+constexpr int kPairSteps = 13;                // chunk pairs per slice (last one half empty)
+
+// one slice of 32 rows -> ring slot lds_dst; `clamp` (a document's last, partial block) redirects the rows past the end to
+// the last chunk of the last real row (vmax): never read past the tensor
+template <bool NT>
+__device__ __forceinline__ void issue_slice(const char* gbase, const uint32_t (&voff)[kSliceInstr], uint32_t vmax,
+                                            bool clamp, uint32_t lds_dst) {
+  uint32_t v[kSliceInstr];
+#pragma unroll
+  for (int n = 0; n < kSliceInstr; ++n) v[n] = clamp ? (voff[n] < vmax ? voff[n] : vmax) : voff[n];
+  lds_dma<0x400, NT, true>(gbase, v, lds_dst);
+}
+
+// MAXY: the most slices a ring keeps in flight behind the one awaited
+template <int MAXY>
+__device__ __forceinline__ void wait_slices(int younger) { wait_ring<kSliceInstr, MAXY>(younger); }
 
 // tkl_stage1_rows.hip: TKL stage 1 with the cosine hand-off, whole chunk rows streamed (E = 100 / 200 / 300, Q <= 32)
 bool tkl_stage1_rows_supported(int Q, int E);

@@ -342,20 +342,8 @@ __global__ void __launch_bounds__(64, 2) maxsim_allpairs_tiled_kernel(const Maxs
 // ---------------------------------------------------------------------------------------------
 template <bool TAIL>
 __device__ __forceinline__ void issue_quarter(const char* gbase, uint32_t v0, uint32_t v1, uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(v0), "v"(v1), "s"(gbase), "s"(lds_dst)
-      : "memory", "scc");
+  const uint32_t v[2] = {v0, v1};
+  lds_dma<0x400, false>(gbase, v, lds_dst);
 }
 
 template <int DT, int NSL, int NQT>

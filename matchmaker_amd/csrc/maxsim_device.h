@@ -3,6 +3,7 @@
 #pragma once
 #include "mm_internal.h"
 #include "elem_device.h"
+#include "lds_dma_device.h"
 
 namespace mm {
 
@@ -169,44 +170,15 @@ __device__ __forceinline__ float finish_sum(float s, int rnd) {
 constexpr int kBlkBytes = 32 * 256;  // 32 document tokens x 128 dims x 2 B
 
 // 8 LDS-DMA instructions = one 8 KiB document block.  Instruction k moves rows 4k..4k+3:
-// 16 lanes per row, each lane one 16-B chunk.  LDS destination is lane-linear (M0 + lane*16), so
-// the bank swizzle is applied on the SOURCE side: the chunk stored at slot p of row r is chunk
-// p ^ (r & 15).  A later ds_read_b128 of chunk c of row (lane & 31) then reads slot c ^ (r & 15):
+// 16 lanes per row, each lane one 16-B chunk.  Source-side bank swizzle (in voff): the chunk stored at slot p of row r
+// is chunk p ^ (r & 15).  A later ds_read_b128 of chunk c of row (lane & 31) then reads slot c ^ (r & 15):
 // every 16-lane service group of the read covers 16 distinct slots of the 256-B bank row.
 template <bool NT>
 __device__ __forceinline__ void issue_block(const char* gbase, const uint32_t (&voff)[8], uint32_t lds_dst) {
-  uint32_t keep;
-#define MM_BLK_LD(N, NTS) "s_nop 0\n\tglobal_load_lds_dwordx4 %" #N ", %9" NTS "\n\t"
-#define MM_BLK_NEXT "s_add_u32 m0, m0, 0x400\n\t"
-#define MM_ISSUE_BLOCK(NTS)                                                                                               \
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %10\n\t" MM_BLK_LD(1, NTS) MM_BLK_NEXT             \
-                   MM_BLK_LD(2, NTS) MM_BLK_NEXT MM_BLK_LD(3, NTS) MM_BLK_NEXT MM_BLK_LD(4, NTS) MM_BLK_NEXT             \
-                       MM_BLK_LD(5, NTS) MM_BLK_NEXT MM_BLK_LD(6, NTS) MM_BLK_NEXT MM_BLK_LD(7, NTS) MM_BLK_NEXT         \
-                           MM_BLK_LD(8, NTS) "s_mov_b32 m0, %0"                                                          \
-               : "=&s"(keep)                                                                                             \
-               : "v"(voff[0]), "v"(voff[1]), "v"(voff[2]), "v"(voff[3]), "v"(voff[4]), "v"(voff[5]), "v"(voff[6]),       \
-                 "v"(voff[7]), "s"(gbase), "s"(lds_dst)                                                                  \
-               : "memory", "scc")
-  if (NT) {
-    MM_ISSUE_BLOCK(" nt");
-  } else {
-    MM_ISSUE_BLOCK("");
-  }
-#undef MM_ISSUE_BLOCK
-#undef MM_BLK_NEXT
-#undef MM_BLK_LD
+  lds_dma<0x400, NT>(gbase, voff, lds_dst);
 }
 
 // Wait until at most `younger` blocks (8 LDS-DMA each) issued after the one we need are pending.
-__device__ __forceinline__ void wait_block(int younger) {
-  switch (younger) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(16)" ::: "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); break;
-    case 4: asm volatile("s_waitcnt vmcnt(32)" ::: "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(40)" ::: "memory"); break;
-  }
-}
+__device__ __forceinline__ void wait_block(int younger) { wait_ring<8, 5>(younger); }
 
 }  // namespace mm

@@ -27,23 +27,7 @@ constexpr int kMaskEntries = 8;    // producer runs at most NBUF + 1 pairs ahead
 // three LDS-DMA instructions: 2 KiB of the document mask row + 1 KiB slot for the query mask row
 __device__ __forceinline__ void issue_masks(const char* dm_row, const uint32_t (&voff_d)[2], const char* qm_row, uint32_t voff_q,
                                             uint32_t lds_dst) {
-  uint32_t keep;
-  asm volatile(
-      "s_waitcnt lgkmcnt(0)\n\t"
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %6\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %4\n\t"
-      "s_add_u32 m0, m0, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %4\n\t"
-      "s_add_u32 m0, m0, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %3, %5\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(voff_d[0]), "v"(voff_d[1]), "v"(voff_q), "s"(dm_row), "s"(qm_row), "s"(lds_dst)
-      : "memory", "scc");
+  lds_dma_two<0x400, false, true>(dm_row, voff_d, qm_row, voff_q, lds_dst);
 }
 
 template <int DT, int NBUF, int NSL, bool I64>

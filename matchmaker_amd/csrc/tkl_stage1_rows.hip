@@ -44,40 +44,16 @@ __device__ __forceinline__ f32x4 mfma16x32(const bf16x8& a, const bf16x8& b, con
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 
-// LDS-DMA instructions of 64 lanes x 16 bytes each, global (sbase + voff + 1024 n) -> LDS (lds_dst + 1024 n + 16 lane).  The
-// instruction offset advances the global AND the LDS address, so four instructions share one M0 / base pair: a 4-KiB group costs
-// 4 + 3 instructions instead of the 5 per instruction of a one-at-a-time wrapper (the wavefront is alone on its SIMD: every
-// instruction it issues is ~10 cycles of its critical path, profiles/r06_experiments/tkl_stage1_rows_phases.txt).
-template <int N>
-__device__ __forceinline__ void glds_group(const char* sbase, uint32_t voff, uint32_t lds_dst) {
-  static_assert(N >= 1 && N <= 4, "instruction offsets reach 3 x 1024");
-  uint32_t keep;
-  if constexpr (N == 4)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:3072\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-  else if constexpr (N == 3)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\tglobal_load_lds_dwordx4 %1, %2 offset:2048\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-  else if constexpr (N == 2)
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:1024\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-  else
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// the NFULL full-width instructions of a unit
+// the NFULL full-width instructions of a unit, four to an M0 / base pair (lds_dma_group): a 4-KiB group costs 4 + 3 instructions
+// instead of the 5 per instruction of a one-at-a-time wrapper (the wavefront is alone on its SIMD: every instruction it issues is
+// ~10 cycles of its critical path, profiles/r06_experiments/tkl_stage1_rows_phases.txt)
 template <int NFULL>
 __device__ __forceinline__ void glds_run(const char* sbase, uint32_t voff, uint32_t lds_dst) {
   if constexpr (NFULL >= 4) {
-    glds_group<4>(sbase, voff, lds_dst);
+    lds_dma_group<4>(sbase, voff, lds_dst);
     glds_run<NFULL - 4>(sbase + 4096, voff, lds_dst + 4096u);
   } else if constexpr (NFULL >= 1) {
-    glds_group<NFULL>(sbase, voff, lds_dst);
+    lds_dma_group<NFULL>(sbase, voff, lds_dst);
   }
 }
 
@@ -129,7 +105,7 @@ __global__ void __launch_bounds__(64) tkl_stage1_rows_kernel(const KpArgs a) {
       const char* g = dbase + (pp * 50 + 5 + kUnitRows * pu) * (int64_t)RB;
       const uint32_t dst = lds0 + (uint32_t)pslot * UB;
       glds_run<NSTEP - 1>(g, vlane, dst);
-      if (lane < tail_lanes) glds_group<1>(g + 1024 * (NSTEP - 1), vlane, dst + 1024u * (NSTEP - 1));
+      if (lane < tail_lanes) lds_dma_one(g + 1024 * (NSTEP - 1), vlane, dst + 1024u * (NSTEP - 1));
       young = (young + 0x01010101u * NSTEP) << 8;
       pslot = (pslot + 1) & (kRing - 1);
       ++inflight;
@@ -252,11 +228,11 @@ __global__ void __launch_bounds__(64) tkl_stage1_rows_kernel(const KpArgs a) {
         if (act) {
           if (i < NSTEP - 1) {
             if (jj == 0 && paired)
-              glds_group<2>(ug + 1024 * i, vlane, ud + 1024u * i);
+              lds_dma_group<2>(ug + 1024 * i, vlane, ud + 1024u * i);
             else
-              glds_group<1>(ug + 1024 * i, vlane, ud + 1024u * i);
+              lds_dma_one(ug + 1024 * i, vlane, ud + 1024u * i);
           } else {
-            if (lane < tail_lanes) glds_group<1>(ug + 1024 * i, vlane, ud + 1024u * i);
+            if (lane < tail_lanes) lds_dma_one(ug + 1024 * i, vlane, ud + 1024u * i);
             young = (young + 0x01010101u * NSTEP) << 8;
             pslot = (pslot + 1) & (kRing - 1);
             ++inflight;
