@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) ah_score_kernel(const IvfArgs a, int roun
     const int nqs = a.cnt[l];
     if (nqs == 0) continue;
     int64_t lb, len;
-    ivf_list_range(a, l, &lb, &len);
+    list_range(a.lb, a.n, l, &lb, &len);
     const int row0 = (t - a.tstart[l]) * 32;
     const int rows = (int)(len - row0 < 32 ? len - row0 : 32);   // >= 1 by construction of the task table
     if (rows <= 0) continue;

@@ -17,6 +17,7 @@
 // Every output element is written once, by one lane; no atomics, nothing read back: graph-capturable, bit-reproducible.
 #include "mm_internal.h"
 #include "bitonic_device.h"
+#include "scan_select_device.h"
 
 namespace mm {
 
@@ -118,28 +119,15 @@ __global__ void __launch_bounds__(kCandThreads, 8) colbert_candidates_kernel(Can
       }
     }
     const int n_mine = __popc(flags);
-    int incl = n_mine;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-      const int t = __shfl_up(incl, o, kWave);
-      if (lane >= o) incl += t;
-    }
-    if (lane == kWave - 1) wtot[wave] = incl;
-    __syncthreads();                                       // also: every lane has read its keys
-    int off = incl - n_mine, c = 0;
-    for (int w = 0; w < nwaves; ++w) {
-      const int t = wtot[w];
-      if (w < wave) off += t;
-      c += t;
-    }
+    int c;                                                 // (the helper's barrier also: every lane has read its keys)
+    int off = block_offset_from_waves(wave_incl_scan(n_mine, lane), n_mine, wtot, lane, wave, nwaves, &c);
 #pragma unroll
     for (int i = 0; i < kCandPer; ++i)
       if (flags >> i & 1u) key[off++] = mine[i];
     __syncthreads();
 
     // ---- 2. the c distinct documents by their index in seq_ids order
-    int c2 = 1;
-    while (c2 < c) c2 <<= 1;
+    const int c2 = pow2_ge(c);
     for (int i = tid; i < c2; i += nt) {
       int32_t d = kCandNone;
       if (i < c) {

@@ -15,6 +15,7 @@
 // and two calls give the same bits.
 #include "mm_internal.h"
 #include "bitonic_device.h"
+#include "scan_select_device.h"
 
 namespace mm {
 
@@ -59,21 +60,10 @@ __global__ void __launch_bounds__(1024) distinct_hits_kernel(const uint32_t* hit
     const uint32_t f = flag[p];
     mine += (f & 1u) + ((f >> 1) << 16);
   }
-  uint32_t inc = mine;
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
-  if (lane == 63) wave_sum[wave] = inc;
-  __syncthreads();
-  uint32_t before = 0, total = 0;
-  for (int w = 0; w < (nt >> 6); ++w) {
-    const uint32_t s = wave_sum[w];
-    before += w < wave ? s : 0u;
-    total += s;
-  }
+  uint32_t total;
+  const uint32_t excl = block_offset_from_waves(wave_incl_scan(mine, lane), mine, wave_sum, lane, wave, nt >> 6, &total);
   const int distinct = (int)(total & 0xffffu), valid = (int)(total >> 16);
-  int rank = (int)((before + inc - mine) & 0xffffu);
+  int rank = (int)(excl & 0xffffu);
   const int64_t o = q * top_n;
   for (int p = p0; p < p1 && rank < top_n; ++p) {
     if (flag[p] & 1u) {
@@ -107,8 +97,7 @@ extern "C" int mm_distinct_hits_fwd(const float* hit_scores, const int64_t* hit_
   if (nq == 0) return MM_OK;
   if (!hit_scores || !hit_ids || !out_scores || !out_ids || !out_pos || !n_distinct || !n_valid)
     return set_error(MM_EINVAL, "distinct_hits: null pointer");
-  int n2 = 1;
-  while (n2 < K) n2 <<= 1;
+  const int n2 = pow2_ge(K);
   const int nt = n2 / 2 > 1024 ? 1024 : (n2 / 2 < 64 ? 64 : n2 / 2);      // a multiple of 64: the scan's wavefronts are whole
   const size_t lds = distinct_lds_bytes(K, n2);
   if (lds > 64 * 1024) {

@@ -897,8 +897,7 @@ __global__ void __launch_bounds__(1024) topk_rows_kernel(const float* __restrict
     }
   }
   if (!in_regs) {
-    int n2 = 2;
-    while (n2 < n) n2 <<= 1;  // sort only as much as survived
+    const int n2 = pow2_ge(n, 2);  // sort only as much as survived
     for (int i = n + tid; i < n2; i += 1024) {
       key[i] = -__builtin_huge_valf();
       val[i] = 0x7fffffff;

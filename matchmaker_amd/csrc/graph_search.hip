@@ -119,23 +119,10 @@ __device__ __forceinline__ void gs_score(const GsArgs& a, const short8 (&qv)[NSL
 // nk[0 .. C) unsorted keys -> merged into the ascending list L [lcap], which is then cut to ef.
 __device__ __forceinline__ void gs_merge(const GsArgs& a, unsigned long long* L, unsigned long long* nk, int C) {
   const int tid = threadIdx.x;
-  int c2 = 1;
-  while (c2 < C) c2 <<= 1;
+  const int c2 = pow2_ge(C);
   for (int i = C + tid; i < c2; i += kGsThreads) nk[i] = kGsEmpty;
   __syncthreads();
-  // bitonic sort, DESCENDING
-  for (int size = 2; size <= c2; size <<= 1)
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int i = tid; i < c2; i += kGsThreads) {
-        const int j = i ^ stride;
-        if (j > i) {
-          const unsigned long long x = nk[i], y = nk[j];
-          const bool down = (i & size) == 0;
-          if ((x < y) == down) { nk[i] = y; nk[j] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  bitonic_desc(nk, c2, tid, kGsThreads);
   // L ascending, (padding, nk) descending: the element-wise minimum is bitonic and holds the lcap smallest keys
   const int off = a.lcap - c2;
   for (int j = tid; j < c2; j += kGsThreads) {
@@ -143,14 +130,7 @@ __device__ __forceinline__ void gs_merge(const GsArgs& a, unsigned long long* L,
     if (y < x) L[off + j] = y;
   }
   __syncthreads();
-  for (int stride = a.lcap >> 1; stride > 0; stride >>= 1) {
-    for (int t = tid; t < (a.lcap >> 1); t += kGsThreads) {
-      const int i = ((t & ~(stride - 1)) << 1) | (t & (stride - 1)), j = i | stride;
-      const unsigned long long x = L[i], y = L[j];
-      if (x > y) { L[i] = y; L[j] = x; }
-    }
-    __syncthreads();
-  }
+  bitonic_merge_asc(L, a.lcap, tid, kGsThreads);
   for (int i = a.ef + tid; i < a.lcap; i += kGsThreads) L[i] = kGsEmpty;
   __syncthreads();
 }

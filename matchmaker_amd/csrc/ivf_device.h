@@ -1,13 +1,16 @@
 // Shared scaffolding of the list-major scans (ivf_scan.hip: 16-bit rows; ah_scan.hip: 4-bit codes; ivf_scan_fp8.hip: e4m3fn
 // codes + row scales): the ragged candidate
 // rows, the 32-row task table, the rounds, the counting sort of the (query, list) pairs by list and the exact radix
-// selection.  A scan supplies its own score kernel (one wavefront per 32-row block of a list, which writes every
-// candidate score of the round) and runs through ivf_run.  Kernels have internal linkage: every translation unit that
-// includes this header gets its own copy of the small ones.
+// selection (its scans and ivf_radix_kth are scan_select_device.h's).  A scan supplies its score kernel (one wavefront per
+// 32-row block of a list, which writes every candidate score of the round) and runs through ivf_run: the two row scans
+// instantiate ivf_score_kernel below over their row source, ah_scan.hip has its own.  Kernels have internal linkage: every
+// translation unit that includes this header gets its own copy of the small ones.
 #pragma once
 #include "mm_internal.h"
 #include "elem_device.h"
 #include "bitonic_device.h"
+#include "fp8_device.h"
+#include "scan_select_device.h"
 
 namespace mm {
 namespace ivf_dev {
@@ -68,23 +71,6 @@ struct IvfArgs {
   int64_t* out_r;           // [nq, k]
 };
 
-__device__ __forceinline__ void ivf_list_range(const IvfArgs& a, int l, int64_t* b, int64_t* len) {
-  int64_t lo = a.lb[l], hi = a.lb[l + 1];
-  lo = lo < 0 ? 0 : (lo > a.n ? a.n : lo);
-  hi = hi < lo ? lo : (hi > a.n ? a.n : hi);
-  *b = lo;
-  *len = hi - lo;
-}
-
-__device__ __forceinline__ int64_t wave_incl_scan(int64_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int64_t t = __shfl_up((long long)v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // one wavefront per query
 static __global__ void __launch_bounds__(256) ivf_rows_kernel(const IvfArgs a) {
   const int lane = threadIdx.x & 63;
@@ -98,42 +84,18 @@ static __global__ void __launch_bounds__(256) ivf_rows_kernel(const IvfArgs a) {
       const int l = a.probes[(int64_t)q * a.nprobe + j];
       if (l >= 0 && l < a.nlist) {
         int64_t b, ln;
-        ivf_list_range(a, l, &b, &ln);
+        list_range(a.lb, a.n, l, &b, &ln);
         len = (int)ln;
       }
     }
     // a row never holds more than n_vectors candidates: lists named twice (an error) are dropped, not written past the buffer
-    int64_t incl = wave_incl_scan(len, lane);
+    int64_t incl = wave_incl_scan<int64_t>(len, lane);
     if (carry + incl > a.n) len = 0;
-    incl = wave_incl_scan(len, lane);
+    incl = wave_incl_scan<int64_t>(len, lane);
     if (j < a.nprobe) a.seg_off[(int64_t)q * a.nprobe + j] = (int32_t)(carry + incl - len);
     carry += __shfl((long long)incl, 63, 64);
   }
   if (lane == 0) a.total[q] = (int32_t)carry;
-}
-
-// exclusive scan of f(i), i < n, by ONE workgroup of 1024 threads; out[n] = the total
-template <typename T, typename F, typename O>
-__device__ void block_excl_scan(F f, O out, int n, T* sh /* [1024] */) {
-  const int tid = threadIdx.x;
-  T carry = 0;
-  for (int i0 = 0; i0 < n; i0 += 1024) {
-    const int i = i0 + tid;
-    const T v = i < n ? f(i) : (T)0;
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const T t = tid >= o ? sh[tid - o] : (T)0;
-      __syncthreads();
-      sh[tid] += t;
-      __syncthreads();
-    }
-    if (i < n) out(i, carry + sh[tid] - v);
-    const T tot = sh[1023];
-    __syncthreads();
-    carry += tot;
-  }
-  if (tid == 0) out(n, carry);
 }
 
 static __global__ void __launch_bounds__(1024) ivf_tasks_kernel(const IvfArgs a) {
@@ -141,7 +103,7 @@ static __global__ void __launch_bounds__(1024) ivf_tasks_kernel(const IvfArgs a)
   block_excl_scan<int>(
       [&](int l) {
         int64_t b, len;
-        ivf_list_range(a, l, &b, &len);
+        list_range(a.lb, a.n, l, &b, &len);
         return (int)((len + 31) >> 5);
       },
       [&](int l, int v) { a.tstart[l] = v; }, a.nlist, sh);
@@ -188,44 +150,6 @@ static __global__ void __launch_bounds__(1024) ivf_lscan_kernel(const IvfArgs a,
   block_excl_scan<int>([&](int l) { return a.cnt[l]; }, [&](int l, int v) { a.start[l] = v; }, a.nlist, sh);
 }
 
-// The `want`-th smallest key (want >= 1) among the elements i < n with ok(i), by ONE workgroup: 4 passes of 8 bits.
-// Returns the key; *below = elements with a smaller key, *ties = elements with that key.
-template <typename OK, typename KEY>
-__device__ uint32_t ivf_radix_kth(int n, int want, OK ok, KEY key, int* hist /* [256] */, int* sh /* [4] */, int* below, int* ties) {
-  const int tid = threadIdx.x, nt = blockDim.x;
-  uint32_t prefix = 0, mask = 0;
-  int remaining = want, less = 0, eq = 0;
-  for (int shift = 24; shift >= 0; shift -= 8) {
-    for (int i = tid; i < 256; i += nt) hist[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += nt) {
-      if (!ok(i)) continue;
-      const uint32_t kx = key(i);
-      if ((kx & mask) == prefix) atomicAdd(hist + ((kx >> shift) & 255u), 1);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      int cum = 0, b = 0;
-      for (; b < 255; ++b) {
-        if (cum + hist[b] >= remaining) break;
-        cum += hist[b];
-      }
-      sh[0] = b; sh[1] = cum; sh[2] = hist[b];
-    }
-    __syncthreads();
-    const int b = sh[0];
-    remaining -= sh[1];
-    less += sh[1];
-    eq = sh[2];
-    prefix |= (uint32_t)b << shift;
-    mask |= 255u << shift;
-    __syncthreads();
-  }
-  *below = less;
-  *ties = eq;
-  return prefix;
-}
-
 static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a, int round, int k2) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* sel = (unsigned long long*)smem;    // [k2] (key << 32 | row), ascending = the output order
@@ -249,7 +173,7 @@ static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a
     }
     const int j = lo - 1;
     int64_t b, len;
-    ivf_list_range(a, pr[j], &b, &len);
+    list_range(a.lb, a.n, pr[j], &b, &len);
     return (uint32_t)(b + (pos - so[j]));
   };
   for (int i = tid; i < k2; i += 1024) sel[i] = ~0ull;
@@ -281,6 +205,87 @@ static __global__ void __launch_bounds__(1024) ivf_select_kernel(const IvfArgs a
     const bool okv = i < kk && e != ~0ull;
     a.out_s[(int64_t)q * k + i] = okv ? desc_unkey((uint32_t)(e >> 32)) : neg_inf();
     a.out_r[(int64_t)q * k + i] = okv ? (int64_t)(uint32_t)e : -1;
+  }
+}
+
+// ---- the score kernel of the row scans (ivf_scan.hip, ivf_scan_fp8.hip) -----------------------------------------------------
+// A row-source policy turns the lane's part of row `trow` into the KS MFMA A fragments (lane (r, h): elements 16 s + 8 h .. + 7
+// of k-step s) and names the factor of the finished dot product.
+
+// 16-bit rows [n, E]: the fragment is the load.
+struct IvfRows16 {
+  static constexpr bool kScaled = false;
+  template <int DT, int KS>
+  static __device__ __forceinline__ void load(const IvfArgs& a, int64_t trow, int h, short8 (&af)[KS], float (&)[16]) {
+    const char* arow = (const char*)a.v + trow * (KS * 32) + h * 16;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) af[s] = *(const short8*)(arow + s * 32);
+  }
+};
+
+// e4m3fn codes [n, E] + row scales [n]: 8 bytes per lane and k-step, converted once to the query's type (cvt8 at scale 1.0:
+// exact); lane r (h = 0) fetches the scale of row r, and 16 cross-lane reads hand every lane the scales of its 16 accumulator
+// rows (register i = row (i & 3) + 8 (i >> 2) + 4 h) — once per block.
+struct IvfRowsFp8 {
+  static constexpr bool kScaled = true;
+  template <int DT, int KS>
+  static __device__ __forceinline__ void load(const IvfArgs& a, int64_t trow, int h, short8 (&af)[KS], float (&sc)[16]) {
+    const uint8_t* arow = (const uint8_t*)a.v + trow * (KS * 16) + h * 8;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) af[s] = cvt8<DT>(*(const u32x2*)(arow + s * 16));
+    const float mine = h == 0 ? a.scales[trow] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) sc[i] = __shfl(mine, rowof(i) + 4 * h, 64);
+  }
+};
+
+// One wavefront per task = 32-row block of a list.  A = the block's rows (ROWS::load), B = 32 of the queries that probe the
+// list (lane (r, h): query r, same elements); D: lane's column = its query, register i = row (i & 3) + 8 (i >> 2) + 4 h.
+// A lane past the end of a partial last block reads the block's LAST row and never stores.
+template <int DT, int NSL, class ROWS>
+__global__ void __launch_bounds__(256) ivf_score_kernel(const IvfArgs a, int round) {
+  constexpr int QB = NSL * 256;   // bytes per query
+  constexpr int KS = NSL * 8;     // k-steps of 16
+  const int qa = a.qbeg[round];
+  if (qa >= a.qbeg[round + 1]) return;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t t = (int64_t)blockIdx.x * 4 + w;
+  if (t >= a.tstart[a.nlist]) return;
+  const int l = a.blk_list[t];
+  const int nqs = a.cnt[l];
+  if (nqs == 0) return;
+  int64_t lb, len;
+  list_range(a.lb, a.n, l, &lb, &len);
+  const int row0 = (int)(t - a.tstart[l]) * 32;
+  const int rows = (int)(len - row0 < 32 ? len - row0 : 32);   // >= 1 by construction of the task table
+  if (rows <= 0) return;
+  const int64_t base0 = a.prefix[qa];
+
+  short8 af[KS];
+  float sc[16];
+  ROWS::template load<DT, KS>(a, lb + row0 + (r < rows ? r : rows - 1), h, af, sc);   // never past the list
+  const int32_t* pl = a.pairs + a.start[l];
+  for (int t0 = 0; t0 < nqs; t0 += 32) {
+    const int qi = t0 + r < nqs ? t0 + r : nqs - 1;
+    const int64_t p = pl[qi];
+    const int q = (int)(p / a.nprobe);
+    const char* qrow = (const char*)a.q + (int64_t)q * QB + h * 16;
+    f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
+#pragma unroll
+    for (int s = 0; s < KS; s += 2) {
+      acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
+      acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
+    }
+    if (t0 + r < nqs) {
+      float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = rowof(i) + 4 * h;
+        if (row < rows) dst[row] = ROWS::kScaled ? (acc0[i] + acc1[i]) * sc[i] : acc0[i] + acc1[i];
+      }
+    }
   }
 }
 

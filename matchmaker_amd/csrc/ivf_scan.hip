@@ -27,72 +27,15 @@
 //                        score, a second radix select over the ROW numbers of the candidates that tie with it (lower row
 //                        first), then a bitonic sort of the k survivors by (score descending, row ascending).
 //
-// The preparation, the grouping and the selection are ivf_device.h's, shared with ah_scan.hip; the score kernel is this
-// file's.
+// The preparation, the grouping and the selection are ivf_device.h's, shared with ah_scan.hip; so is the score kernel, one
+// template with ivf_scan_fp8.hip's, here over the 16-bit row source (IvfRows16).
 //
 // Workspace bound: CAP = min(nq n_vectors, max(2^28, 2 n_vectors)) floats of candidate scores (<= 1 GiB below 2^27
 // vectors) + 12 bytes per (query, probe) pair + 20 bytes per query + 12 bytes per list + 4 bytes per 32-row block.
 #include "ivf_device.h"
 
-namespace mm {
-using namespace ivf_dev;
-
-// One wavefront per task = 32-row block of a list.  A = the block's rows (lane (r, h): row r, elements 16 s + 8 h .. + 7 of
-// k-step s), B = 32 of the queries that probe the list (lane (r, h): query r, same elements); D: lane's column = its query,
-// register i = row (i & 3) + 8 (i >> 2) + 4 h.
-template <int DT, int NSL>
-__global__ void __launch_bounds__(256) ivf_score_kernel(const IvfArgs a, int round) {
-  constexpr int RB = NSL * 256;   // bytes per row
-  constexpr int KS = NSL * 8;     // k-steps of 16
-  const int qa = a.qbeg[round];
-  if (qa >= a.qbeg[round + 1]) return;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t t = (int64_t)blockIdx.x * 4 + w;
-  if (t >= a.tstart[a.nlist]) return;
-  const int l = a.blk_list[t];
-  const int nqs = a.cnt[l];
-  if (nqs == 0) return;
-  int64_t lb, len;
-  ivf_list_range(a, l, &lb, &len);
-  const int row0 = (int)(t - a.tstart[l]) * 32;
-  const int rows = (int)(len - row0 < 32 ? len - row0 : 32);   // >= 1 by construction of the task table
-  if (rows <= 0) return;
-  const int64_t base0 = a.prefix[qa];
-
-  short8 af[KS];
-  {
-    const char* arow = (const char*)a.v + (lb + row0 + (r < rows ? r : rows - 1)) * RB + h * 16;   // never past the list
-#pragma unroll
-    for (int s = 0; s < KS; ++s) af[s] = *(const short8*)(arow + s * 32);
-  }
-  const int32_t* pl = a.pairs + a.start[l];
-  for (int t0 = 0; t0 < nqs; t0 += 32) {
-    const int qi = t0 + r < nqs ? t0 + r : nqs - 1;
-    const int64_t p = pl[qi];
-    const int q = (int)(p / a.nprobe);
-    const char* qrow = (const char*)a.q + (int64_t)q * RB + h * 16;
-    f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
-#pragma unroll
-    for (int s = 0; s < KS; s += 2) {
-      acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
-      acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
-    }
-    if (t0 + r < nqs) {
-      float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = rowof(i) + 4 * h;
-        if (row < rows) dst[row] = acc0[i] + acc1[i];
-      }
-    }
-  }
-}
-
-}  // namespace mm
-
 using namespace mm;
+using namespace mm::ivf_dev;
 
 extern "C" size_t mm_ivf_scan_workspace_bytes(int64_t n_vectors, int nlist, int nq, int nprobe, int k) {
   (void)k;
@@ -118,7 +61,7 @@ extern "C" int mm_ivf_scan_fwd(const void* queries, const void* vectors, const i
     const unsigned grid_score = (unsigned)((g.max_tasks + 3) / 4);
     return with_dtype16(dtype, [&](auto dt) {
       return with_nsl(E, [&](auto nsl) {
-        hipLaunchKernelGGL((ivf_score_kernel<MM_V(dt), MM_V(nsl)>), dim3(grid_score), dim3(256), 0, stream, b, r);
+        hipLaunchKernelGGL((ivf_score_kernel<MM_V(dt), MM_V(nsl), IvfRows16>), dim3(grid_score), dim3(256), 0, stream, b, r);
         return check_launch("ivf_score_kernel");
       });
     });

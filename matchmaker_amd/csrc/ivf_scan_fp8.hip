@@ -8,9 +8,9 @@
 //   score(q, t) = scales[t] * sum_k queries[q, k] * deq(codes[t, k])
 //
 // The preparation, the rounds, the grouping and the selection are ivf_device.h's, shared with ivf_scan.hip and ah_scan.hip;
-// the score kernel is this file's:
+// so is the score kernel, one template with ivf_scan.hip's, here over the fp8 row source (IvfRowsFp8):
 //
-//   ivf_fp8_score_kernel   one wavefront per 32-row block of a list.  The block's codes are read ONCE (8 bytes per lane and
+//   ivf_score_kernel       one wavefront per 32-row block of a list.  The block's codes are read ONCE (8 bytes per lane and
 //                          k-step: 128 NSL bytes per row, half of the 16-bit scan's), converted ONCE to the query's 16-bit
 //                          type (cvt8 at scale 1.0: exact) into the MFMA A fragments and multiplied against every query that
 //                          probes the list, 32 queries per v_mfma_f32_32x32x16 chain.  Every product is exact and the sum is
@@ -24,71 +24,8 @@
 #include "fp8_device.h"
 #include "ivf_device.h"
 
-namespace mm {
-using namespace ivf_dev;
-
-// A = the block's rows (lane (r, h): row r, codes 16 s + 8 h .. + 7 of k-step s, converted), B = 32 of the queries that probe
-// the list (lane (r, h): query r, same elements); D: lane's column = its query, register i = row (i & 3) + 8 (i >> 2) + 4 h.
-template <int DT, int NSL>
-__global__ void __launch_bounds__(256) ivf_fp8_score_kernel(const IvfArgs a, int round) {
-  constexpr int CB = NSL * 128;   // bytes per row of codes
-  constexpr int QB = NSL * 256;   // bytes per query
-  constexpr int KS = NSL * 8;     // k-steps of 16
-  const int qa = a.qbeg[round];
-  if (qa >= a.qbeg[round + 1]) return;
-  const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = lane & 31, h = lane >> 5;
-  const int64_t t = (int64_t)blockIdx.x * 4 + w;
-  if (t >= a.tstart[a.nlist]) return;
-  const int l = a.blk_list[t];
-  const int nqs = a.cnt[l];
-  if (nqs == 0) return;
-  int64_t lb, len;
-  ivf_list_range(a, l, &lb, &len);
-  const int row0 = (int)(t - a.tstart[l]) * 32;
-  const int rows = (int)(len - row0 < 32 ? len - row0 : 32);   // >= 1 by construction of the task table
-  if (rows <= 0) return;
-  const int64_t base0 = a.prefix[qa];
-
-  short8 af[KS];
-  float sc[16];
-  {
-    const int64_t trow = lb + row0 + (r < rows ? r : rows - 1);   // never past the list
-    const uint8_t* arow = (const uint8_t*)a.v + trow * CB + h * 8;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) af[s] = cvt8<DT>(*(const u32x2*)(arow + s * 16));
-    // lane r (h = 0) holds the scale of row r; register i of a lane is row (i & 3) + 8 (i >> 2) + 4 h
-    const float mine = h == 0 ? a.scales[trow] : 0.0f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) sc[i] = __shfl(mine, rowof(i) + 4 * h, 64);
-  }
-  const int32_t* pl = a.pairs + a.start[l];
-  for (int t0 = 0; t0 < nqs; t0 += 32) {
-    const int qi = t0 + r < nqs ? t0 + r : nqs - 1;
-    const int64_t p = pl[qi];
-    const int q = (int)(p / a.nprobe);
-    const char* qrow = (const char*)a.q + (int64_t)q * QB + h * 16;
-    f32x16 acc0 = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, acc1 = acc0;
-#pragma unroll
-    for (int s = 0; s < KS; s += 2) {
-      acc0 = Mfma32x16<DT>::run(af[s], *(const short8*)(qrow + s * 32), acc0);
-      acc1 = Mfma32x16<DT>::run(af[s + 1], *(const short8*)(qrow + (s + 1) * 32), acc1);
-    }
-    if (t0 + r < nqs) {
-      float* dst = a.cand + (a.prefix[q] - base0) + a.seg_off[p] + row0;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int row = rowof(i) + 4 * h;
-        if (row < rows) dst[row] = (acc0[i] + acc1[i]) * sc[i];
-      }
-    }
-  }
-}
-
-}  // namespace mm
-
 using namespace mm;
+using namespace mm::ivf_dev;
 
 extern "C" size_t mm_ivf_scan_fp8_workspace_bytes(int64_t n_rows, int nlist, int nq, int nprobe, int k) {
   (void)k;
@@ -118,7 +55,7 @@ extern "C" int mm_ivf_scan_fp8_fwd(const void* queries, const uint8_t* codes, co
     const unsigned grid_score = (unsigned)((g.max_tasks + 3) / 4);
     return with_dtype16(q_dtype, [&](auto dt) {
       return with_nsl(E, [&](auto nsl) {
-        hipLaunchKernelGGL((ivf_fp8_score_kernel<MM_V(dt), MM_V(nsl)>), dim3(grid_score), dim3(256), 0, stream, b, r);
+        hipLaunchKernelGGL((ivf_score_kernel<MM_V(dt), MM_V(nsl), IvfRowsFp8>), dim3(grid_score), dim3(256), 0, stream, b, r);
         return check_launch("ivf_fp8_score_kernel");
       });
     });

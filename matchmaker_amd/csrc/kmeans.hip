@@ -28,6 +28,7 @@
 //     kms_combine_kernel     one workgroup per list: zeros for an empty list, the chunks of a long list added in ascending order
 #include "mm_internal.h"
 #include "elem_device.h"
+#include "scan_select_device.h"
 
 namespace mm {
 
@@ -134,40 +135,15 @@ struct KmsArgs {
   float* sums;              // [nlist, E]
 };
 
-__device__ __forceinline__ void kms_list_range(const KmsArgs& a, int l, int64_t* b, int64_t* len) {
-  int64_t lo = a.lb[l], hi = a.lb[l + 1];
-  lo = lo < 0 ? 0 : (lo > a.n ? a.n : lo);
-  hi = hi < lo ? lo : (hi > a.n ? a.n : hi);
-  *b = lo;
-  *len = hi - lo;
-}
-
 __global__ void __launch_bounds__(1024) kms_tasks_kernel(const KmsArgs a) {
   __shared__ int sh[1024];
-  const int tid = threadIdx.x;
-  int carry = 0;
-  for (int l0 = 0; l0 < a.nlist; l0 += 1024) {
-    const int l = l0 + tid;
-    int v = 0;
-    if (l < a.nlist) {
-      int64_t b, len;
-      kms_list_range(a, l, &b, &len);
-      v = (int)((len + kKmSplit - 1) / kKmSplit);
-    }
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {
-      const int t = tid >= o ? sh[tid - o] : 0;
-      __syncthreads();
-      sh[tid] += t;
-      __syncthreads();
-    }
-    if (l < a.nlist) a.tstart[l] = carry + sh[tid] - v;
-    const int tot = sh[1023];
-    __syncthreads();
-    carry += tot;
-  }
-  if (tid == 0) a.tstart[a.nlist] = carry;
+  block_excl_scan<int>(
+      [&](int l) {
+        int64_t b, len;
+        list_range(a.lb, a.n, l, &b, &len);
+        return (int)((len + kKmSplit - 1) / kKmSplit);
+      },
+      [&](int l, int v) { a.tstart[l] = v; }, a.nlist, sh);
 }
 
 template <int DT>
@@ -184,7 +160,7 @@ __global__ void __launch_bounds__(256) kms_partial_kernel(const KmsArgs a) {
   }
   const int l = lo;
   int64_t lbeg, len;
-  kms_list_range(a, l, &lbeg, &len);
+  list_range(a.lb, a.n, l, &lbeg, &len);
   const int nch = a.tstart[l + 1] - a.tstart[l];
   const int c = (int)(t - a.tstart[l]);
   const int64_t p0 = lbeg + (int64_t)c * kKmSplit;

@@ -70,8 +70,7 @@ __global__ void seg_rank_block_kernel(const void* scores, const int64_t* sb, int
   seg_range(sb, blockIdx.x, n, &beg, &len64);
   if (len64 <= 64 || len64 > cap) return;      // the wavefront kernel's (uniform over the workgroup: no barrier is skipped)
   const int len = (int)len64;
-  int n2 = 128;
-  while (n2 < len) n2 <<= 1;                    // <= the LDS of the launch: len <= cap <= its power of two
+  const int n2 = pow2_ge(len, 128);             // <= the LDS of the launch: len <= cap <= its power of two
   for (int i = tid; i < n2; i += nt) rank_keys[i] = i < len ? rank_key(load_elem<DT>(scores, beg + i), i) : kPadKey;
   bitonic_asc(rank_keys, n2, tid, nt);
   for (int i = tid; i < len; i += nt) order[beg + i] = (int32_t)(beg + (int64_t)(uint32_t)rank_keys[i]);
@@ -261,8 +260,7 @@ extern "C" int mm_segment_rank_fwd(const void* scores, int dtype, const int64_t*
     hipLaunchKernelGGL(seg_rank_wave_kernel<MM_V(dt)>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream, scores, seg_begin,
                        n_rows, nq, max_len, order);
     if (max_len > 64) {
-      int n2 = 128;
-      while (n2 < max_len) n2 <<= 1;
+      const int n2 = pow2_ge(max_len, 128);
       const int nt = n2 / 2 > 1024 ? 1024 : n2 / 2;      // one comparator per thread per pass up to 2,048 rows
       hipLaunchKernelGGL(seg_rank_block_kernel<MM_V(dt)>, dim3((unsigned)nq), dim3(nt), (size_t)n2 * 8, stream, scores, seg_begin,
                          n_rows, max_len, order);

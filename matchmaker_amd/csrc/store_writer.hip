@@ -18,6 +18,7 @@
 #include "mm_internal.h"
 #include "elem_device.h"
 #include "fp8_device.h"
+#include "scan_select_device.h"
 
 namespace mm {
 
@@ -100,13 +101,7 @@ __global__ void __launch_bounds__(1024) store_scan_kernel(const StoreArgs a) {
   int32_t s = 0;
   for (int w = w0; w < w1; ++w) s += __popcll(a.bits[w]);
   part[t] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {
-    const int32_t v = t >= o ? part[t - o] : 0;
-    __syncthreads();
-    part[t] += v;
-    __syncthreads();
-  }
+  block_incl_scan_lds(part, t);
   int32_t run = part[t] - s;
   for (int w = w0; w < w1; ++w) {
     a.pre[w] = run;

@@ -80,6 +80,14 @@ def short_union_probes():
 SHORT_FOUND = [16, 0, 17, 31, 0]
 
 
+def tie_problem():
+    """tests/ivf_reference.py's tie problem with its rows quantised (integers up to 7: exact in e4m3fn under a power-of-two
+    scale) -> (q, codes [n, 128] uint8, scales [n] float32, list_begin, probes, k, the tie group's rows ascending)"""
+    q, v, lb, probes, k, group = IR.tie_problem()
+    codes, scales = F.quantize_torch(torch.from_numpy(v).half())
+    return q, codes.numpy(), scales.numpy(), lb, probes, k, group
+
+
 # ---- random unit rows -----------------------------------------------------------------------------------------------------
 def random_problem(dtype, E, nq=40, nprobe=6, seed=7):
     """unit rows over LENS quantised by the restated quantiser, unit queries rounded to `dtype`, probes as above"""

@@ -199,6 +199,47 @@ def test_refuses_small_training_sets_fp32_and_subsamples_reproducibly():
     assert torch.equal(a.centroids, b.centroids)              # a fixed seed gives a reproducible index
 
 
+# ---- the two exact problems of the GPU suite: the restatement against a plain sort ---------------------------------------
+
+def _sorted_topk(q, v, lb, probes, k):
+    """(score descending, row ascending) by one lexsort per query; nothing of ivf_reference.ivf_scan is used"""
+    out_s, out_r = np.full((q.shape[0], k), -np.inf), np.full((q.shape[0], k), -1, np.int64)
+    for i in range(q.shape[0]):
+        rows = np.array(sorted(r for l in probes[i] if l >= 0 for r in range(lb[l], lb[l + 1])), np.int64)
+        s = v[rows].astype(np.float64) @ q[i].astype(np.float64)
+        order = np.lexsort((rows, -s))[:k]
+        out_s[i, : order.size], out_r[i, : order.size] = s[order], rows[order]
+    return out_s, out_r
+
+
+def test_carry_problem_reaches_past_the_tile_and_the_restatement_equals_a_plain_sort():
+    q, v, lb, probes, k = IR.carry_problem()
+    lens = np.diff(lb)
+    assert lens.size == 1030 and q.shape == (1030, 128) and lb[-1] == v.shape[0] == 2000 and probes.shape == (1030, 3) and k == 5
+    assert (lens == 0).sum() >= 5 and np.median(lens) in (1, 2)
+    for i in range(1024, 1030):                                  # queries behind the tile probe non-empty lists behind the tile
+        assert any(l >= 1024 and lens[l] > 0 for l in probes[i]), i
+    assert all(len(set(p.tolist())) == 3 for p in probes)
+    assert np.abs(v).max() <= 2 and np.abs(q).max() <= 2         # |score| <= 512: exact in fp16 inputs and any fp32 order
+    ref_s, ref_r = IR.ivf_scan(q, v, lb, probes, k)
+    srt_s, srt_r = _sorted_topk(q, v, lb, probes, k)
+    assert np.array_equal(ref_r, srt_r) and np.array_equal(ref_s, srt_s)
+    assert (ref_r[:, -1] == -1).any() and (ref_r[:, -1] >= 0).any()      # unions shorter and longer than k
+
+
+def test_tie_problem_has_40_ties_from_rank_8_and_the_restatement_equals_a_plain_sort():
+    q, v, lb, probes, k, group = IR.tie_problem()
+    assert k == 10 and group.size == 40 and (v[group] == v[group[0]]).all()
+    in_list = [int(((group >= lb[l]) & (group < lb[l + 1])).sum()) for l in range(lb.size - 1)]
+    assert in_list == [0, 20, 0, 0, 20] and set(probes[0].tolist()) == {4, -1, 1}
+    ref_s, ref_r = IR.ivf_scan(q, v, lb, probes, k)
+    srt_s, srt_r = _sorted_topk(q, v, lb, probes, k)
+    assert np.array_equal(ref_r, srt_r) and np.array_equal(ref_s, srt_s)
+    assert ref_s[0].tolist() == [7, 6, 5, 4, 3, 2, 1, 0, 0, 0] and ref_r[0, 7:].tolist() == group[:3].tolist()
+    full = v[np.concatenate([np.arange(lb[1], lb[2]), np.arange(lb[4], lb[5])])] @ q[0]
+    assert (full == 0).sum() == 40 and (full > 0).sum() == 7     # nothing else ties with the group
+
+
 # ---- sharded IVF index under gloo ---------------------------------------------------------------------
 
 def _free_port():

@@ -443,6 +443,21 @@ def test_exact_cases_are_exact_in_fp32_and_hold_ties(E, nq, k):
         assert at_cut > 0
 
 
+def test_tie_problem_keeps_its_40_ties_from_rank_8_when_quantised():
+    q, codes, scales, lb, probes, k, group = I8.tie_problem()
+    assert (codes[group] == codes[group[0]]).all() and (scales[group] == scales[group[0]]).all()
+    _, v, _, _, _, _ = IR.tie_problem()
+    assert np.array_equal(F.dequantize_numpy(codes, scales), v)            # the quantisation is exact: the scores are the 16-bit ones
+    ref_s, ref_r = I8.ivf_scan_fp8(q, codes, scales, lb, probes, k)
+    full = R.scores64(q, codes, scales)
+    for i in range(q.shape[0]):                                            # the restatement against a plain (score, row) sort
+        rows = IR.union_rows(lb, probes[i])
+        order = np.lexsort((rows, -full[i, rows]))[:k]
+        assert np.array_equal(ref_r[i], rows[order]) and np.array_equal(ref_s[i], full[i, rows][order])
+    assert ref_s[0].tolist() == [7, 6, 5, 4, 3, 2, 1, 0, 0, 0] and ref_r[0, 7:].tolist() == group[:3].tolist()
+    assert (full[0, IR.union_rows(lb, probes[0])] == 0).sum() == 40
+
+
 def test_short_union_case_finds_16_0_17_31_0():
     lb = I8.list_begin()
     assert [IR.union_rows(lb, p).size for p in I8.short_union_probes()] == I8.SHORT_FOUND

@@ -51,6 +51,16 @@ def test_scan_equals_the_restatement_bit_for_bit_on_the_exact_store(dtype, E, nq
     assert np.array_equal(s, ref_s)                                        # (-inf pads compare equal)
 
 
+def test_more_ties_at_the_kth_score_than_fit_keep_the_lowest_rows():
+    """tests/ivf_reference.py's tie problem, quantised: identical rows have identical codes and scales, so the 40 rows still
+    tie from rank 8 on and the three lowest of them close the ten results."""
+    q, codes, scales, lb, probes, k, group = I8.tie_problem()
+    s, r = _scan(q, codes, scales, lb, probes, k, torch.float16)
+    ref_s, ref_r = I8.ivf_scan_fp8(q, codes, scales, lb, probes, k)
+    assert np.array_equal(r, ref_r) and np.array_equal(s, ref_s.astype(np.float32))
+    assert r[0, 7:].tolist() == group[:3].tolist() and (s[0, 7:] == s[0, 7]).all() and s[0, 6] > s[0, 7]
+
+
 # ---- 2. the same bits as the 16-bit scan over the dequantised rows ----------------------------------------------------------
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("E,nq,k", [(128, 37, 10), (768, 37, 1000)])

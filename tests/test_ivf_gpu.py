@@ -90,6 +90,36 @@ def test_ivf_scan_k_larger_than_the_union_and_empty_rows():
     assert [(r >= 0).sum() for r in rows] == [16, 0, 17, 31, 0]
 
 
+def _scan_exact(q, v, lb, probes, k):
+    """the fp16 scan of an integer-valued problem (exact in fp16 and in any fp32 summation order) -> numpy scores, rows"""
+    from matchmaker_amd import ops
+    dev = util.require_gpu()
+    s, rows = ops.ivf_scan(torch.from_numpy(q).half().to(dev), torch.from_numpy(v).half().to(dev), torch.from_numpy(lb).to(dev),
+                           torch.from_numpy(probes).to(dev), k)
+    return s.cpu().numpy(), rows.cpu().numpy()
+
+
+def test_block_scans_carry_past_their_1024_thread_tile_bit_for_bit():
+    """1,030 lists and 1,030 queries: ivf_tasks_kernel, ivf_lscan_kernel (over the lists) and ivf_chunks_kernel (over the
+    queries) each scan one tile of 1,024 and carry into a second one, whose lists and queries are probed and answered."""
+    q, v, lb, probes, k = IR.carry_problem()
+    s, rows = _scan_exact(q, v, lb, probes, k)
+    ref_s, ref_r = IR.ivf_scan(q, v, lb, probes, k)
+    assert np.array_equal(rows, ref_r), f"rows differ for queries {np.nonzero((rows != ref_r).any(axis=1))[0][:10]}"
+    assert np.array_equal(s, ref_s.astype(np.float32))                     # (-inf pads compare equal)
+    assert (rows[1024:, 0] >= lb[1024]).any()                               # rows of the lists behind the tile are returned
+
+
+def test_more_ties_at_the_kth_score_than_fit_keep_the_lowest_rows():
+    """40 bit-identical rows over two probed lists tie from rank 8 on, k = 10: the second radix selection (over the row
+    numbers of the candidates that tie with the k-th score) keeps the three lowest rows of the group."""
+    q, v, lb, probes, k, group = IR.tie_problem()
+    s, rows = _scan_exact(q, v, lb, probes, k)
+    ref_s, ref_r = IR.ivf_scan(q, v, lb, probes, k)
+    assert np.array_equal(rows, ref_r) and np.array_equal(s, ref_s.astype(np.float32))
+    assert rows[0, 7:].tolist() == group[:3].tolist() and (s[0, 7:] == s[0, 7]).all() and s[0, 6] > s[0, 7]
+
+
 def _clustered_index(dev, n=30000, E=128, nlist=200, nprobe=5, seed=21):
     from matchmaker_amd.retrieval import FlatIPIndexer, IVFFlatIPIndexer
     x, centres = IR.clustered(n, E, nlist, seed, spread=1.0)
